@@ -8,9 +8,16 @@ step and GPU, built from ten independent instances of the 1 000-locus config.  E
 seeds) rotate through the timed region, so that nothing adaptive inside the library (candidate-window level, band
 probation, history-sized grids) is replaying one input.
 
-    python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W [--strong --config 4|5]
+
+A plain run does only what the headline needs: it generates the batches, primes and warms up, times the K steps and prints
+the line.  --full adds everything else this script measures or checks: the CPU baseline, one call at a time
+with its un-overlapped kernel durations and the roofline / VALU figures built on them, the host-buffer entry point, the
+end-to-end run from files, BASELINE's other configurations and the oracle parity checks.  --dump-outputs DIR writes what the
+last timed step returned to its caller (cn, score, n_iters, start per read) as DIR/<name>.npy in float64; the inputs are
+seeded, so two builds can be compared output for output.
 
 Default (weak scaling): every rank owns its own batches; the per-read results of every step are collected on every
 rank with one RCCL all-gather per `--gather-every` steps.  --strong: ONE catalog (the named config at its full size)
@@ -68,13 +75,20 @@ def _gen_worker(args):
     return make_config(cfg, n_loci=n_loci, seed_shift=seed_shift)
 
 
-def make_batches(cfg: int, n_loci: int, n_batches: int, rank: int, pool) -> list:
+def make_batches(cfg: int, n_loci: int, n_batches: int, rank: int, pool, meanwhile=None) -> list:
     """`n_batches` distinct batches of `n_loci` loci of config `cfg`: each is the concatenation of independent
-    instances of <= 1 000 loci (seed shifts unique per rank, batch and instance), generated on all host cores."""
+    instances of <= 1 000 loci (seed shifts unique per rank, batch and instance), generated on all host cores.
+    `meanwhile()` runs in this process while the pool's workers generate."""
     from strkit_amd.synth import LocusBatch
     per = [min(UNIT_LOCI, n_loci - k) for k in range(0, n_loci, UNIT_LOCI)]
     jobs = [(cfg, n, (rank * 64 + b) * 1024 + j) for b in range(n_batches) for j, n in enumerate(per)]
-    parts = pool.map(_gen_worker, jobs) if pool is not None else [_gen_worker(j) for j in jobs]
+    if pool is not None:
+        pending = pool.map_async(_gen_worker, jobs)
+        if meanwhile is not None:
+            meanwhile()
+        parts = pending.get()
+    else:
+        parts = [_gen_worker(j) for j in jobs]
     return [LocusBatch.concat(parts[b * len(per):(b + 1) * len(per)]) for b in range(n_batches)]
 
 
@@ -290,6 +304,26 @@ def progress(msg: str) -> None:
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
 
+DUMP_FIELDS = ("cn", "score", "n_iters", "start")
+DUMP_MAX_BYTES = 60_000_000         # the data of all the files of a --dump-outputs directory (every rank's share): under 64 MB with the headers
+
+
+def dump_outputs(out_dir: str, table: np.ndarray, max_bytes: int, prefix: str = "") -> None:
+    """Writes int32[4, n_reads] (cn, score, n_iters, start per read) as <prefix><field>.npy in float64 (exact for int32).
+    Past `max_bytes` a fixed, seeded sample of the reads is written instead, with their indices in <prefix>sample_index.npy."""
+    n = table.shape[1]
+    cap = max_bytes // (8 * (len(DUMP_FIELDS) + 1))
+    idx = None
+    if n * 8 * len(DUMP_FIELDS) > max_bytes:
+        idx = np.sort(np.random.default_rng(20261016).choice(n, size=cap, replace=False))
+        table = table[:, idx]
+    os.makedirs(out_dir, exist_ok=True)
+    for k, name in enumerate(DUMP_FIELDS):
+        np.save(os.path.join(out_dir, f"{prefix}{name}.npy"), table[k].astype(np.float64))
+    if idx is not None:
+        np.save(os.path.join(out_dir, f"{prefix}sample_index.npy"), idx.astype(np.float64))
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -316,6 +350,9 @@ def main() -> None:
     ap.add_argument("--e2e-loci", type=int, default=10000)
     ap.add_argument("--e2e-depth", type=int, default=30)
     ap.add_argument("--e2e-read-len", type=int, default=15000)
+    ap.add_argument("--full", action="store_true", help="also the CPU baseline, the extras (one call at a time, host buffers, end to end, "
+                    "other configurations; --no-* switch them off one by one), the roofline / VALU figures and the oracle parity checks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's per-read results to DIR/<name>.npy")
     a = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -333,22 +370,29 @@ def main() -> None:
     cores = max(1, min(16, len(os.sched_getaffinity(0)) // max(1, min(world, 8))))
     cpu = None
     with mp.get_context("fork").Pool(cores) as pool:
-        if rank == 0 and a.gpus == 1 and not a.no_cpu_baseline:
+        if a.full and rank == 0 and a.gpus == 1 and not a.no_cpu_baseline:
             import oracle
             oracle.build()
             progress("cpu baseline")
             cpu = cpu_baseline(a.config, a.cpu_sample_loci, pool, cores)
         progress("generating batches")
+
+        def import_torch():
+            # (an import initialises no GPU, and the pool's workers were forked before it: the first import of torch in a
+            # fresh process can take seconds, which the generation hides; --full forks more processes later, so not there)
+            import torch  # noqa: F401
+            import torch.distributed  # noqa: F401
+        meanwhile = None if a.full else import_torch
         if a.strong:
-            catalog = make_batches(a.config, n_loci, 1, 0, pool)[0]      # the same catalog on every rank
+            catalog = make_batches(a.config, n_loci, 1, 0, pool, meanwhile)[0]      # the same catalog on every rank
         else:
-            batches = make_batches(a.config, n_loci, max(1, a.batches), rank, pool)
+            batches = make_batches(a.config, n_loci, max(1, a.batches), rank, pool, meanwhile)
         sub_batches = {}
-        if rank == 0 and a.gpus == 1 and not a.no_extras and not a.no_configs and not a.strong and a.config == 2 and a.loci is None:
+        if a.full and rank == 0 and a.gpus == 1 and not a.no_extras and not a.no_configs and not a.strong and a.config == 2 and a.loci is None:
             for name, (c, nl, _) in SUB_CONFIGS.items():     # the other single-GPU configurations of BASELINE.json, two batches each
                 sub_batches[name] = make_batches(c, nl, 2, 7, pool)
     e2e_data = None
-    if rank == 0 and a.gpus == 1 and not a.no_e2e and not a.strong:
+    if a.full and rank == 0 and a.gpus == 1 and not a.no_e2e and not a.strong:
         # files for the end-to-end sub-result: north_star's "10 000 loci x 30x HiFi reads genotyped end-to-end", ~15 kb reads
         import tempfile
         from strkit_amd.frontend.synth_large import make_dataset_large
@@ -365,6 +409,7 @@ def main() -> None:
     from strkit_amd.batch import batch_struct, make_params
     from strkit_amd.sharding import NF, deal_blocks, gathered_step_table, select_loci, share_sizes, step_rows
 
+    progress("device set-up")
     torch.cuda.set_device(local_rank)
     dev = torch.device("cuda", local_rank)
     use_dist = world > 1 or a.force_dist
@@ -515,6 +560,17 @@ def main() -> None:
         reads_all, loci_all = int(tot[0]), int(tot[1])
     else:
         reads_all, loci_all = acc["reads"], acc["loci"]
+    strong_table = None
+    if a.strong and rank == 0:      # the last step's table of the whole catalog, by global read index
+        strong_table = (gathered_step_table(gathered.cpu().numpy(), world, G, last % G, catalog.n_reads) if use_dist else
+                        gathered_step_table(out_last.cpu().numpy(), 1, 1, 0, catalog.n_reads))
+    if a.dump_outputs:
+        # what the last timed step handed its caller: the whole catalog's table (strong, rank 0), else every rank's own batch
+        if strong_table is not None:
+            dump_outputs(a.dump_outputs, strong_table, DUMP_MAX_BYTES)
+        elif not a.strong:
+            dump_outputs(a.dump_outputs, out_last[1:5, :batches[batch_of(last)].n_reads].cpu().numpy(), DUMP_MAX_BYTES // world,
+                         f"rank{rank}_" if world > 1 else "")
 
     # ---- sub-results outside the timed region (rank 0 of a one-GPU run) -------------------------------------------
     def one_at_a_time(res_list, blist, n_calls, out_rows):
@@ -539,7 +595,7 @@ def main() -> None:
 
     extras = {}
     iso = None
-    if rank == 0 and world == 1 and not a.no_extras:
+    if a.full and rank == 0 and world == 1 and not a.no_extras:
         # (a) one call at a time on one context: no overlap between calls; its per-kernel durations are un-overlapped
         progress("extras: one call at a time, host-buffer entry point")
         n1 = max(4, min(a.steps, 16))
@@ -638,16 +694,11 @@ def main() -> None:
     strong_check = None
     if a.strong and rank == 0:
         # the gathered table of the last step against this rank counting the WHOLE catalog alone, bit for bit
-        j = last % G
-        if use_dist:
-            table = gathered_step_table(gathered.cpu().numpy(), world, G, j, catalog.n_reads)
-        else:
-            table = gathered_step_table(out_last.cpu().numpy(), 1, 1, 0, catalog.n_reads)
         _t, sb_all = resident(catalog)
         one = torch.zeros((4, catalog.n_reads), dtype=torch.int32, device=dev)
         _lib.check(L.strk_count_loci_device(ctxs[0].handle, C.byref(sb_all), C.byref(p), one[0].data_ptr(), one[1].data_ptr(),
                                             one[2].data_ptr(), one[3].data_ptr(), None, C.byref(st)))
-        strong_check = "identical" if np.array_equal(table, one.cpu().numpy()) else "MISMATCH"
+        strong_check = "identical" if np.array_equal(strong_table, one.cpu().numpy()) else "MISMATCH"
 
     def parity_check(bl, got4):
         """The device's answers (int32[4, >= n]: cn, score, n_iters, start) on the first loci of batch `bl` against the oracle
@@ -732,12 +783,13 @@ def main() -> None:
         extras["configs"] = configs_out
 
     if rank == 0:
-        # sanity: the timed path's answers on the first loci of the last step agree with the oracle (checker only)
-        parity = parity_check(batches[batch_of(last)], out_last[1:5].cpu().numpy())
         n = max(1, acc["n"])
-        plain = a.loci is None and not a.no_dedupe and not a.no_band and not a.strong and a.window == 0
-        roof = roofline_block(a.config, acc, iso, acc["n"], plain)
-        dp_ms_un = sum(iso[k] for k, _ in DP_KERNELS) if iso else None
+        if a.full:
+            # sanity: the timed path's answers on the first loci of the last step agree with the oracle (checker only)
+            parity = parity_check(batches[batch_of(last)], out_last[1:5].cpu().numpy())
+            plain = a.loci is None and not a.no_dedupe and not a.no_band and not a.strong and a.window == 0
+            roof = roofline_block(a.config, acc, iso, acc["n"], plain)
+            dp_ms_un = sum(iso[k] for k, _ in DP_KERNELS) if iso else None
         b0 = batches[0]
         wl = (f"cfg{a.config} shape" + (" (1000 loci x 30 HiFi reads, motif 3-6 bp, flank 70)" if a.config == 2 else "") +
               (f": ONE catalog of {catalog.n_loci} loci dealt to {world} rank(s) in blocks of <= 200 loci by estimated cells" if a.strong else
@@ -747,16 +799,16 @@ def main() -> None:
             "metric": "reads/sec realigned", "value": reads_all / elapsed, "unit": "reads/s",
             "n_gpus": a.gpus, "steps": a.steps, "warmup": a.warmup, "ms_per_step": elapsed / a.steps * 1e3,
             "higher_is_better": True, "scaling": "strong" if a.strong else "weak", "vs_baseline": None, "dtype": "int32",
-            "data": "synthetic",
+            "data": "synthetic", "full": a.full,
             "config": {"workload": wl, "loci_per_step_per_gpu": b0.n_loci, "reads_per_step_per_gpu": b0.n_reads,
                        "distinct_batches": NB, "window": sorted(acc["windows"]), "window_by_motif_bucket": bucket_windows(acc),
                        "parallelism": f"loci-sharded x{a.gpus}" + (f" + all_gather every {G} steps" if use_dist else ""),
                        "calls_in_flight": D},
             "loci_per_s": loci_all / elapsed,
-            "roofline": roof,
-            "valu": {"gcups": (iso["cells"] / max(dp_ms_un, 1e-9) / 1e6) if iso else None, "cells_per_step": acc["cells"] / n,
-                     "unit": "G cell updates/s: cells the DP kernels executed per call / the summed un-overlapped durations of all five "
-                             "DP kernels (one call at a time)"},
+            **({"roofline": roof,
+                "valu": {"gcups": (iso["cells"] / max(dp_ms_un, 1e-9) / 1e6) if iso else None, "cells_per_step": acc["cells"] / n,
+                         "unit": "G cell updates/s: cells the DP kernels executed per call / the summed un-overlapped durations of all five "
+                                 "DP kernels (one call at a time)"}} if a.full else {}),
             "device_ms_per_step": acc["all_ms"] / n,
             # event spans inside the timed region, where calls_in_flight calls share the device (a span includes the wait for
             # the other call's kernels): where a call's time goes when calls overlap
@@ -765,9 +817,9 @@ def main() -> None:
             "window_miss_reads_per_step": acc["misses"] / n, "generic_kernel_items_per_step": acc["fallback"] / n,
             "dedup_reads_per_step": acc["dedup"] / n, "dedupe": not a.no_dedupe,
             **extras,
-            "parity_check": parity,
+            **({"parity_check": parity} if a.full else {}),
             **({"strong_scaling_check": strong_check} if a.strong else {}),
-            "cpu_baseline": cpu,
+            **({"cpu_baseline": cpu} if a.full else {}),
         }
         print(json.dumps(line), flush=True)
     if use_dist:

@@ -59,7 +59,7 @@ def main():
         line = out.stdout.strip() or out.stderr.strip()[-300:]
         print(f"{name:16s} {line}", flush=True)
         if bench:
-            out = subprocess.run([sys.executable, "bench.py", "--no-cpu-baseline", "--no-extras", "--no-e2e", "--steps", "40", "--warmup", "8",
+            out = subprocess.run([sys.executable, "bench.py", "--full", "--no-cpu-baseline", "--no-extras", "--no-e2e", "--steps", "40", "--warmup", "8",
                                   "--config", str(cfg)], env=env, capture_output=True, text=True, cwd=ROOT)
             try:
                 j = json.loads(out.stdout.strip().splitlines()[-1])
