@@ -182,7 +182,7 @@ constexpr int kBandProbationReads = 2048;
 // default half-widths of the candidate window, see g_win_level.  A search that converges at once scores start +- 4, so +-4 is
 // the floor of the TABLE; tools/window_need.py (BASELINE config 4): motifs of 11+ bases never need more, 7-10 bases in 0.7 % of
 // the loci, 5-6 bases in 6 %, 3-4 in 27 %.  Levels 4 and 5 exist for the long-motif buckets but are switched off (kWinMinLevel):
-// measured in round 4 on config 4's shard (tools/cfg_probe.py, STRKIT_AMD_WINDOW_B), a narrower TABLE puts the band into a
+// measured in round 4 on config 4's shard (tools/cfg_probe.py, windows pinned per bucket), a narrower TABLE puts the band into a
 // narrower class, and what that class lacks is the slack the certificate needs — +-6 everywhere 6.40 ms per call, +-5 for motifs
 // of 7+ bases 6.34 ms (15 000 certificate failures per call instead of 500), +-4: 8.08 ms (62 000 failures).  The cells a narrow
 // window saves are taken by laying the BAND around the table's inner candidates instead (strk_search.h: BandTune), which keeps
@@ -281,13 +281,7 @@ KArgs make_args(strk_ctx* c, const strk_batch* b, int end_flags, int window, int
     a.long_slot = (long long)c->long_slot_ints;
     a.long_waves = kLongWaves;
     a.list_stride = list_stride;
-    static const int dbg = getenv("STRKIT_AMD_DBG") ? atoi(getenv("STRKIT_AMD_DBG")) : 0;
-    a.dbg = dbg;
-    // tuning aids: STRKIT_AMD_SPAN_W / STRKIT_AMD_SLACK_M8 override where the forward band lies (strk_search.h: BandTune)
-    static const int span_w = getenv("STRKIT_AMD_SPAN_W") ? atoi(getenv("STRKIT_AMD_SPAN_W")) : kBandSpanW;
-    static const int slack_m8 = getenv("STRKIT_AMD_SLACK_M8") ? atoi(getenv("STRKIT_AMD_SLACK_M8")) : kBandSlackM8;
-    a.band_tune.span_w = std::max(0, span_w);
-    a.band_tune.slack_m8 = std::max(0, slack_m8);
+    a.band_tune = {kBandSpanW, kBandSlackM8};
     a.end_flags = end_flags;
     a.window = window;
     for (int k = 0; k < kWinBuckets; ++k) a.window_b[k] = c->p_window_b[k] > 0 ? c->p_window_b[k] : window;
@@ -319,7 +313,6 @@ void enqueue_scoring(strk_ctx* c, const KArgs& a, int mode, const int32_t* d_ite
     const bool hist0 = mode == 0 && c->hist_valid && c->hist_band_mode == a.band_mode;
     const bool sort_wide = a.band_mode && mode == 0 && !force_generic && (!hist0 || (c->hist_wide_chunks > 0 && c->hist_wide_chunks <= 8192));
     hipLaunchKernelGGL(k_plan, dim3((n_items + 255) / 256), dim3(256), 0, st, a, mode, d_items, n_items, force_generic);
-    static const int tune = getenv("STRKIT_AMD_DP_BLOCKS") ? atoi(getenv("STRKIT_AMD_DP_BLOCKS")) : 0;   // tuning aid
     // A call that shares the device with other calls in flight takes fifteen sixteenths of the CU slots per kernel: the free
     // slots are what lets the LDS-holding tail kernels of one call (k_dp_band_wide, k_dp_all, k_dp_long) start while another
     // call's band pass is resident; k_hash / k_plan / k_replay need no LDS and fit NEXT to two band waves per SIMD (2 x 184 of
@@ -330,27 +323,9 @@ void enqueue_scoring(strk_ctx* c, const KArgs& a, int mode, const int32_t* d_ite
     // ms — two calls' big kernels take turns on fifteen sixteenths of the chip each (measured with two calls in flight: 7.1 ms
     // per call against 6.55 ms with whole grids; the other way round for configs 3 and 5: 8.9 against 7.7 ms, 3.5 against 2.65 ms):
     // such a context takes the whole grid (hist_tail_heavy, from the previous call's cell counts).
-    static const int force_heavy = getenv("STRKIT_AMD_FORCE_HEAVY") ? atoi(getenv("STRKIT_AMD_FORCE_HEAVY")) : -1;   // tuning aid: 1 / 0 pins the rule
-    const bool heavy = force_heavy >= 0 ? force_heavy != 0 : (c->hist_valid && c->hist_tail_heavy);
-    const int sixteenths = (g_calls_in_flight.load(std::memory_order_relaxed) > 1 && !heavy) ? 15 : 16;
-    // tuning aid: STRKIT_AMD_GRID16="band,wide,exact" pins the sixteenths of the three persistent grids when calls overlap
-    static const std::array<int, 3> pin16 = [] {
-        std::array<int, 3> v{};
-        if (const char* e = getenv("STRKIT_AMD_GRID16")) {
-            for (int k = 0; k < 3 && *e; ++k) {
-                v[k] = atoi(e);
-                while (*e && *e != ',') ++e;
-                if (*e == ',') ++e;
-            }
-        }
-        return v;
-    }();
     const bool overlap = g_calls_in_flight.load(std::memory_order_relaxed) > 1;
-    // tuning aid: block slots a whole grid of an overlapping call leaves free (for the other call's small LDS-holding kernels)
-    static const int spare_env = getenv("STRKIT_AMD_GRID_SPARE") ? atoi(getenv("STRKIT_AMD_GRID_SPARE")) : 0;
-    const int spare = overlap ? std::max(0, spare_env) : 0;
-    const int s16_band = (overlap && pin16[0] > 0) ? pin16[0] : sixteenths, s16_wide = (overlap && pin16[1] > 0) ? pin16[1] : sixteenths,
-              s16_exact = (overlap && pin16[2] > 0) ? pin16[2] : sixteenths;
+    const bool heavy = c->hist_valid && c->hist_tail_heavy;
+    const int sixteenths = (overlap && !heavy) ? 15 : 16;
     // expected chunks of the sparsely used kernels, from the previous call of this context (same band mode), scaled
     // to this batch with 50 % head-room; without history every grid is the full resident one.  A grid that turns
     // out too small only makes that kernel slower: every wave pulls chunks until the queue is empty.
@@ -362,10 +337,6 @@ void enqueue_scoring(strk_ctx* c, const KArgs& a, int mode, const int32_t* d_ite
         return std::max(1, std::min(full, blocks));
     };
     if (time_dp) (void)hipEventRecord(c->ev[kEvHead], st);
-    static const bool grid_dbg = getenv("STRKIT_AMD_GRID_DEBUG") != nullptr;
-    if (grid_dbg && mode == 0)
-        fprintf(stderr, "[strk grid] ctx %p reads %d in flight %d hist %d heavy %d -> sixteenths %d (wide chunks %d, exact chunks %d)\n", (void*)c, a.n_reads,
-                g_calls_in_flight.load(), (int)c->hist_valid, (int)c->hist_tail_heavy, sixteenths, c->hist_wide_chunks, c->hist_exact_chunks);
     const bool band = a.band_mode && mode == 0 && !force_generic;
     int band_blocks = 1;
     if (band && time_dp) {
@@ -381,7 +352,7 @@ void enqueue_scoring(strk_ctx* c, const KArgs& a, int mode, const int32_t* d_ite
     }
     if (band) {
         // banded first pass: certified reads are done, the others are appended to the exact lists below
-        band_blocks = std::max(1, std::min(tune > 0 ? tune : std::max(1, 256 * kBandBlocksPerCU * s16_band / 16 - (s16_band == 16 ? spare : 0)), (a.list_stride + 3) / 4));
+        band_blocks = std::max(1, std::min(256 * kBandBlocksPerCU * sixteenths / 16, (a.list_stride + 3) / 4));
         hipLaunchKernelGGL(k_dp_band, dim3(band_blocks), dim3(256), 0, st, a);
     }
     if (time_dp) (void)hipEventRecord(c->ev[kEvBand], st);
@@ -397,7 +368,7 @@ void enqueue_scoring(strk_ctx* c, const KArgs& a, int mode, const int32_t* d_ite
             hipLaunchKernelGGL(k_sort_wide, dim3(kSortWideBlocks, kNumWideLists), dim3(256), 0, st, a, c->band_recs_w.as<int4>());
             aw.band_recs_w = c->band_recs_w.as<int4>();
         }
-        const int wide_full = std::max(1, std::min(tune > 0 ? tune : std::max(1, 256 * kBandBlocksPerCU * s16_wide / 16 - (s16_wide == 16 ? spare : 0)), (a.list_stride + 3) / 4));
+        const int wide_full = std::max(1, std::min(256 * kBandBlocksPerCU * sixteenths / 16, (a.list_stride + 3) / 4));
         hipLaunchKernelGGL(k_dp_band_wide, dim3(predicted_blocks(c->hist_wide_chunks, wide_full)), dim3(256), 0, st, aw);
     }
     if (time_dp) (void)hipEventRecord(c->ev[kEvWide], st);
@@ -407,7 +378,7 @@ void enqueue_scoring(strk_ctx* c, const KArgs& a, int mode, const int32_t* d_ite
     if (!force_generic) {
         // persistent-style grid: every wave pulls chunks from the device-side queue until it is empty
         constexpr int kBlocksPerCU = std::max(1, std::min(8, (160 * 1024) / (4 * kWaveLdsBytes + kLdsSlack + 1024)));
-        const int full = std::max(1, std::min(tune > 0 ? tune : 256 * kBlocksPerCU * s16_exact / 16, (a.list_stride + 3) / 4));
+        const int full = std::max(1, std::min(256 * kBlocksPerCU * sixteenths / 16, (a.list_stride + 3) / 4));
         const int blocks = a.ref_mode ? full : predicted_blocks(c->hist_exact_chunks, full);
         if (a.ref_mode) hipLaunchKernelGGL(k_dp_ref, dim3(blocks), dim3(256), 0, st, a);
         else hipLaunchKernelGGL(k_dp_all, dim3(blocks), dim3(256), 0, st, a);
@@ -481,22 +452,9 @@ int submit_device(strk_ctx* c, const strk_batch* b, const strk_params* params, i
     c->p_window_auto = params->window <= 0;
     for (int k = 0; k < kWinBuckets; ++k) c->p_window_b[k] = 0;
     if (c->p_window_auto) {
-        // tuning aid: STRKIT_AMD_WINDOW_B="w0,w1,w2,w3,w4" pins the default window of each motif-length bucket (0: adaptive)
-        static const std::array<int, kWinBuckets> pinned = [] {
-            std::array<int, kWinBuckets> v{};
-            if (const char* e = getenv("STRKIT_AMD_WINDOW_B")) {
-                for (int k = 0; k < kWinBuckets && *e; ++k) {
-                    v[k] = atoi(e);
-                    while (*e && *e != ',') ++e;
-                    if (*e == ',') ++e;
-                }
-            }
-            return v;
-        }();
         p.window = 0;
         for (int k = 0; k < kWinBuckets; ++k) {
-            const int w = pinned[k] > 0 ? std::min(pinned[k], kWindowLevels[kWinLevels - 1])
-                                        : kWindowLevels[std::min(kWinLevels - 1, std::max(kWinMinLevel[k], g_win_level[k].load(std::memory_order_relaxed)))];
+            const int w = kWindowLevels[std::min(kWinLevels - 1, std::max(kWinMinLevel[k], g_win_level[k].load(std::memory_order_relaxed)))];
             c->p_window_b[k] = std::max(w, std::min(kWindowLevels[kWinLevels - 1], p.local_search_range + p.step_size));
             p.window = std::max(p.window, c->p_window_b[k]);
         }
@@ -612,13 +570,6 @@ int finish_device(strk_ctx* c, strk_stats* stats) {
         stats->n_band_fallback = c->h_counters[kCntBandFallback];
         stats->dp_cells = (int64_t) * reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->h_counters) + kCellsOff);
     }
-#ifdef STRK_PHASE_TIMING
-    fprintf(stderr, "[phase ticks/64] header %d stage %d (of which pads %d, window bytes %d) tables %d bwd %d fwd %d epilogue %d\n", c->h_counters[48],
-            c->h_counters[49] + c->h_counters[54] + c->h_counters[55], c->h_counters[55], c->h_counters[54], c->h_counters[50], c->h_counters[51],
-            c->h_counters[52], c->h_counters[53]);
-    fprintf(stderr, "[phase] longest chunk %d ticks/64 (%.3f ms at 2.4 GHz), most rows in a chunk %d, chunks %d\n", c->h_counters[45],
-            c->h_counters[45] * 64.0 / 2.4e6, c->h_counters[46], c->h_counters[47]);
-#endif
     int n_band_reads = 0;
     for (int k = 0; k < kNumBandClasses; ++k) n_band_reads += c->h_counters[kCntClass0 + kBandClass0 + k];
     // (a call whose band certificates mostly failed reports those reads as misses too: not a window problem)
@@ -675,11 +626,7 @@ int finish_device(strk_ctx* c, strk_stats* stats) {
         // twice as long every time a retry (again on probation) fails.
         int nb = 0;
         for (int k = 0; k < kNumBandClasses; ++k) nb += c->h_counters[kCntClass0 + kBandClass0 + k];
-        static const bool aid = getenv("STRKIT_AMD_DBG") && atoi(getenv("STRKIT_AMD_DBG")) != 0;
-        if (aid) {   // profiling runs with parts of the kernels switched off (wrong scores by design): keep the band on
-            c->band_cooldown = 0;
-            c->band_probation = false;
-        } else if (c->band_cooldown > 0) {
+        if (c->band_cooldown > 0) {
             --c->band_cooldown;
         } else if (nb >= 64) {
             if (2 * c->h_counters[kCntBandFallback] > nb) {
@@ -767,9 +714,8 @@ constexpr size_t kScOffSeqOff = 0, kScOffLens = 16, kScOffReadOff = 32, kScOffMo
 int scalar_fast(strk_ctx* c, int32_t start, const uint8_t* tr, int32_t ntr, const uint8_t* fl, int32_t nfl, const uint8_t* fr, int32_t nfr,
                 const uint8_t* motif, int32_t m, int32_t max_iters, int32_t lsr, int32_t step, int32_t window, int32_t* cn, int32_t* score,
                 int32_t* n_explored) {
-    static const bool off = getenv("STRKIT_AMD_NO_SCALAR_FAST") != nullptr;
     const size_t ndb = (size_t)nfl + ntr + nfr;
-    if (off || c->pending || nfl < 1 || nfr < 1 || ndb + 1 > kScalarSeqMax || (size_t)m > kScalarMotifMax || lsr < 0 || step < 1) return 1;
+    if (c->pending || nfl < 1 || nfr < 1 || ndb + 1 > kScalarSeqMax || (size_t)m > kScalarMotifMax || lsr < 0 || step < 1) return 1;
     HIP_TRY(hipSetDevice(c->device));
     int rc;
     if (!c->sc_host) {

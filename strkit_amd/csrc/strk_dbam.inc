@@ -407,7 +407,6 @@ static int64_t dbam_inflate_file_impl(strk_dbam* d, const char* path, int64_t lo
     d->coff0 = lo;
     d->n_data = 0;
     if (n == 0) { ::close(fd); return 0; }
-    const bool timing = getenv("STRKIT_AMD_OPEN_TIMING") != nullptr;
     const auto clk0 = std::chrono::steady_clock::now();
     auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - clk0).count(); };
     constexpr int64_t kPiece = 8 << 20;
@@ -544,15 +543,7 @@ static int64_t dbam_inflate_file_impl(strk_dbam* d, const char* path, int64_t lo
     else if (rc == 0) out = blocks.empty() ? 0 : dbam_run_inflate(d, blocks, n, total, lo, stream);
     if (stream) (void)hipStreamSynchronize(stream);
     if (out < 0) { d->blk_coff.clear(); d->blk_out.clear(); d->blk_len.clear(); }
-    if (timing) {
-        int per_cu = 0;
-        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bgzf_inflate, 64, 0);
-        fprintf(stderr, "strkit_amd: inflater: %d workgroups of 64 lanes per CU\n", per_cu);
-    }
     d->file_ms[0] = t_alloc; d->file_ms[1] = t_read - t_alloc; d->file_ms[2] = since() - t_read;
-    if (timing)
-        fprintf(stderr, "strkit_amd: open %s: buffers %.1f ms, read + upload of %.1f MB %.1f ms (%d readers), inflation (allocation, %zu blocks, kernel) %.1f ms\n",
-                path, t_alloc, (double)n / 1e6, t_read - t_alloc, threads, blocks.size(), since() - t_read);
     return out;
 }
 

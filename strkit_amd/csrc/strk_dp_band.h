@@ -288,19 +288,6 @@ __device__ __forceinline__ void band_pass(const BandCtx& x, const uint8_t* rowsy
 #undef STRK_BAND_FORK
 }
 
-// Profiling aid (tools/phase_timing.sh builds a private copy of the library with -DSTRK_PHASE_TIMING): shader-clock
-// ticks per phase of band_wave, summed over waves into the spare counter slots 48..55.
-#ifdef STRK_PHASE_TIMING
-#define STRK_PHASE(i)                                                                                  \
-    do {                                                                                               \
-        const unsigned long long t_ = __builtin_readcyclecounter();                                    \
-        if (lane == 0) atomicAdd(&a.counters[48 + (i)], (int)((t_ - tphase) >> 6));                    \
-        tphase = t_;                                                                                   \
-    } while (0)
-#else
-#define STRK_PHASE(i) do { } while (0)
-#endif
-
 // Processes 64/G items of band class BC (G = band_class_G(BC) lanes per read), one per group.
 // nextA / nextB / nextC: the caller's three steps towards the NEXT chunk (take it from the queue; fetch its records; touch its
 // window bytes), called where each one's result has had time to arrive and where its own loads are not in the way of this
@@ -313,10 +300,6 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
     constexpr bool LMAX = band_class_lmax(BC);
     constexpr BandLayout lay(band_class_layout(BC));
     const int lane = threadIdx.x & 63;
-#ifdef STRK_PHASE_TIMING
-    unsigned long long tphase = __builtin_readcyclecounter();
-    const unsigned long long tchunk = tphase;
-#endif
     int lig_ = lane & (G - 1);
     // (opaque per chunk: what a pass derives from the lane index and the class's constants — sixteen clamped row-0 values of
     // the backward band, for one — would otherwise be hoisted out of the chunk loop and held, or spilled, across both passes)
@@ -352,7 +335,6 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
     const int rowsT = act ? nfr : 0;
     const bool dbBeg = a.end_flags & 1, dbEnd = a.end_flags & 2, cBeg = a.end_flags & 4, cEnd = a.end_flags & 8;
 
-    STRK_PHASE(0);
     // ---- stage: selector bytes with pads, row symbols ----
     if (first) misc[0] = 0;
     wave_lds_sync();
@@ -369,7 +351,6 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
         const int nd = act ? (ndb + 3) >> 2 : 0;
         for (int d = lig; d < PD; d += G) selw[d] = kFront;
         for (int d = PD + nd + lig; d < min(ND, PD + nd + kBehind); d += G) selw[d] = kBack;
-        STRK_PHASE(7);
         for (int d0 = lig; d0 < nd; d0 += 8 * G) {
             unsigned w[8];
 #pragma unroll
@@ -399,13 +380,11 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
                 if (d < nd) selw[PD + d] = out;
             }
         }
-        STRK_PHASE(6);
         nextA();
         if (other) misc[0] = 1;
         for (int k = lig; k < m; k += G) motifL[k] = act ? s_enc[motif[k]] : (uint8_t)kNullSym;
     }
     wave_lds_sync();
-    STRK_PHASE(1);
     const bool fallback = act && misc[0] != 0;   // a symbol outside the fixed classes (IUPAC code in a read): exact path decides
     for (int e = lig; e < kTableMax; e += G) { comb[e] = kNegInf; if (LMAX) lmaxA[e] = kNegInf; }
     {
@@ -457,14 +436,13 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
     }
     wave_lds_sync();
     nextB();
-    STRK_PHASE(2);
 
     // Long-window classes: a chunk of 12 000 rows is the critical path of a launch that does not fill the chip many times over
     // (BASELINE config 5 at one GPU's share: the longest chunk alone ran 3.0 of the kernel's 3.95 ms, census of the phase-timing
     // build) — and it ran at HALF speed, sharing its SIMD's issue slots with the wave of a short chunk.  Priority goes by rows: the
     // long chunk takes the issue slots it can use (arbitration is by priority, then age), its partner gets the rest; the work is the
     // same, the longest chunk's latency is not.
-    if (FLY && !(a.dbg & 32)) {   // (dbg 32: profiling aid, no priorities)
+    if (FLY) {
         const int rmax = wave_max_over_groups(rowsP);
         if (rmax >= 11264) __builtin_amdgcn_s_setprio(3);
         else if (rmax >= 8192) __builtin_amdgcn_s_setprio(2);
@@ -480,15 +458,13 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
     const int nEff = run ? n : 0;
     // backward pass (reversed right flank x reversed window), then forward pass with the fork rows
     x.tbl = s_tbl + kBandTblBytes;
-    band_pass<G, D, true, false, false>(x, ct, (run && !(a.dbg & 2)) ? rowsT : 0, geo.bdlo, dbEnd, cEnd, 0, 0, 1, geo.cmin, geo.ncol, comb, b0col, lmaxA);
+    band_pass<G, D, true, false, false>(x, ct, run ? rowsT : 0, geo.bdlo, dbEnd, cEnd, 0, 0, 1, geo.cmin, geo.ncol, comb, b0col, lmaxA);
     wave_lds_sync();
     nextC();
-    STRK_PHASE(3);
     x.tbl = s_tbl;
-    band_pass<G, D, false, FLY, LMAX>(x, cp, (run && !(a.dbg & 1)) ? rowsP : 0, geo.dlo, dbBeg, cBeg, (a.dbg & 8) ? 0 : nEff, nfl + lo * m, m, geo.cmin, geo.ncol, comb, b0col, lmaxA);
+    band_pass<G, D, false, FLY, LMAX>(x, cp, run ? rowsP : 0, geo.dlo, dbBeg, cBeg, nEff, nfl + lo * m, m, geo.cmin, geo.ncol, comb, b0col, lmaxA);
     wave_lds_sync();
     if (FLY) __builtin_amdgcn_s_setprio(0);
-    STRK_PHASE(4);
     if (run) {
         for (int k = lig; k < n; k += G) {
             const int R = nfl + (lo + k) * m;
@@ -510,8 +486,8 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
     // maximum 5 |motif| to 7 |motif| per size below it, under the 2 * len(diagonal) bound of its inexact entries.  Reads that
     // turn out uncertain from their real start are re-scored on the device instead: k_replay's append lists, strk_replay.h.)
     if (act && first) {
-        bool certified = (a.dbg & 4) != 0;
-        if (run && !(a.dbg & 4)) {
+        bool certified = false;
+        if (run) {
             SeenMask64 seen;
             auto ub = [&](int k) { return ubA[k]; };
             const CertResult cr = search_replay_cert(q2.w, a.step, a.lsr, a.max_iters, a.tie_last, comb, lo, n, seen, ub, a.narrow);
@@ -541,17 +517,6 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
         }
     }
     wave_lds_sync();
-    STRK_PHASE(5);
-#ifdef STRK_PHASE_TIMING
-    {   // the longest chunk of the launch (ticks / 64), the most rows a chunk had, chunks, and the sum of their longest items' rows
-        const int rows_ = wave_max_over_groups(act ? nfl + (lo + n - 1) * m : 0);
-        if (lane == 0) {
-            atomicMax(&a.counters[45], (int)((tphase - tchunk) >> 6));
-            atomicMax(&a.counters[46], rows_);
-            atomicAdd(&a.counters[47], 1);
-        }
-    }
-#endif
 }
 
 // Two kernels so that the common short classes (8 and 16 lanes per read) are not register-allocated together with the long-

@@ -353,7 +353,7 @@ __device__ __forceinline__ void dp_wave(KArgsKernarg ap, int cls, int base, uint
     constexpr int ref_mode = REF ? 1 : 0;   // k_dp_ref (reference side) / k_dp_all (reads)
     const int rowsT = (act && !ref_mode) ? nfr : 0;
     // staircase fork rows (bwd_pass / fwd_pass): every item of the chunk must have G - 1 motif rows in its smallest candidate
-    const bool stair = !ref_mode && G >= kStairMinG && !(ap->dbg & 32) &&
+    const bool stair = !ref_mode && G >= kStairMinG &&
                        __builtin_amdgcn_ballot_w64(act && (long long)lo * m < G - 1) == 0;
 
     // ---- stage the encoded read window and collect its symbol set ------------------------------

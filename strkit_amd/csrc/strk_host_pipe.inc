@@ -19,6 +19,11 @@
 
 constexpr int kPipeDefaultMB = 24;   // sub-batch size of the host pipeline (STRKIT_AMD_PIPE_MB)
 
+size_t pipe_sub_bytes() {
+    const char* e = getenv("STRKIT_AMD_PIPE_MB");
+    return (size_t)std::max(1, e ? atoi(e) : kPipeDefaultMB) << 20;
+}
+
 struct CopyPool {
     struct Piece { uint8_t* dst; const uint8_t* src; size_t n; };
     std::vector<std::thread> threads;
@@ -111,7 +116,6 @@ struct HostPipe {
     hipStream_t copy_st = nullptr;
     CopyPool* pool = nullptr;
     size_t sub_bytes = 0;
-    double t_stage = 0, t_enqueue = 0, t_wait = 0, t_scatter = 0;   // host seconds per phase (STRKIT_AMD_PIPE_DEBUG prints them)
 };
 
 void pipe_destroy(HostPipe* p) {
@@ -135,8 +139,7 @@ void pipe_destroy(HostPipe* p) {
 int pipe_get(strk_ctx* c, HostPipe** out) {
     if (c->pipe) { *out = c->pipe; return 0; }
     HostPipe* p = new HostPipe();
-    const char* e = getenv("STRKIT_AMD_PIPE_MB");
-    p->sub_bytes = (size_t)std::max(1, e ? atoi(e) : kPipeDefaultMB) << 20;
+    p->sub_bytes = pipe_sub_bytes();
     const char* t = getenv("STRKIT_AMD_COPY_THREADS");
     p->pool = new CopyPool(std::max(0, std::min(15, t ? atoi(t) : std::min(7, host_cpus() - 1))));
     bool ok = hipStreamCreateWithFlags(&p->copy_st, hipStreamNonBlocking) == hipSuccess;
@@ -236,11 +239,8 @@ int pipe_upload(HostPipe* p, HostPipe::Slot& s, const strk_batch* b, int l0, int
             ro[k] = b->read_off[l0 + k] - r0;
             mo[k] = b->motif_off[l0 + k] - m0;
         }
-        const auto t0 = std::chrono::steady_clock::now();
         p->pool->run(std::move(pieces));
-        p->t_stage += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     }
-    const auto t1 = std::chrono::steady_clock::now();
     uint8_t* d = s.d_in.as<uint8_t>();
     if (direct) {
         // the caller's bases are page-locked: DMA from where they lie (93 % of the bytes); the per-read arrays and the rebased
@@ -263,7 +263,6 @@ int pipe_upload(HostPipe* p, HostPipe::Slot& s, const strk_batch* b, int l0, int
     db.motif_off = reinterpret_cast<const int32_t*>(d + o_motif_off);
     db.motifs = d + o_motifs;
     db.seqs = d + o_seqs - s0;   // the kernels add the caller's own seq_off values
-    p->t_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
     s.state = HostPipe::kUploaded;
     s.r0 = r0;
     s.nr = (int)nr;
@@ -272,14 +271,12 @@ int pipe_upload(HostPipe* p, HostPipe::Slot& s, const strk_batch* b, int l0, int
 
 // The batched call of an uploaded sub-batch on a free compute context (behind its upload).
 int pipe_compute(HostPipe* p, HostPipe::Slot& s, int k, const strk_params* params) {
-    const auto t1 = std::chrono::steady_clock::now();
     HostPipe::Ctx& c = p->ctx[k];
     HIP_TRY(hipStreamWaitEvent(c.st, s.ev_h2d, 0));
     int32_t* o = s.d_out.as<int32_t>();
     const size_t st_ = std::max<size_t>((size_t)s.nr, 1);
     const int rc = submit_device(c.sub, &s.db, params, o, o + st_, o + 2 * st_, o + 3 * st_, c.st);
     if (rc) return rc;
-    p->t_enqueue += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
     s.state = HostPipe::kComputing;
     s.ctx = k;
     c.busy = true;
@@ -292,20 +289,16 @@ int pipe_complete(HostPipe* p, HostPipe::Slot& s, int32_t* out_cn, int32_t* out_
     s.state = HostPipe::kFree;
     c.busy = false;
     strk_stats st;
-    const auto t0 = std::chrono::steady_clock::now();
     int rc = finish_device(c.sub, &st);
     if (rc && rc != STRK_E_EMPTY) return rc;
     const size_t nr = (size_t)s.nr, stride = std::max<size_t>(nr, 1);
     if (nr) {
         HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out.p, stride * 16, hipMemcpyDeviceToHost, c.st));
         HIP_TRY(hipStreamSynchronize(c.st));
-        const auto t1 = std::chrono::steady_clock::now();
-        p->t_wait += std::chrono::duration<double>(t1 - t0).count();
         if (out_cn) memcpy(out_cn + s.r0, s.h_out, nr * 4);
         if (out_score) memcpy(out_score + s.r0, s.h_out + stride, nr * 4);
         if (out_n) memcpy(out_n + s.r0, s.h_out + 2 * stride, nr * 4);
         if (out_start) memcpy(out_start + s.r0, s.h_out + 3 * stride, nr * 4);
-        p->t_scatter += std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
     }
     if (agg) {
         agg->dp_cells += st.dp_cells; agg->n_fallback += st.n_fallback; agg->n_miss_reads += st.n_miss_reads;
@@ -337,15 +330,10 @@ int count_loci_pipelined(strk_ctx* c, const strk_batch* b, const strk_params* pa
     for (int l = 0; l < b->n_loci; ++l)
         if (b->read_off[l] < 0 || b->read_off[l + 1] < b->read_off[l] || b->read_off[l + 1] > b->n_reads || b->motif_off[l + 1] <= b->motif_off[l])
             return 0;
-    static const bool off = getenv("STRKIT_AMD_NO_PIPE") != nullptr;
-    if (off) return 0;
     const int64_t total_bytes = b->seq_off[b->n_reads] - b->seq_off[0] + (int64_t)b->n_reads * 24;
+    // (the decision needs the sub-batch size, which lives in the pipe: cheap to read before the pipe exists)
+    if (total_bytes < (int64_t)(pipe_sub_bytes() / 2)) return 0;
     HostPipe* p = nullptr;
-    {   // (the decision needs the sub-batch size, which lives in the pipe: cheap to read before the pipe exists)
-        const char* e = getenv("STRKIT_AMD_PIPE_MB");
-        const int64_t sub = (int64_t)std::max(1, e ? atoi(e) : kPipeDefaultMB) << 20;
-        if (total_bytes < sub / 2) return 0;
-    }
     int rc;
     if ((rc = pipe_get(c, &p))) { *taken = true; return rc; }
     *taken = true;
@@ -353,11 +341,7 @@ int count_loci_pipelined(strk_ctx* c, const strk_batch* b, const strk_params* pa
     if (stats) memset(stats, 0, sizeof *stats);
     const int nl = b->n_loci;
     // page-locked bases (strk_host_register / hipHostMalloc) are read by DMA where they lie
-    static const bool no_direct = getenv("STRKIT_AMD_NO_DIRECT") != nullptr;
-    const bool direct = !no_direct && host_range_pinned(b->seqs + b->seq_off[0], (size_t)(b->seq_off[b->n_reads] - b->seq_off[0]));
-    static const bool dbg_tl = getenv("STRKIT_AMD_PIPE_DEBUG") != nullptr;
-    const auto t_call = std::chrono::steady_clock::now();
-    auto now_ms = [&]() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); };
+    const bool direct = host_range_pinned(b->seqs + b->seq_off[0], (size_t)(b->seq_off[b->n_reads] - b->seq_off[0]));
     int next_l = 0, n_sub = 0, rc_keep = 0, err = 0;
     std::string err_msg, empty_msg;
     auto note = [&](int r) {
@@ -381,10 +365,8 @@ int count_loci_pipelined(strk_ctx* c, const strk_batch* b, const strk_params* pa
         for (int k = 0; k < HostPipe::kSlots; ++k) own_computing += p->slot[k].state == HostPipe::kComputing;
         const bool device_has_room = own_computing == 0 || g_calls_in_flight.load(std::memory_order_relaxed) < 2;
         if (k_up >= 0 && k_ctx >= 0 && !err && device_has_room) {   // 1. an uploaded sub-batch and a free context: compute
-            const double t_s = now_ms();
             rc = pipe_compute(p, p->slot[k_up], k_ctx, params);
             if (rc) { note(rc); p->slot[k_up].state = HostPipe::kFree; }
-            if (dbg_tl) fprintf(stderr, "[strk pipe]   compute slot %d on context %d: %.3f -> %.3f ms\n", k_up, k_ctx, t_s, now_ms());
             continue;
         }
         if (next_l < nl && k_free >= 0 && !err) {                 // 2. a free slot: stage and upload the next sub-batch
@@ -405,9 +387,7 @@ int count_loci_pipelined(strk_ctx* c, const strk_batch* b, const strk_params* pa
                 const int64_t bytes = b->seq_off[b->read_off[l1]] - base_bytes + (int64_t)(b->read_off[l1] - base_reads) * 24;
                 if ((size_t)bytes >= budget) break;
             }
-            const double t_s = now_ms();
             rc = pipe_upload(p, p->slot[k_free], b, next_l, l1, direct);
-            if (dbg_tl) fprintf(stderr, "[strk pipe]   upload loci [%d, %d) into slot %d: %.3f -> %.3f ms\n", next_l, l1, k_free, t_s, now_ms());
             if (rc) { note(rc); continue; }
             p->slot[k_free].seq = n_sub++;
             next_l = l1;
@@ -415,9 +395,7 @@ int count_loci_pipelined(strk_ctx* c, const strk_batch* b, const strk_params* pa
         }
         const int k_done = oldest(HostPipe::kComputing);           // 3. nothing to start: finish the oldest call in flight
         if (k_done >= 0) {
-            const double t_a = now_ms();
             note(pipe_complete(p, p->slot[k_done], out_cn, out_score, out_n, out_start, stats));
-            if (dbg_tl) fprintf(stderr, "[strk pipe]   complete slot %d (%d reads): waited %.3f -> %.3f ms\n", k_done, p->slot[k_done].nr, t_a, now_ms());
             continue;
         }
         if (err) {   // uploads that will not be computed any more
@@ -425,12 +403,6 @@ int count_loci_pipelined(strk_ctx* c, const strk_batch* b, const strk_params* pa
             for (auto& s : p->slot) s.state = HostPipe::kFree;
         }
         break;
-    }
-    static const bool dbg = dbg_tl;
-    if (dbg) {
-        fprintf(stderr, "[strk pipe] %s%d sub-batches, %d copy threads: staging %.3f ms, enqueue %.3f ms, waiting %.3f ms, scatter %.3f ms\n", direct ? "direct DMA from the caller's page-locked arrays, " : "", n_sub,
-                (int)p->pool->threads.size(), p->t_stage * 1e3, p->t_enqueue * 1e3, p->t_wait * 1e3, p->t_scatter * 1e3);
-        p->t_stage = p->t_enqueue = p->t_wait = p->t_scatter = 0;
     }
     if (err) { g_err = err_msg; return err; }
     if (stats) stats->n_sub_batches = n_sub;   // (n_dp_launches keeps its meaning: DP launch rounds, summed over the sub-batches)

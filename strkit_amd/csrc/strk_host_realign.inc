@@ -121,13 +121,6 @@ int realign_impl(strk_ctx* c, int32_t n_pairs, const uint8_t* s1, const int64_t*
         a.queue = c->rl_queue.as<int32_t>();
         a.cells = reinterpret_cast<unsigned long long*>(c->rl_queue.as<char>() + 32);
         HIP_TRY(hipEventRecord(ev0, nullptr));
-        int32_t* hdbg = nullptr;
-        const bool dbg = getenv("STRKIT_AMD_RL_DEBUG") != nullptr;
-        if (dbg) {   // progress markers per wave of block 0, host-visible (diagnosis of a kernel that does not finish)
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&hdbg), 4096, hipHostMallocMapped));
-            memset(hdbg, 0, 4096);
-            a.dbg = hdbg;
-        }
         for (int first = 0, q = 0; first < n; ++q) {
             int cnt = 1;
             while (first + cnt < n && chunk[first + cnt].cl == chunk[first].cl) ++cnt;
@@ -149,18 +142,12 @@ int realign_impl(strk_ctx* c, int32_t n_pairs, const uint8_t* s1, const int64_t*
             const auto t0 = std::chrono::steady_clock::now();
             hipError_t q;
             while ((q = hipStreamQuery(nullptr)) == hipErrorNotReady) {
-                if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit_s) {
-                    if (hdbg)
-                        for (int w = 0; w < 4; ++w)
-                            fprintf(stderr, "[strk_realign] wave %d: iters=%d item=%d cl=%d n2=%d t=%d done=%d\n", w, hdbg[w * 8],
-                                    hdbg[w * 8 + 1], hdbg[w * 8 + 2], hdbg[w * 8 + 3], hdbg[w * 8 + 4], hdbg[w * 8 + 5]);
+                if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit_s)
                     return fail(STRK_E_DEVICE, "realignment kernels did not finish within %.0f s", limit_s);
-                }
                 usleep(50);
             }
             if (q != hipSuccess) return fail(STRK_E_DEVICE, "realignment kernels: %s", hipGetErrorString(q));
         }
-        if (hdbg) (void)hipHostFree(hdbg);
         HIP_TRY(hipGetLastError());
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));

@@ -109,8 +109,6 @@ struct KArgs {
     int32_t band_limit;   // only reads with index < band_limit are eligible (a context on probation tries the band on a sample)
     BandTune band_tune;   // where the forward band lies (strk_search.h: band_geometry)
     uint8_t* exact;       // [n_reads] 1: the read's table holds exact scores, 0: band lower bounds
-    int32_t dbg;          // profiling aid (env STRKIT_AMD_DBG, results are wrong when set): 1 no forward pass, 2 no backward
-                          //    pass, 4 no in-kernel search, 8 no fork rows, 16 band items in arrival order, 32 no wave priorities
     int32_t ref_mode;     // 1: reference-side scoring (repeats.py:23-43): candidate = fl + motif*i only, the
                           //    table holds (score, end_query) pairs, end_flags must be STRK_DB_END_FREE
 };
@@ -129,13 +127,12 @@ enum Counter {
     kCntTotal = kNumLists + 8 + 10,
     kCntLongNeed = 56                     // the largest scratch slot (int32 units) an item of k_dp_long asked for and did not get
 };
-static_assert(kCntTotal <= 48 && kCntLongNeed < 64, "counters: 64 ints; 45..55 belong to the -DSTRK_PHASE_TIMING aid");
+static_assert(kCntTotal <= 48 && kCntLongNeed < 64, "counters: 64 ints in front of the 64-bit counters; kCntLongNeed sits in the spare slots");
 // motif-length buckets of the adaptive candidate window: 1-2, 3-4, 5-6, 7-10, 11 and more bases (round 4: the two long-motif
 // buckets may go below +-6 — tools/window_need.py: no locus of BASELINE config 4 with a motif of 11+ bases needs more than
 // +-4, 0.7 % of those with 7-10 bases do — and a narrow window is what puts a long motif's band into 256 instead of 384 diagonals)
 constexpr int kWinBuckets = 5;
 __host__ __device__ constexpr int win_bucket(int m) { return m <= 2 ? 0 : (m <= 4 ? 1 : (m <= 6 ? 2 : (m <= 10 ? 3 : 4))); }
-static_assert(kCntTotal <= 48, "counters 48..55 belong to the phase-timing aid, the 64-bit counters start at int 64");
 // wide band classes (k_dp_band_wide: 2, 3, 6, 7) -> 0..3, and rows -> bucket of the longest-first order
 constexpr int kNumWideLists = 4;
 __host__ __device__ constexpr int wide_slot(int band_cls) { return (band_cls & 1) | ((band_cls >> 2) << 1); }
@@ -380,7 +377,7 @@ __global__ void __launch_bounds__(256) k_plan(KArgs a, int mode, const int32_t* 
     for (int k0 = 0; k0 < n; k0 += kTableMax) {
         const int nn = min(kTableMax, n - k0);
         const int c = band_list >= 0 ? band_list : classify(nfl, ntr, nfr, m, lo + k0, nn, force_generic, a.ref_mode);
-        const int idx = s_base[c] + ((band_list >= 0 && !(a.dbg & 16)) ? band_rank : atomicAdd(&s_cnt[c], 1));
+        const int idx = s_base[c] + (band_list >= 0 ? band_rank : atomicAdd(&s_cnt[c], 1));
         if (idx < a.list_stride) {
             a.cls_list[(size_t)c * a.list_stride * 2 + 2 * idx] = r;
             a.cls_list[(size_t)c * a.list_stride * 2 + 2 * idx + 1] = band_list >= 0 ? l : k0;   // band items: the locus (k0 is 0)

@@ -68,7 +68,6 @@ struct RealignArgs {
     uint32_t* cigar;
     int32_t* queue;              // work-queue counters, one per launch (zeroed by the host)
     unsigned long long* cells;   // DP cell updates (statistics)
-    volatile int32_t* dbg;       // debug progress markers (host-pinned) or nullptr
 };
 
 template <int CL>
@@ -207,10 +206,7 @@ __device__ __forceinline__ void realign_tile(const RealignArgs& a, const Realign
     };
 
     for (int t0 = 0; t0 < steps; t0 += 64) {
-        if ((t0 & (kRealignStrip - 1)) == 0) {
-            if (a.dbg && lane == 0) a.dbg[(threadIdx.x >> 6) * 8 + 4] = t0;
-            refill(t0);
-        }
+        if ((t0 & (kRealignStrip - 1)) == 0) refill(t0);
         load_chunk(t0, chunk_sym, chunk_h, chunk_e);
         const int tend = min(t0 + 64, steps);
         if (t0 == 0) {
@@ -248,13 +244,10 @@ __global__ void __launch_bounds__(256) k_realign_dp(RealignArgs a, int first, in
         // lanes then run ahead, readfirstlane() returns THEIR (zero) item, and the wave re-runs item 0 for ever.
         __builtin_amdgcn_wave_barrier();
         int item = 0;
-        if (a.dbg && lane == 0) a.dbg[(threadIdx.x >> 6) * 8 + 0] += 1;
         if (lane == 0) item = atomicAdd(a.queue + qslot, 1);
         item = __builtin_amdgcn_readfirstlane(item);
-        if (a.dbg && lane == 0) a.dbg[(threadIdx.x >> 6) * 8 + 1] = item;
         if (item >= count) break;
         const RealignPair pr = a.pairs[first + item];
-        if (a.dbg && lane == 0) { a.dbg[(threadIdx.x >> 6) * 8 + 2] = pr.cl; a.dbg[(threadIdx.x >> 6) * 8 + 3] = pr.n2; }
         int best = INT32_MIN, bestj = 0;
         for (int tile = 0; tile < pr.ntiles; ++tile) {
             if (tile > 0) {   // the previous tile's edge stores must be visible to this tile's loads
@@ -264,7 +257,6 @@ __global__ void __launch_bounds__(256) k_realign_dp(RealignArgs a, int first, in
             }
             realign_tile<CL, EXT0>(a, pr, tile, tab, s_enc, s2strip + (threadIdx.x >> 6) * kRealignStrip, best, bestj);
         }
-        if (a.dbg && lane == 0) a.dbg[(threadIdx.x >> 6) * 8 + 5] += 1;
         __builtin_amdgcn_wave_barrier();
         if (lane == 63) {
             a.score[pr.orig] = best >> 4;

@@ -226,9 +226,6 @@ STRK_HD BandGeo band_geometry(int32_t nfl, int32_t ntr, int32_t nfr, int32_t m, 
     int32_t cls = -1;
     for (int32_t k = 0; k < kNumBandClasses && cls < 0; ++k) {   // narrowest class that holds band and window: 96, 128, 192, 256, ...
         const int32_t c = (k >> 1) + ((k & 1) ? 0 : 4);
-#ifdef STRK_NO_NARROW
-        if (c >= 4) continue;
-#endif
         const int64_t w = band_class_wd(c);
         const int64_t slack = (c >= 4 && smin < kBandNarrowSlack) ? kBandNarrowSlack : smin;
         if (span_hi - span_lo + 1 + 2 * slack > w) continue;

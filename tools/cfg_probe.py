@@ -3,7 +3,6 @@
 fall-backs / window misses and the windows per motif-length bucket — and the first loci against the oracle (checker).
 
     python tools/cfg_probe.py <config> [n_loci] [n_calls] [check_loci]
-    STRKIT_AMD_WINDOW_B="6,6,6,4,4" python tools/cfg_probe.py 4 21250        # pinned windows per motif-length bucket
 """
 import ctypes as C
 import os

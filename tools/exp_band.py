@@ -40,20 +40,14 @@ def main():
         i = args.index("--config"); cfg = int(args[i + 1]); del args[i:i + 2]
     if "--bench" in args:
         bench = True; args.remove("--bench")
-    dbgs = []          # extra runs of the product library with STRKIT_AMD_DBG set (e.g. 32: no staircase fork rows)
-    while "--dbg" in args:
-        i = args.index("--dbg"); dbgs.append(args[i + 1]); del args[i:i + 2]
     libs = {"product": os.path.join(ROOT, "strkit_amd", "lib", "libstrkit_amd.so")}
     for p in sorted(glob.glob(os.path.join(ROOT, "strkit_amd", "lib", "exp", "*.so"))):
         libs[os.path.basename(p)[:-3]] = p
     if args:
         libs = {k: v for k, v in libs.items() if k in args or k == "product"}
     nb = {2: 10, 3: 1, 4: 1, 5: 1}.get(cfg, 10)
-    runs = [(name, path, None) for name, path in libs.items()] + [(f"product dbg={d}", libs["product"], d) for d in dbgs]
-    for name, path, dbg in runs:
-        env = dict(os.environ, STRKIT_AMD_LIB=path, STRKIT_AMD_NO_PIPE="1")   # (one call = one launch of every kernel)
-        if dbg is not None:
-            env["STRKIT_AMD_DBG"] = dbg
+    for name, path in libs.items():
+        env = dict(os.environ, STRKIT_AMD_LIB=path, STRKIT_AMD_PIPE_MB="4096")   # (one piece: one launch of every kernel per call)
         print(f"# {name} ...", flush=True)
         out = subprocess.run([sys.executable, "-c", CODE, str(cfg), str(nb)], env=env, capture_output=True, text=True, cwd=ROOT)
         line = out.stdout.strip() or out.stderr.strip()[-300:]
