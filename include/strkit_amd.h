@@ -271,6 +271,34 @@ int strk_realign(strk_ctx* ctx, int32_t n_pairs, const uint8_t* s1, const int64_
 int strk_realign_i16_flags(int32_t n_pairs, const int64_t* s1_off, const int64_t* s2_off, const int32_t* scores,
                            int32_t* out_flags);
 
+/* ---- allele calling ------------------------------------------------------------------------------------------------
+ * Drop-in for call_alleles (strkit/call/allele.py:176-336) and the distance-based peak assignment of call_locus.py
+ * (1536-1600): per locus, num_bootstrap weighted resamples of the read copy numbers, a k-means++-seeded spherical GMM
+ * fit per resample (sklearn 1.7's EM), medians and percentiles across resamples, then every read's peak.  The random
+ * stream is the library's own, seeded per locus by seed[l]; it does not reproduce numpy's Generator.
+ * Defaults: min_reads 4, min_allele_reads 2, num_bootstrap 100, n_init 3, max_iter 100, filter_factor 3,
+ * force_gm_filter 0, tol 1e-3, reg_covar 1e-6, expansion_ratio 5.0. */
+typedef struct strk_allele_params {
+    int32_t min_reads, min_allele_reads, num_bootstrap, n_init, max_iter, filter_factor, force_gm_filter, pad;
+    double tol, reg_covar, expansion_ratio;
+} strk_allele_params;
+
+#define STRK_ALLELE_CALLED 0
+#define STRK_ALLELE_TOO_FEW 1    /* fewer than min_reads reads: no call */
+#define STRK_ALLELE_EMPTY_PEAK 2 /* a peak got no read (the reference nullifies such a call); every output is still set */
+
+/* Locus l owns reads read_off[l] .. read_off[l+1] (copy number cn[r], weight w[r] > 0, at most 65 535 reads) and has
+ * n_alleles[l] in {1, 2}.  All buffers are host buffers.  Per locus: out_status, out_modal_n; per allele a (2 slots per
+ * locus, slot 1 unused when n_alleles is 1): out_call[2l+a], out_ci95[4l+2a .. +1] and out_ci99 (lo, hi), out_means,
+ * out_weights, out_stdevs, out_peak_n_reads[2l+a]; per read: out_read_peak (-1 when no call).  Unused integer slots
+ * are -1 (peak counts 0), unused doubles NaN.  num_bootstrap must be 2..1024, n_init 1..15 and reg_covar > 0; every
+ * input is checked before the first launch.  stats (optional) receives kernel_ms. */
+int strk_call_alleles(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off /*[n_loci+1]*/, const int32_t* cn, const double* w,
+                      const int32_t* n_alleles, const uint64_t* seed, const strk_allele_params* p,
+                      int32_t* out_status, int32_t* out_modal_n, int32_t* out_call /*[2n]*/, int32_t* out_ci95 /*[4n]*/,
+                      int32_t* out_ci99 /*[4n]*/, double* out_means, double* out_weights, double* out_stdevs /*[2n]*/,
+                      int32_t* out_peak_n_reads /*[2n]*/, int32_t* out_read_peak /*[n_reads], -1 = none*/, strk_stats* stats);
+
 /* ---- host-side front end (CPU only; no context, thread-safe) ---------------------------------------------------
  * What the reference's Rust extension does before the counter runs: walk the alignment records
  * (STRkitBAMReader / STRkitAlignedSegment, call sites strkit/call/call_sample.py:81-131) and cut each read into

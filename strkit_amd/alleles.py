@@ -1,0 +1,182 @@
+"""Allele calling on the GPU: bootstrapped GMM genotypes per locus (strk_call_alleles, kernel k_alleles).
+
+Drop-in for STRkit's call_alleles (strkit/call/allele.py:176-336) plus the distance-based peak assignment of
+call_locus.py:1536-1600.  The algorithm is the reference's with one specified random stream instead of numpy's
+Generator and sklearn's seeds, so results are deterministic per locus seed.  There is no CPU path.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib
+
+CALLED, TOO_FEW, EMPTY_PEAK = 0, 1, 2
+ASSIGN_SINGLE, ASSIGN_DIST = "single", "dist"
+
+
+@dataclass(frozen=True)
+class AlleleParams:
+    """strkit/call/params.py:39-56,166-172 and sklearn's GaussianMixture defaults."""
+    min_reads: int = 4
+    min_allele_reads: int = 2
+    num_bootstrap: int = 100
+    n_init: int = 3
+    max_iter: int = 100
+    filter_factor: int = 3
+    force_gm_filter: bool = False
+    tol: float = 1e-3
+    reg_covar: float = 1e-6
+    expansion_ratio: float = 5.0
+
+    def _c(self) -> _lib.StrkAlleleParams:
+        return _lib.StrkAlleleParams(int(self.min_reads), int(self.min_allele_reads), int(self.num_bootstrap),
+                                     int(self.n_init), int(self.max_iter), int(self.filter_factor),
+                                     int(bool(self.force_gm_filter)), 0, float(self.tol), float(self.reg_covar),
+                                     float(self.expansion_ratio))
+
+
+def _ptr(a: np.ndarray) -> C.c_void_p:
+    return C.c_void_p(a.ctypes.data)
+
+
+def call_alleles_batch(read_off, cns, weights, n_alleles, seeds, params: AlleleParams | None = None, ctx=None,
+                       with_stats: bool = False):
+    """One library call for many loci.  Locus l owns cns/weights[read_off[l]:read_off[l+1]].  Returns a dict of numpy
+    arrays: status, modal_n [L]; call, means, weights, stdevs, peak_n_reads [L, 2]; ci95, ci99 [L, 2, 2];
+    read_peak [n_reads] (-1: no call).  Slot 1 of a one-allele locus is -1 / NaN."""
+    params = params or AlleleParams()
+    ctx = ctx or _lib.default_context()
+    read_off = np.ascontiguousarray(read_off, dtype=np.int32)
+    cns = np.ascontiguousarray(cns, dtype=np.int32)
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    n_loci = read_off.shape[0] - 1
+    n_alleles = np.ascontiguousarray(np.broadcast_to(np.asarray(n_alleles, dtype=np.int32), (n_loci,)))
+    seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (n_loci,)))
+    if n_loci < 0 or cns.shape != weights.shape or (n_loci >= 0 and int(read_off[-1]) != cns.shape[0]):
+        raise ValueError("read_off must span cns, and cns and weights must have one entry per read")
+    out = dict(status=np.empty(n_loci, np.int32), modal_n=np.empty(n_loci, np.int32),
+               call=np.empty((n_loci, 2), np.int32), ci95=np.empty((n_loci, 2, 2), np.int32),
+               ci99=np.empty((n_loci, 2, 2), np.int32), means=np.empty((n_loci, 2)),
+               weights=np.empty((n_loci, 2)), stdevs=np.empty((n_loci, 2)),
+               peak_n_reads=np.empty((n_loci, 2), np.int32), read_peak=np.empty(cns.shape[0], np.int32))
+    cp = params._c()
+    st = _lib.StrkStats()
+    _lib.check(_lib.load().strk_call_alleles(
+        ctx.handle, n_loci, _ptr(read_off), _ptr(cns), _ptr(weights), _ptr(n_alleles), _ptr(seeds), C.byref(cp),
+        *[_ptr(out[k]) for k in ("status", "modal_n", "call", "ci95", "ci99", "means", "weights", "stdevs",
+                                  "peak_n_reads", "read_peak")], C.byref(st)))
+    if with_stats:
+        return out, st.as_dict()
+    return out
+
+
+class CallData:
+    """What call_locus.py and output/vcf.py read from strkit_rust_ext.CallData."""
+
+    def __init__(self, call, call_95_cis, call_99_cis, means, weights, stdevs, modal_n, n_reads=None,
+                 status: int = CALLED):
+        self.call = np.asarray(call, dtype=np.int32)
+        self.call_95_cis = np.asarray(call_95_cis, dtype=np.int32)
+        self.call_99_cis = np.asarray(call_99_cis, dtype=np.int32)
+        self.means = np.asarray(means, dtype=np.float64)
+        self.weights = np.asarray(weights, dtype=np.float64)
+        self.stdevs = np.asarray(stdevs, dtype=np.float64)
+        self.modal_n = int(modal_n)
+        self.n_reads = None if n_reads is None else np.asarray(n_reads, dtype=np.uint16)
+        self.status = int(status)
+        self._assign_method = ASSIGN_DIST if self.call.shape[0] > 1 else ASSIGN_SINGLE
+
+    @property
+    def peak_means(self):
+        return self.means
+
+    @property
+    def peak_weights(self):
+        return self.weights
+
+    @property
+    def peak_stdevs(self):
+        return self.stdevs
+
+    @property
+    def peak_modal_n(self) -> int:
+        return self.modal_n
+
+    def set_assign_method(self, method) -> None:
+        self._assign_method = str(getattr(method, "value", method))
+
+    def get_assign_method_str(self) -> str:
+        return self._assign_method
+
+    def set_n_reads(self, n_reads) -> None:
+        self.n_reads = np.asarray(n_reads, dtype=np.uint16)
+
+    def to_dict(self) -> dict:
+        k = self.modal_n
+        return {
+            "assign_method": self._assign_method,
+            "call": self.call.tolist(),
+            "call_95_cis": self.call_95_cis.tolist(),
+            "call_99_cis": self.call_99_cis.tolist(),
+            "peaks": {
+                "means": self.means[:k].tolist(),
+                "weights": self.weights[:k].tolist(),
+                "stdevs": self.stdevs[:k].tolist(),
+                "modal_n": k,
+                "n_reads": None if self.n_reads is None else self.n_reads[:k].tolist(),
+            },
+        }
+
+
+def call_data_from_batch(out: dict, l: int, n_alleles: int) -> CallData | None:
+    """Locus l of a call_alleles_batch result as CallData (None when it had too few reads)."""
+    if int(out["status"][l]) == TOO_FEW:
+        return None
+    a = int(n_alleles)
+    return CallData(out["call"][l, :a], out["ci95"][l, :a], out["ci99"][l, :a], out["means"][l, :a],
+                    out["weights"][l, :a], out["stdevs"][l, :a], int(out["modal_n"][l]),
+                    n_reads=out["peak_n_reads"][l, :int(out["modal_n"][l])], status=int(out["status"][l]))
+
+
+def _param(params, name, default):
+    if params is None:
+        return default
+    if hasattr(params, name):
+        return getattr(params, name)
+    gp = getattr(params, "gmm_params", None)
+    return getattr(gp, name, default) if gp is not None else default
+
+
+def call_alleles(repeats_fwd, repeats_rev, read_weights_fwd, read_weights_rev, params, min_reads: int, n_alleles: int,
+                 separate_strands: bool, read_bias_corr_min: int, seed: int | None, logger_=None, debug_str: str = "",
+                 ctx=None) -> CallData | None:
+    """The reference's signature (strkit/call/allele.py:176-189).  `params` is an AlleleParams or the reference's
+    CallParams (num_bootstrap, min_allele_reads, force_gm_filter, gmm_params.{n_init, filter_factor, expansion_ratio});
+    `seed` is the locus seed.  The returned CallData also carries the peak assignment of the reads (in the order
+    forward then reverse) as `read_peaks`."""
+    repeats_fwd = np.asarray(repeats_fwd, dtype=np.int32).ravel()
+    repeats_rev = np.asarray(repeats_rev, dtype=np.int32).ravel()
+    if separate_strands and repeats_rev.size:
+        raise NotImplementedError("separate_strands=True is not supported by the GPU allele caller")
+    d = AlleleParams()
+    p = AlleleParams(min_reads=int(min_reads), min_allele_reads=int(_param(params, "min_allele_reads", d.min_allele_reads)),
+                     num_bootstrap=int(_param(params, "num_bootstrap", d.num_bootstrap)),
+                     n_init=int(_param(params, "n_init", d.n_init)), max_iter=int(_param(params, "max_iter", d.max_iter)),
+                     filter_factor=int(_param(params, "filter_factor", d.filter_factor)),
+                     force_gm_filter=bool(_param(params, "force_gm_filter", d.force_gm_filter)),
+                     tol=float(_param(params, "tol", d.tol)), reg_covar=float(_param(params, "reg_covar", d.reg_covar)),
+                     expansion_ratio=float(_param(params, "expansion_ratio", d.expansion_ratio)))
+    cns = np.concatenate((repeats_fwd, repeats_rev))
+    w = np.concatenate((np.asarray(read_weights_fwd, dtype=np.float64).ravel(),
+                        np.asarray(read_weights_rev, dtype=np.float64).ravel()))
+    if seed is None:
+        seed = int(np.random.default_rng().integers(0, 1 << 63))
+    out = call_alleles_batch(np.array([0, cns.shape[0]], np.int32), cns, w, [int(n_alleles)],
+                             [int(seed) & ((1 << 64) - 1)], p, ctx)
+    cd = call_data_from_batch(out, 0, n_alleles)
+    if cd is not None:
+        cd.read_peaks = out["read_peak"].copy()
+    return cd

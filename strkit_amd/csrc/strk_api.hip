@@ -17,6 +17,7 @@
 #include <array>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -36,6 +37,7 @@
 #include "strk_realign.h"
 #include "strk_frontend.h"
 #include "strk_inflate.h"
+#include "strk_alleles.h"
 
 extern "C" int strk_repeat_count(strk_ctx* ctx, int32_t start_count, const uint8_t* tr, int32_t tr_len, const uint8_t* fl,
                                  int32_t fl_len, const uint8_t* fr, int32_t fr_len, const uint8_t* motif, int32_t motif_len,
@@ -142,6 +144,9 @@ struct strk_ctx {
     DevBuf out_cn, out_score, out_n, out_start;
     // realignment (strk_realign)
     DevBuf rl_s1, rl_s2, rl_pairs, rl_trace, rl_edge, rl_out, rl_cigar, rl_queue;
+    // allele calling (strk_call_alleles), on a stream of its own (created by the first call)
+    DevBuf al_off, al_cn, al_w, al_meta, al_ws, al_out, al_rp;
+    hipStream_t al_stream = nullptr;
     int32_t* h_counters = nullptr;  // pinned: counters + cells + scratch_used
     // a chain of events along one call: start | after k_hash + k_plan | after k_dp_band | after k_dp_band_wide | after the
     // first k_replay pass | after k_dp_all / k_dp_ref | after k_dp_long | after k_dp_generic | end (after k_replay and the
@@ -843,6 +848,8 @@ int score_table_impl(strk_ctx* ctx, const strk_batch* batch, const int32_t* lo, 
 
 #include "strk_host_realign.inc"
 
+#include "strk_host_alleles.inc"
+
 }  // namespace
 
 extern "C" {
@@ -931,8 +938,10 @@ void strk_destroy(strk_ctx* c) {
                       &c->items, &c->in_seqs, &c->in_seq_off, &c->in_nfl, &c->in_ntr, &c->in_nfr, &c->in_est,
                       &c->in_read_off, &c->in_motifs, &c->in_motif_off, &c->out_cn, &c->out_score, &c->out_n,
                       &c->out_start, &c->rl_s1, &c->rl_s2, &c->rl_pairs, &c->rl_trace, &c->rl_edge, &c->rl_out, &c->rl_cigar,
-                      &c->rl_queue, &c->band_recs_w, &c->sc_dev, &c->long_list};
+                      &c->rl_queue, &c->band_recs_w, &c->sc_dev, &c->long_list, &c->al_off, &c->al_cn, &c->al_w, &c->al_meta,
+                      &c->al_ws, &c->al_out, &c->al_rp};
     for (DevBuf* b : bufs) b->release();
+    if (c->al_stream) (void)hipStreamDestroy(c->al_stream);
     {
         std::lock_guard<std::mutex> lk(g_band_chain_mu);
         if (g_band_chain_ev == c->ev[kEvBand]) g_band_chain_ev = nullptr;
@@ -1081,6 +1090,18 @@ int strk_realign(strk_ctx* ctx, int32_t n_pairs, const uint8_t* s1, const int64_
     if (ctx->pending) return fail(STRK_E_INVALID, "a submitted call is pending on this context");
     return realign_impl(ctx, n_pairs, s1, s1_off, s2, s2_off, open, extend, gap_pref, out_score, out_end_ref, out_n_cigar,
                         cigar, cigar_off, stats);
+}
+
+int strk_call_alleles(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off, const int32_t* cn, const double* w,
+                      const int32_t* n_alleles, const uint64_t* seed, const strk_allele_params* p, int32_t* out_status,
+                      int32_t* out_modal_n, int32_t* out_call, int32_t* out_ci95, int32_t* out_ci99, double* out_means,
+                      double* out_weights, double* out_stdevs, int32_t* out_peak_n_reads, int32_t* out_read_peak,
+                      strk_stats* stats) {
+    if (!ctx) return fail(STRK_E_INVALID, "ctx is NULL");
+    if (ctx->pending) return fail(STRK_E_INVALID, "a submitted call is pending on this context");
+    static_assert(STRK_ALLELE_CALLED == 0 && STRK_ALLELE_TOO_FEW == 1 && STRK_ALLELE_EMPTY_PEAK == 2, "include/strkit_amd.h <-> strk_alleles.h");
+    return call_alleles_impl(ctx, n_loci, read_off, cn, w, n_alleles, seed, p, out_status, out_modal_n, out_call, out_ci95,
+                             out_ci99, out_means, out_weights, out_stdevs, out_peak_n_reads, out_read_peak, stats);
 }
 
 int strk_ref_repeat_count_batch(strk_ctx* ctx, int32_t n_loci, const int32_t* start_count, const uint8_t* seqs,
