@@ -299,6 +299,29 @@ int strk_call_alleles(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off /*[
                       int32_t* out_ci99 /*[4n]*/, double* out_means, double* out_weights, double* out_stdevs /*[2n]*/,
                       int32_t* out_peak_n_reads /*[2n]*/, int32_t* out_read_peak /*[n_reads], -1 = none*/, strk_stats* stats);
 
+/* ---- best representative of a group of sequences ------------------------------------------------------------------
+ * Stands where the reference calls strkit_rust_ext.consensus_seq (call_locus.py:1602-1613) for the methods `single` and
+ * `best_rep`; partial-order alignment is not built.  A group is an ordered list of byte strings.  No string: index -1,
+ * STRK_CONS_NONE.  All strings byte-identical (a group of one included): index 0, STRK_CONS_SINGLE, distance sum 0.
+ * Otherwise STRK_CONS_BEST_REP: the smallest i with minimal D(i) = sum over all j of the group of lev(s_i, s_j), lev the
+ * unit-cost Levenshtein distance on raw bytes (case-sensitive; an empty string is legal).  Unpinned against STRkit, whose
+ * consensus code is not in its tree. */
+#define STRK_CONS_NONE 0
+#define STRK_CONS_SINGLE 1
+#define STRK_CONS_BEST_REP 2
+/* Group g owns sequences group_off[g] .. group_off[g+1] (group_off[0] = 0, ascending, at most 250 per group); sequence i is
+ * the seq_len[i] (0 .. 65 535) bytes at seqs + seq_start[i], which must lie inside n_seq_bytes; slices may overlap.
+ * out_index is the index INSIDE the group.  All buffers are host buffers; every input is checked before the first launch.
+ * stats (optional) receives kernel_ms. */
+int strk_best_representatives(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off /*[n_groups+1]*/, const uint8_t* seqs,
+                              int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len, int32_t* out_index,
+                              int32_t* out_method, int64_t* out_dist_sum, strk_stats* stats);
+/* The same with the bases already in memory of the context's device (what strk_dbam_extract leaves behind); everything
+ * else on the host. */
+int strk_best_representatives_dseqs(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const void* d_seqs,
+                                    int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len, int32_t* out_index,
+                                    int32_t* out_method, int64_t* out_dist_sum, strk_stats* stats);
+
 /* ---- host-side front end (CPU only; no context, thread-safe) ---------------------------------------------------
  * What the reference's Rust extension does before the counter runs: walk the alignment records
  * (STRkitBAMReader / STRkitAlignedSegment, call sites strkit/call/call_sample.py:81-131) and cut each read into

@@ -1,5 +1,6 @@
 """`python -m strkit_amd call <alignments.bam> --ref ref.fa --loci catalog.bed [--json out.json] [--realign]` — the
-subset of `strkit call` (strkit/entry.py:20-342) that the device backend covers: per-read copy numbers per locus."""
+subset of `strkit call` (strkit/entry.py:20-342) that the device backend covers: per-read copy numbers per locus and, with
+`--call-alleles`, a genotype per locus (`--consensus`: with the sequence of every allele, which a VCF with alleles needs)."""
 from __future__ import annotations
 
 import argparse
@@ -14,7 +15,7 @@ def main(argv=None) -> int:
     c.add_argument("--ref", required=True)
     c.add_argument("--loci", required=True)
     c.add_argument("--json", default="-")
-    c.add_argument("--vcf", default=None, help="also write the loci as VCF (read-level fields; alleles come from allele calling)")
+    c.add_argument("--vcf", default=None, help="also write the loci as VCF (read-level fields; with --call-alleles: alleles and genotypes, which switches --consensus on)")
     c.add_argument("--flank-size", type=int, default=70)
     c.add_argument("--min-avg-phred", type=int, default=13)
     c.add_argument("--max-reads", type=int, default=250)
@@ -26,8 +27,12 @@ def main(argv=None) -> int:
     c.add_argument("--span-mb", type=int, default=4096,
                    help="device front end, files of 24 GB and more: compressed megabytes of the file that go through device memory at a time")
     c.add_argument("--respect-ref", action="store_true")
-    # same names as `strkit call` (strkit/entry.py:20-342); --seed is accepted for command-line compatibility (the
-    # per-read path has no random component), --processes sizes the locus blocks as the reference does (loci.py:193)
+    c.add_argument("--call-alleles", action="store_true", help="call a genotype per locus (GPU allele caller)")
+    c.add_argument("--consensus", action="store_true",
+                   help="with --call-alleles: report the sequence of every allele (single / best_rep; no partial-order alignment)")
+    c.add_argument("--n-alleles", type=int, choices=(1, 2), default=2, help="alleles per locus, all contigs")
+    # same names as `strkit call` (strkit/entry.py:20-342); --seed seeds the allele caller (the per-read path has no random
+    # component), --processes sizes the locus blocks as the reference does (loci.py:193)
     c.add_argument("--sample-id", default=None)
     c.add_argument("--processes", type=int, default=1)
     c.add_argument("--seed", type=int, default=None)
@@ -35,6 +40,8 @@ def main(argv=None) -> int:
     c.add_argument("--max-rcn-iters", type=int, default=50)
     c.add_argument("--min-read-align-score", type=float, default=0.1)
     a = ap.parse_args(argv)
+    if a.consensus and not a.call_alleles:
+        ap.error("--consensus needs --call-alleles")
     import os
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:   # python -m torch.distributed.run --nproc-per-node N -m strkit_amd call ...: one rank per GPU
@@ -50,7 +57,9 @@ def main(argv=None) -> int:
     rep = call_sample(a.read_file, a.ref, a.loci, flank_size=a.flank_size, realign=a.realign,
                       min_avg_phred=a.min_avg_phred, max_reads=a.max_reads, respect_ref=a.respect_ref,
                       sample_id=a.sample_id, processes=a.processes, rc_params=rc,
-                      min_read_align_score=a.min_read_align_score, front_end=a.front_end, span_bytes=a.span_mb << 20)
+                      min_read_align_score=a.min_read_align_score, front_end=a.front_end, span_bytes=a.span_mb << 20,
+                      **(dict(call_alleles=True, consensus=a.consensus or bool(a.vcf), seed=a.seed, n_alleles=a.n_alleles)
+                         if a.call_alleles else {}))
     if world > 1:
         import torch.distributed as dist
         rank0 = dist.get_rank() == 0

@@ -64,7 +64,8 @@ EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk
            "strk_score_ref_table", "strk_ref_repeat_count", "strk_ref_repeat_count_batch", "strk_realign", "strk_realign_i16_flags", "strk_bam_scan",
            "strk_extract_reads", "strk_bgzf_inflate", "strk_bgzf_inflate_range", "strk_bam_names", "strk_bam_scan_piece",
            "strk_dbam_open", "strk_dbam_close", "strk_dbam_release_cache", "strk_dbam_inflate", "strk_dbam_inflate_file", "strk_dbam_inflate_file_range", "strk_dbam_file_ms", "strk_dbam_download", "strk_dbam_data", "strk_bgzf_inflate_sw",
-           "strk_dbam_download_seqs", "strk_dbam_kernel_ms", "strk_dbam_voffsets", "strk_dbam_scan", "strk_dbam_extract", "strk_dbam_names", "strk_count_loci_dseqs", "strk_read_coords_both", "strk_call_alleles")
+           "strk_dbam_download_seqs", "strk_dbam_kernel_ms", "strk_dbam_voffsets", "strk_dbam_scan", "strk_dbam_extract", "strk_dbam_names", "strk_count_loci_dseqs", "strk_read_coords_both", "strk_call_alleles",
+           "strk_best_representatives", "strk_best_representatives_dseqs")
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -190,6 +191,9 @@ def load(build: bool = True):
         L.strk_call_alleles.restype = C.c_int
         L.strk_call_alleles.argtypes = ([C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(StrkAlleleParams)]
                                         + [C.c_void_p] * 10 + [C.POINTER(StrkStats)])
+        for f in (L.strk_best_representatives, L.strk_best_representatives_dseqs):
+            f.restype = C.c_int
+            f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(StrkStats)]
         L.strk_device_mem.restype = C.c_int
         L.strk_device_mem.argtypes = [C.c_int, _i64p, _i64p]
         L.strk_realign_i16_flags.restype = C.c_int

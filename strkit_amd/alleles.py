@@ -38,6 +38,33 @@ class AlleleParams:
                                      float(self.expansion_ratio))
 
 
+_M64 = (1 << 64) - 1
+_GAMMA = 0x9E3779B97F4A7C15
+
+
+def mix64(z: int) -> int:
+    """The finaliser of splitmix64 (the library's random stream uses the same one)."""
+    z &= _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def locus_seed(seed: int, t_idx: int) -> int:
+    """Per-locus seed of the front end: mix64(seed + gamma * (locus_index + 1)).  A locus's call then depends on the run
+    seed and its own index only, not on its block, the reader or the order of the blocks."""
+    return mix64((int(seed) + _GAMMA * (int(t_idx) + 1)) & _M64)
+
+
+def locus_seeds(seed: int, t_idx) -> np.ndarray:
+    """locus_seed for an array of locus indices (uint64, wrapping arithmetic)."""
+    with np.errstate(over="ignore"):
+        z = np.uint64(int(seed) & _M64) + np.uint64(_GAMMA) * (np.asarray(t_idx).astype(np.uint64) + np.uint64(1))
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        return z ^ (z >> np.uint64(31))
+
+
 def _ptr(a: np.ndarray) -> C.c_void_p:
     return C.c_void_p(a.ctypes.data)
 

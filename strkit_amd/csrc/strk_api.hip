@@ -38,6 +38,7 @@
 #include "strk_frontend.h"
 #include "strk_inflate.h"
 #include "strk_alleles.h"
+#include "strk_consensus.h"
 
 extern "C" int strk_repeat_count(strk_ctx* ctx, int32_t start_count, const uint8_t* tr, int32_t tr_len, const uint8_t* fl,
                                  int32_t fl_len, const uint8_t* fr, int32_t fr_len, const uint8_t* motif, int32_t motif_len,
@@ -147,6 +148,9 @@ struct strk_ctx {
     // allele calling (strk_call_alleles), on a stream of its own (created by the first call)
     DevBuf al_off, al_cn, al_w, al_meta, al_ws, al_out, al_rp;
     hipStream_t al_stream = nullptr;
+    // best representatives (strk_best_representatives), likewise
+    DevBuf cs_off, cs_start, cs_len, cs_seqs, cs_bound, cs_out;
+    hipStream_t cs_stream = nullptr;
     int32_t* h_counters = nullptr;  // pinned: counters + cells + scratch_used
     // a chain of events along one call: start | after k_hash + k_plan | after k_dp_band | after k_dp_band_wide | after the
     // first k_replay pass | after k_dp_all / k_dp_ref | after k_dp_long | after k_dp_generic | end (after k_replay and the
@@ -849,6 +853,7 @@ int score_table_impl(strk_ctx* ctx, const strk_batch* batch, const int32_t* lo, 
 #include "strk_host_realign.inc"
 
 #include "strk_host_alleles.inc"
+#include "strk_host_consensus.inc"
 
 }  // namespace
 
@@ -939,9 +944,10 @@ void strk_destroy(strk_ctx* c) {
                       &c->in_read_off, &c->in_motifs, &c->in_motif_off, &c->out_cn, &c->out_score, &c->out_n,
                       &c->out_start, &c->rl_s1, &c->rl_s2, &c->rl_pairs, &c->rl_trace, &c->rl_edge, &c->rl_out, &c->rl_cigar,
                       &c->rl_queue, &c->band_recs_w, &c->sc_dev, &c->long_list, &c->al_off, &c->al_cn, &c->al_w, &c->al_meta,
-                      &c->al_ws, &c->al_out, &c->al_rp};
+                      &c->al_ws, &c->al_out, &c->al_rp, &c->cs_off, &c->cs_start, &c->cs_len, &c->cs_seqs, &c->cs_bound, &c->cs_out};
     for (DevBuf* b : bufs) b->release();
     if (c->al_stream) (void)hipStreamDestroy(c->al_stream);
+    if (c->cs_stream) (void)hipStreamDestroy(c->cs_stream);
     {
         std::lock_guard<std::mutex> lk(g_band_chain_mu);
         if (g_band_chain_ev == c->ev[kEvBand]) g_band_chain_ev = nullptr;
@@ -1102,6 +1108,33 @@ int strk_call_alleles(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off, co
     static_assert(STRK_ALLELE_CALLED == 0 && STRK_ALLELE_TOO_FEW == 1 && STRK_ALLELE_EMPTY_PEAK == 2, "include/strkit_amd.h <-> strk_alleles.h");
     return call_alleles_impl(ctx, n_loci, read_off, cn, w, n_alleles, seed, p, out_status, out_modal_n, out_call, out_ci95,
                              out_ci99, out_means, out_weights, out_stdevs, out_peak_n_reads, out_read_peak, stats);
+}
+
+int strk_best_representatives(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const uint8_t* seqs, int64_t n_seq_bytes,
+                              const int64_t* seq_start, const int32_t* seq_len, int32_t* out_index, int32_t* out_method,
+                              int64_t* out_dist_sum, strk_stats* stats) {
+    if (!ctx) return fail(STRK_E_INVALID, "ctx is NULL");
+    if (ctx->pending) return fail(STRK_E_INVALID, "a submitted call is pending on this context");
+    static_assert(STRK_CONS_NONE == kConsNone && STRK_CONS_SINGLE == kConsSingle && STRK_CONS_BEST_REP == kConsBestRep,
+                  "include/strkit_amd.h <-> strk_consensus.h");
+    return best_rep_impl(ctx, n_groups, group_off, seqs, nullptr, n_seq_bytes, seq_start, seq_len, out_index, out_method,
+                         out_dist_sum, stats);
+}
+
+int strk_best_representatives_dseqs(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const void* d_seqs,
+                                    int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len, int32_t* out_index,
+                                    int32_t* out_method, int64_t* out_dist_sum, strk_stats* stats) {
+    if (!ctx) return fail(STRK_E_INVALID, "ctx is NULL");
+    if (ctx->pending) return fail(STRK_E_INVALID, "a submitted call is pending on this context");
+    if (!d_seqs) return fail(STRK_E_INVALID, "d_seqs is NULL");
+    (void)hipSetDevice(ctx->device);
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, d_seqs) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+        (void)hipGetLastError();
+        return fail(STRK_E_INVALID, "d_seqs is not device memory of device %d (the context's)", ctx->device);
+    }
+    return best_rep_impl(ctx, n_groups, group_off, nullptr, static_cast<const uint8_t*>(d_seqs), n_seq_bytes, seq_start, seq_len,
+                         out_index, out_method, out_dist_sum, stats);
 }
 
 int strk_ref_repeat_count_batch(strk_ctx* ctx, int32_t n_loci, const int32_t* start_count, const uint8_t* seqs,

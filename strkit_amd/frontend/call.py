@@ -2,8 +2,10 @@
 numbers.  Follows the worker loop of strkit/call/call_sample.py:81-197 (blocks of loci, segments fetched once per
 block) and the per-locus path of strkit/call/call_locus.py:700-835 (reference window, reference copy number, adjusted
 boundaries), :837-958 (read coordinates, optional realignment), :1082-1161 (triples, start estimates) and
-:1172-1283 (adjusted score, filters, read_dict).  Allele calling, SNV phasing and VCF output stay with the reference
-(SURVEY.md §8f rank 4): the JSON written here carries the `reads` records they start from.
+:1172-1283 (adjusted score, filters, read_dict).  With `call_alleles` the kept reads of a block go on to the allele caller
+(:1490-1600, strkit_amd.alleles) and, with `consensus`, the reads of every called allele to the best-representative function
+(:1602-1613, strkit_amd.consensus); both are off by default (genotype.py).  SNV phasing, haplotags and partial-order
+alignment are not part of this backend.
 """
 from __future__ import annotations
 
@@ -16,6 +18,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .. import _lib
+from ..alleles import AlleleParams
 from ..batch import MIN_READ_ALIGN_SCORE, count_loci, filter_reads
 from ..realign import _gate as realign_gate, realign_pairs, realign_reads
 from ..repeat_count_params import RepeatCountParams, get_reference_rc_params
@@ -26,6 +29,7 @@ from .bam import BamFile, read_bam
 from .extract import (LowMeanBaseQual, MIN_AVG_PHRED, get_read_coords_from_cigar, get_read_coords_from_matched_pairs,
                       get_sequence_data_for_locus)
 from .fasta import Fasta
+from .genotype import block_consensus, call_block_alleles, genotype_row
 from .loci import Locus, load_loci, parse_loci_bed, resolve_contig
 from .native import DeviceBam, IndexedBam, NativeBam, extract_reads, host_header, realign_cigar_to_read_alignment
 from .output import read_weights
@@ -46,6 +50,16 @@ class CallOptions:
     tie_rule: int = _lib.STRK_TIE_FIRST
     end_flags: int = _lib.STRK_SG_ALL
     narrowing: int = _lib.STRK_NARROW_NONE
+    # genotypes (off by default): allele calls per locus, the sequence of every allele, the run seed (an int once a run has
+    # started), alleles per locus (one number, or a dict per contig), the caller's parameters, and the two limits of
+    # strkit/call/params.py:67-68 for the tract groups of long alleles
+    call_alleles: bool = False
+    consensus: bool = False
+    seed: int | None = None
+    n_alleles: int | dict = 2
+    allele_params: AlleleParams | None = None
+    large_consensus_length: int = 1200
+    max_n_large_consensus_reads: int = 20
 
 
 MAX_READS = 250                 # params.max_reads default (strkit/call/params.py:21)
@@ -236,14 +250,29 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, flank_size
                 sample_id: str | None = None, ctx: _lib.Context | None = None, processes: int = 1,
                 rc_params: RepeatCountParams | None = None, min_read_align_score: float = MIN_READ_ALIGN_SCORE,
                 tie_rule: int = _lib.STRK_TIE_FIRST, end_flags: int = _lib.STRK_SG_ALL, front_end: str = "auto",
-                span_bytes: int = 4 << 30, narrowing: int = _lib.STRK_NARROW_NONE) -> dict:
-    """`front_end` (for a `bam` given as a path): "device" = the file is inflated, scanned and cut on the GPU (DeviceBam) —
+                span_bytes: int = 4 << 30, narrowing: int = _lib.STRK_NARROW_NONE, call_alleles: bool = False,
+                consensus: bool = False, seed: int | None = None, n_alleles: int | dict = 2,
+                allele_params: AlleleParams | None = None, large_consensus_length: int = 1200,
+                max_n_large_consensus_reads: int = 20) -> dict:
+    """`call_alleles`: a genotype per locus (call, intervals, peaks, a peak label `p` per read) from the GPU allele caller, with
+    the locus seed alleles.locus_seed(seed, locus index); `seed=None` draws the run seed once and reports it.  `consensus`
+    (needs call_alleles): the sequence of every allele and of its start anchor as peaks.seqs / peaks.start_anchor_seqs.
+    `n_alleles`: 1 or 2, for all contigs or per contig in a dict.  Not available under torch.distributed yet.
+
+    `front_end` (for a `bam` given as a path): "device" = the file is inflated, scanned and cut on the GPU (DeviceBam) —
     whole when the compressed bytes plus their decompressed form (taken as `RESIDENT_FACTOR` times the file) fit into 90 % of
     the device memory that is free right now, else, with a .bai, in spans of at most `span_bytes` compressed bytes that follow
     the catalog; "host" = block-wise through the .bai on the host cores (IndexedBam) or, without an index, the whole stream
     (NativeBam); "auto" = "device" where that is possible, else "host".  A device reader that runs out of memory all the same
     (a file that inflates more than expected) is retried in spans when the file has an index and replaced by the host reader
     when it has none.  Under torch.distributed every rank opens the file on its own GPU and calls its share of the blocks."""
+    if consensus and not call_alleles:
+        raise ValueError("consensus=True requires call_alleles=True: allele sequences are those of called alleles")
+    if call_alleles and _distributed():
+        raise NotImplementedError("call_alleles=True under torch.distributed: the fixed-size records that the ranks gather "
+                                  "(call_blocks_sharded) have no fields for calls and sequences yet; run one process")
+    if call_alleles and seed is None:
+        seed = int(np.random.default_rng().integers(0, 1 << 63))
     t_open = time.perf_counter()
     own_reader = isinstance(bam, str)
     if isinstance(bam, str):
@@ -294,7 +323,8 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, flank_size
         else:
             bam = IndexedBam(bam) if has_index else NativeBam(bam)
     t_open = time.perf_counter() - t_open       # (device reader: replaced below by the time its thread took)
-    opts = CallOptions(flank_size, realign, min_avg_phred, max_reads, respect_ref, rc_params, min_read_align_score, tie_rule, end_flags, narrowing)
+    opts = CallOptions(flank_size, realign, min_avg_phred, max_reads, respect_ref, rc_params, min_read_align_score, tie_rule, end_flags, narrowing,
+                       call_alleles, consensus, seed, n_alleles, allele_params, large_consensus_length, max_n_large_consensus_reads)
     try:
         ref = Fasta(ref) if isinstance(ref, str) else ref
         t0 = time.perf_counter()
@@ -362,7 +392,13 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, flank_size
                            "min_read_align_score": min_read_align_score, "processes": processes,
                            **({"tie_rule": tie_rule} if tie_rule != _lib.STRK_TIE_FIRST else {}),
                            **({"end_flags": end_flags} if end_flags != _lib.STRK_SG_ALL else {}),
-                           **({"narrowing": narrowing} if narrowing != _lib.STRK_NARROW_NONE else {})},
+                           **({"narrowing": narrowing} if narrowing != _lib.STRK_NARROW_NONE else {}),
+                           **({"call_alleles": True, "seed": seed, "n_alleles": n_alleles,
+                               "min_reads": (allele_params or AlleleParams()).min_reads,
+                               "min_allele_reads": (allele_params or AlleleParams()).min_allele_reads,
+                               "num_bootstrap": (allele_params or AlleleParams()).num_bootstrap} if call_alleles else {}),
+                           **({"consensus": True, "large_consensus_length": large_consensus_length,
+                               "max_n_large_consensus_reads": max_n_large_consensus_reads} if consensus else {})},
             "contigs": sorted({r["contig"] for r in results}),
             "catalog": {"num_loci": len(results), "num_loci_unknown_contig": n_catalog - n_loaded},
             "results": results,
@@ -532,6 +568,10 @@ def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = Non
     exception of call_locus (call_sample.py:159-166: logged, the locus is dropped, the run goes on): the block is
     re-run locus by locus so that only the locus that fails is lost; `stage times["errors"]` lists them."""
     opts = opts or CallOptions()
+    if opts.consensus and not opts.call_alleles:
+        raise ValueError("consensus=True requires call_alleles=True")
+    if opts.call_alleles and opts.seed is None:
+        raise ValueError("call_alleles=True needs a run seed (CallOptions.seed); call_sample draws one when none is given")
     ctx = ctx or _lib.default_context()
     native = isinstance(bam, (NativeBam, IndexedBam, DeviceBam))
     run_block = _call_block_native if native else _call_block_python
@@ -655,7 +695,7 @@ def _locus_row(locus: Locus, rd: dict, reads: dict, opts: CallOptions) -> dict:
         row["start_adj"], row["end_adj"] = rd["left_coord_adj"], rd["right_coord_adj"]
     row["ref_start_anchor"] = rd["ref_left_flank_seq"][-VCF_ANCHOR_SIZE:].upper()      # call_locus.py:1350
     row["ref_seq"] = rd["ref_seq"]                                                      # call_locus.py:1351 (case kept)
-    # allele calling is not part of this backend: the record stops where call_locus.py:1300 starts
+    # the record without a call (genotype.genotype_row adds one when allele calling is on and the locus has enough reads)
     row["peaks"], row["read_peaks_called"] = None, False
     row["reads"] = reads
     return row
@@ -700,6 +740,7 @@ def _call_block_python(block, bam: BamFile, ref: Fasta, opts: CallOptions, ctx, 
     t_a = time.perf_counter()
     # triples of every read of the block -> one batched device call
     loci_reads, meta = [], []
+    raw: list[tuple[str, str]] = []      # per extracted read of the block, in batch order
     for locus, rd, entries in prepared:
         triples, names = [], []
         for seg, pairs, realigned in entries:
@@ -717,6 +758,9 @@ def _call_block_python(block, bam: BamFile, ref: Fasta, opts: CallOptions, ctx, 
                 continue
             triples.append((sd.flank_left_seq_wc[-flank_size:], sd.tr_seq_wc, sd.flank_right_seq_wc[:flank_size]))
             names.append((seg.name, seg.strand, realigned, len(sd.tr_seq)))
+            if opts.consensus:   # the raw tract and the raw read bases in front of it (no wildcards), call_locus.py:1296-1299
+                raw.append((sd.tr_seq, seg.query_sequence[max(coords.left_flank_start, coords.left_flank_end - VCF_ANCHOR_SIZE):
+                                                          coords.left_flank_end]))
         loci_reads.append((locus.motif, triples))
         meta.append(names)
     if not prepared:
@@ -726,6 +770,7 @@ def _call_block_python(block, bam: BamFile, ref: Fasta, opts: CallOptions, ctx, 
     t_a = time.perf_counter()
     res, flt = _count(batch, opts, ctx)
     tm["count_s"] += time.perf_counter() - t_a
+    rows_recs = []
     for li, (locus, rd, _) in enumerate(prepared):
         r0, r1 = int(batch.read_off[li]), int(batch.read_off[li + 1])
         kept = [r for r in range(r0, r1) if flt["keep"][r]]
@@ -742,6 +787,29 @@ def _call_block_python(block, bam: BamFile, ref: Fasta, opts: CallOptions, ctx, 
         row = _locus_row(locus, rd, reads if flt["locus_ok"][li] else {}, opts)
         n_depth += len(row["reads"])
         results.append(row)
+        rows_recs.append((row, kept if flt["locus_ok"][li] else []))
+    if opts.call_alleles:
+        # (a read name that occurs twice at a locus keeps one record, as in the reference's read_dict: the call is made
+        # from the records of the row)
+        recs_of = [list(row["reads"].values()) for row, _ in rows_recs]
+        al = call_block_alleles([p[0] for p in prepared], np.array([len(x) for x in recs_of], np.int64),
+                                np.array([r["cn"] for x in recs_of for r in x], np.int32),
+                                np.array([r["w"] for x in recs_of for r in x], np.float64), opts, ctx, tm)
+        cons = None
+        if opts.consensus:
+            by_name = [{meta[li][r - int(batch.read_off[li])][0]: raw[r] for r in kept} for li, (_, kept) in enumerate(rows_recs)]
+            pairs = [by_name[li][nm] for li, (row, _) in enumerate(rows_recs) for nm in row["reads"]]
+            text, t_start, t_len, a_start, a_len = [], [], [], [], []
+            pos = 0
+            for tr_raw, anchor in pairs:
+                text += [anchor, tr_raw]
+                a_start.append(pos); a_len.append(len(anchor))
+                t_start.append(pos + len(anchor)); t_len.append(len(tr_raw))
+                pos += len(anchor) + len(tr_raw)
+            cons = block_consensus(al, t_start, t_len, a_start, a_len, opts, ctx, tm,
+                                   seqs=np.frombuffer("".join(text).encode("ascii"), np.uint8))
+        for li, (row, _) in enumerate(rows_recs):
+            genotype_row(row, al, li, recs_of[li], cons)
     return results, n_depth
 
 
@@ -831,7 +899,59 @@ def _block_device_stage(block, bam, ref: Fasta, opts: CallOptions, ctx, tm, ref_
           "minus": (bam.flag[kept_rec] & 16) != 0, "lens_all": bam.l_seq[rec].astype(np.int64), "cn": res["cn"], "sc": flt["sc"],
           "nfl": batch.nfl, "ntr": batch.ntr, "nfr": batch.nfr, "alt": alt}
     tm["names_s"] = tm.get("names_s", 0.0) + time.perf_counter() - t_a
+    if opts.call_alleles:
+        _block_genotype_stage(st, bam, coords, opts, ctx, tm)
     return st
+
+
+def _kept_weights(st) -> np.ndarray:
+    """Read weights (call_locus.py:1254-1259, output.read_weights) of the kept reads of all loci of a block at once: the
+    lengths of ALL records fetched for a locus, sorted inside the locus; L = mean length of those that could contain
+    flank + tract + flank."""
+    counts, item_locus, read_locus, kept = (st[k] for k in ("counts", "item_locus", "read_locus", "kept"))
+    big = np.int64(1) << 40
+    lens_all = st["lens_all"]
+    order = np.lexsort((lens_all, item_locus))
+    key = item_locus[order] * big + lens_all[order]
+    csum = np.concatenate(([0], np.cumsum(lens_all[order])))
+    loc_end = np.cumsum(counts)                                   # end of each locus' run in `order`
+    tlwf = (st["nfl"][kept].astype(np.int64) + st["ntr"][kept] + st["nfr"][kept])
+    part = np.searchsorted(key, read_locus[kept] * big + tlwf, side="left")
+    e_ = loc_end[read_locus[kept]]
+    L = (csum[e_] - csum[part]) / np.maximum(e_ - part, 1)
+    return (L + tlwf - 2.0) / (L - tlwf + 1.0)
+
+
+def _block_genotype_stage(st, bam, coords, opts: CallOptions, ctx, tm):
+    """Allele calls of the block's live loci over their kept reads and, with `consensus`, the allele sequences: a second
+    extraction of the kept items with the anchor as the flank and no wildcards leaves anchor | tract | ... of every kept read
+    in one buffer (in HBM for a device reader: the bases are not uploaded), where the best-representative kernel reads the
+    slices in place."""
+    live, kept, read_locus = st["live"], st["kept"], st["read_locus"]
+    st["ws"] = _kept_weights(st)
+    n_kept = np.bincount(read_locus[kept], minlength=len(live))
+    al = st["al"] = call_block_alleles([l for l, _ in live], n_kept, st["cn"][kept], st["ws"], opts, ctx, tm)
+    if not opts.consensus or not kept.size:
+        return
+    t_a = time.perf_counter()
+    items = st["ok_items"][kept]
+    alt = st["alt"]
+    alt2 = {k: alt[int(it)] for k, it in enumerate(items.tolist()) if int(it) in alt} if alt else None
+    ex = extract_reads(bam, st["rec"][items], coords[items], VCF_ANCHOR_SIZE, opts.min_avg_phred, -1, alt2)
+    # same records, same boundaries, same substitute alignments: both extractions cut the same read positions
+    assert not ex["status"].any() and np.array_equal(ex["ntr"], st["ntr"][kept]), "the two extractions of a block disagree"
+    tm["extract2_s"] = tm.get("extract2_s", 0.0) + time.perf_counter() - t_a
+    start = ex["seq_off"][:-1]
+    n_bytes = int(ex["seq_off"][-1])
+    if "d_seqs" in ex:
+        def fetch():
+            host = np.empty(max(n_bytes, 1), np.uint8)
+            _lib.check(_lib.load().strk_dbam_download_seqs(bam._h, n_bytes, host.ctypes.data))
+            return host[:n_bytes]
+        st["cons"] = block_consensus(al, start + ex["nfl"], ex["ntr"], start, ex["nfl"], opts, ctx, tm, d_seqs=ex["d_seqs"],
+                                     n_seq_bytes=n_bytes, fetch=fetch)
+    else:
+        st["cons"] = block_consensus(al, start + ex["nfl"], ex["ntr"], start, ex["nfl"], opts, ctx, tm, seqs=ex["seqs"])
 
 
 def _block_report_stage(st, opts: CallOptions, tm):
@@ -847,19 +967,7 @@ def _block_report_stage(st, opts: CallOptions, tm):
     cns = st["cn"][kept].tolist()
     scs = [None if x != x else x for x in st["sc"][kept].tolist()]
     sls = st["ntr"][kept].tolist()
-    # read weights (call_locus.py:1254-1259, output.read_weights) for all loci at once: the lengths of ALL records fetched
-    # for a locus, sorted inside the locus; L = mean length of those that could contain flank + tract + flank
-    big = np.int64(1) << 40
-    lens_all = st["lens_all"]
-    order = np.lexsort((lens_all, item_locus))
-    key = item_locus[order] * big + lens_all[order]
-    csum = np.concatenate(([0], np.cumsum(lens_all[order])))
-    loc_end = np.cumsum(counts)                                   # end of each locus' run in `order`
-    tlwf = (st["nfl"][kept].astype(np.int64) + st["ntr"][kept] + st["nfr"][kept])
-    part = np.searchsorted(key, read_locus[kept] * big + tlwf, side="left")
-    e_ = loc_end[read_locus[kept]]
-    L = (csum[e_] - csum[part]) / np.maximum(e_ - part, 1)
-    ws = ((L + tlwf - 2.0) / (L - tlwf + 1.0)).tolist()
+    ws = (st["ws"] if "ws" in st else _kept_weights(st)).tolist()     # (computed ahead of the allele calls when those are on)
     realn = [bool(alt) and int(it) in alt for it in ok_items[kept]] if alt else None
     first = np.concatenate(([0], np.cumsum(n_kept))).tolist()
     # the read records of the whole block in one comprehension (values as locals: no indexing), then a dict per locus
@@ -868,9 +976,13 @@ def _block_report_stage(st, opts: CallOptions, tm):
         for k, r_ in enumerate(realn):
             if r_:
                 recs[k]["realn"] = True
+    al, cons = st.get("al"), st.get("cons")
     for li, (locus, rd) in enumerate(live):
         a, b = first[li], first[li + 1]
-        results.append(_locus_row(locus, rd, dict(zip(names[a:b], recs[a:b])), opts))
+        row = _locus_row(locus, rd, dict(zip(names[a:b], recs[a:b])), opts)
+        if al is not None:
+            genotype_row(row, al, li, recs[a:b], cons)
+        results.append(row)
     tm["report_s"] = tm.get("report_s", 0.0) + time.perf_counter() - t_a
     return results, int(len(kept))
 

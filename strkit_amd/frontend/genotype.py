@@ -1,0 +1,143 @@
+"""Genotypes of a block of loci: allele calls (strkit_amd.alleles) and allele sequences (strkit_amd.consensus) over the kept
+reads of all live loci, one library call each per block, and the row fields they become (call_locus.py:1490-1640,
+json_report.py:90).  Shared by the native block path and the readable one; opt-in (CallOptions.call_alleles / consensus).
+"""
+from __future__ import annotations
+
+import math
+import time
+
+import numpy as np
+
+from ..alleles import CALLED, TOO_FEW, AlleleParams, call_alleles_batch, call_data_from_batch, locus_seeds
+from ..consensus import METHOD_NAMES, best_representatives_packed
+
+__all__ = ["n_alleles_of", "call_block_alleles", "peak_groups", "block_consensus", "genotype_row"]
+
+
+def n_alleles_of(n_alleles, contig: str) -> int:
+    """`n_alleles`: one number for every contig or a dict per contig (2 where a contig is not named)."""
+    if isinstance(n_alleles, dict):
+        return int(n_alleles.get(contig, n_alleles.get(contig[3:] if contig.startswith("chr") else "chr" + contig, 2)))
+    return int(n_alleles)
+
+
+def call_block_alleles(loci, n_kept: np.ndarray, cns: np.ndarray, ws: np.ndarray, opts, ctx, tm) -> dict:
+    """Allele calls of all loci of a block.  `loci`: the live loci; locus l owns the next n_kept[l] entries of cns / ws
+    (the kept reads, in read order).  The weights are divided by their per-locus sum (call_locus.py:190-192); a locus with
+    a weight that is not a positive finite number (no fetched read is long enough, output.read_weights) is not called.
+    Returns call_alleles_batch's arrays plus `n_alleles` [L] and `read_off` [L + 1]; read_peak covers every kept read."""
+    t_a = time.perf_counter()
+    n_loci = len(loci)
+    n_kept = np.asarray(n_kept, np.int64)
+    owner = np.repeat(np.arange(n_loci), n_kept)
+    w = np.asarray(ws, np.float64)
+    good = np.isfinite(w) & (w > 0)
+    bad_locus = np.bincount(owner[~good], minlength=n_loci) > 0
+    sel = ~bad_locus[owner]
+    sums = np.bincount(owner[sel], weights=w[sel], minlength=n_loci)
+    n_sel = np.where(bad_locus, 0, n_kept)
+    nal = np.array([n_alleles_of(opts.n_alleles, l.contig) for l in loci], np.int32)
+    seeds = locus_seeds(opts.seed, np.array([l.t_idx for l in loci], np.int64))
+    out, st = call_alleles_batch(np.concatenate(([0], np.cumsum(n_sel))).astype(np.int32), np.asarray(cns, np.int32)[sel],
+                                 w[sel] / sums[owner[sel]], nal, seeds, opts.allele_params or AlleleParams(), ctx, with_stats=True)
+    rp = np.full(owner.shape[0], -1, np.int32)
+    rp[sel] = out["read_peak"]
+    out["read_peak"] = rp
+    out["n_alleles"] = nal
+    out["read_off"] = np.concatenate(([0], np.cumsum(n_kept))).astype(np.int64)
+    tm["alleles_s"] = tm.get("alleles_s", 0.0) + time.perf_counter() - t_a
+    tm["alleles_device_s"] = tm.get("alleles_device_s", 0.0) + st["kernel_ms"] / 1e3
+    return out
+
+
+def peak_groups(al: dict, tract_len: np.ndarray, opts):
+    """The read groups whose sequences are wanted: per called locus and peak, in locus and peak order, the kept reads
+    assigned to the peak in read order.  Returns (group_locus [G], group_peak [G], tract_reads, tract_off [G + 1],
+    anchor_reads, anchor_off [G + 1]) with the reads as indices into the block's kept reads.  A peak whose first tract is
+    longer than large_consensus_length keeps its first max_n_large_consensus_reads reads for the tract group
+    (call_locus.py:1606-1609); anchor groups are never cut."""
+    n_loci = al["status"].shape[0]
+    owner = np.repeat(np.arange(n_loci), np.diff(al["read_off"]))
+    called = al["status"] == CALLED
+    modal = np.where(called, al["modal_n"], 0).astype(np.int64)
+    g_first = np.concatenate(([0], np.cumsum(modal)))            # first group of every locus
+    n_groups = int(g_first[-1])
+    group_locus = np.repeat(np.arange(n_loci), modal)
+    group_peak = np.arange(n_groups) - g_first[:-1][group_locus]
+    rp = al["read_peak"]
+    take = np.flatnonzero(called[owner] & (rp >= 0))
+    gid = g_first[:-1][owner[take]] + rp[take]
+    order = np.argsort(gid, kind="stable")
+    reads, gid = take[order], gid[order]
+    sizes = np.bincount(gid, minlength=n_groups)
+    off = np.concatenate(([0], np.cumsum(sizes)))
+    pos = np.arange(reads.shape[0]) - off[:-1][gid]
+    big = np.zeros(n_groups, bool)
+    nz = sizes > 0
+    big[nz] = tract_len[reads[off[:-1][nz]]] > opts.large_consensus_length
+    keep = ~(big[gid] & (pos >= opts.max_n_large_consensus_reads))
+    t_sizes = np.bincount(gid[keep], minlength=n_groups)
+    return group_locus, group_peak, reads[keep], np.concatenate(([0], np.cumsum(t_sizes))), reads, off
+
+
+def block_consensus(al: dict, tract_start, tract_len, anchor_start, anchor_len, opts, ctx, tm, seqs=None, d_seqs=None,
+                    n_seq_bytes=None, fetch=None) -> dict:
+    """Allele sequences of a block: one strk_best_representatives call over the tract groups and the anchor groups of all
+    called peaks.  The four arrays address every kept read's raw tract and raw start anchor inside one buffer (host `seqs`, or
+    device `d_seqs` with `fetch()` returning its host copy for the few strings that are reported).  Returns
+    {locus: ([[sequence, method] per peak], [[anchor, method] per peak])}."""
+    t_a = time.perf_counter()
+    tract_start, tract_len = np.asarray(tract_start, np.int64), np.asarray(tract_len, np.int32)
+    anchor_start, anchor_len = np.asarray(anchor_start, np.int64), np.asarray(anchor_len, np.int32)
+    g_locus, _g_peak, t_reads, t_off, a_reads, a_off = peak_groups(al, tract_len, opts)
+    n_groups = g_locus.shape[0]
+    if n_groups == 0:
+        return {}
+    starts = np.concatenate((tract_start[t_reads], anchor_start[a_reads]))
+    lens = np.concatenate((tract_len[t_reads], anchor_len[a_reads]))
+    group_off = np.concatenate((t_off, t_off[-1] + a_off[1:])).astype(np.int32)
+    out, st = best_representatives_packed(group_off, starts, lens, seqs=seqs, d_seqs=d_seqs, n_seq_bytes=n_seq_bytes, ctx=ctx,
+                                          with_stats=True)
+    tm["consensus_device_s"] = tm.get("consensus_device_s", 0.0) + st["kernel_ms"] / 1e3
+    t_b = time.perf_counter()
+    host = np.asarray(seqs, np.uint8) if seqs is not None else fetch()
+    tm["consensus_fetch_s"] = tm.get("consensus_fetch_s", 0.0) + time.perf_counter() - t_b
+    first = group_off[:-1].astype(np.int64) + out["index"]
+    res: dict[int, tuple[list, list]] = {}
+    text = host.tobytes()
+    for g in range(n_groups):
+        pair = []
+        for k in (g, n_groups + g):
+            if out["method"][k] == 0:
+                pair.append([None, METHOD_NAMES[0]])
+                continue
+            s0 = int(starts[first[k]])
+            pair.append([text[s0:s0 + int(lens[first[k]])].decode("ascii"), METHOD_NAMES[int(out["method"][k])]])
+        t, a = res.setdefault(int(g_locus[g]), ([], []))
+        t.append(pair[0])
+        a.append(pair[1])
+    tm["consensus_s"] = tm.get("consensus_s", 0.0) + time.perf_counter() - t_a
+    return res
+
+
+def genotype_row(row: dict, al: dict, li: int, recs: list[dict], cons: dict | None) -> None:
+    """Adds the call of locus `li` of the block to its row (call_locus.py:1490-1640 + CallData.to_dict): `p` on every read
+    record, assign_method, call, the intervals, peaks, read_peaks_called, mean_model_align_score.  A locus with too few
+    reads keeps the row it has; a call with an empty peak is nullified as the reference does (call_locus.py:1597-1600) and
+    its reads keep their peak labels."""
+    status = int(al["status"][li])
+    if status == TOO_FEW:
+        return
+    a = int(al["read_off"][li])
+    for k, p in enumerate(al["read_peak"][a:a + len(recs)].tolist()):
+        recs[k]["p"] = p
+    row["read_peaks_called"] = True
+    scs = [r["sc"] for r in recs if r["sc"] is not None]
+    row["mean_model_align_score"] = math.fsum(scs) / len(scs) if scs else None
+    if status != CALLED:
+        return
+    cd = call_data_from_batch(al, li, int(al["n_alleles"][li]))
+    row.update(cd.to_dict())
+    if cons is not None and li in cons:
+        row["peaks"]["seqs"], row["peaks"]["start_anchor_seqs"] = cons[li]

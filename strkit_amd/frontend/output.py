@@ -10,18 +10,23 @@ allele calling starts from and the read-level fields of its VCF.
 * `mcrl_field` / `slr_field` — the `MCRL` / `SLR` sample fields (output/vcf.py:322-342): per allele ("peak") a histogram
   `CNxCOUNT|CNxCOUNT...` of the read-level copy numbers / tract lengths of the reads assigned to it.
 * `write_vcf` — a VCF 4.2 text writer with the reference's header lines and the record layout of
-  create_result_vcf_records (output/vcf.py:67-156,173-342) for what this backend knows.  Alleles, genotypes and the
-  per-allele fields come from allele calling, which stays with the reference; a row that carries peak labels (`p`) per
-  read and a `call` gets `MC` / `MCRL` / `SLR` per peak exactly as there.  For rows without a call the reference writes
-  none of the read-level fields; this writer adds, under its own header note, the one-group histograms of all kept reads
-  so that the read-level answers of the hot path are visible in the VCF too.
+  create_result_vcf_records (output/vcf.py:67-156,173-342) for what this backend knows.  A row with a `call` and allele
+  sequences (`peaks.seqs`, call_sample(call_alleles=True, consensus=True)) gets `ALT`, `GT` and the per-allele fields as
+  there (output/vcf.py:202-342); a row with a call and a `peaks` record but no sequences gets the per-allele counts and
+  intervals and a blank `GT`; a row that carries peak labels (`p`) per read and a `call` only gets `MC` / `MCRL` / `SLR`
+  per peak.  For rows without a call the reference writes none of the read-level fields; this writer adds, under its own
+  header note, the one-group histograms of all kept reads so that the read-level answers of the hot path are visible in
+  the VCF too.
 """
 from __future__ import annotations
 
+import os
 from collections import Counter
 from datetime import datetime
 
 import numpy as np
+
+from .genotype import n_alleles_of
 
 __all__ = ["read_weights", "allele_calling_inputs", "format_count_pair", "mcrl_field", "slr_field", "write_vcf", "VCF_ANCHOR_SIZE"]
 
@@ -93,6 +98,8 @@ _FORMATS = (("AD", ".", "Integer", "Read depth for each allele"),
             ("MMAS", "1", "Float", "Mean model (candidate TR sequence) alignment score across reads."),
             ("PM", "1", "String", "Peak-calling method (dist/snv+dist/snv/hp)"),
             ("SLR", ".", "String", "Read-level sequence lengths for each allele"))
+_SEQ_FORMATS = (("ANCL", ".", "Integer", "Anchor length for the ref and each alt, five-prime of TR sequence"),
+                ("CONS", ".", "String", "Consensus methods used for each alt (single/poa/best_rep)"))
 _INFOS = (("VT", "1", "String", "Variant record type (str/snv)"),
           ("MOTIF", "1", "String", "Motif string"),
           ("REFMC", "1", "Integer", "Motif copy number in the reference genome"),
@@ -101,10 +108,48 @@ _INFOS = (("VT", "1", "String", "Variant record type (str/snv)"),
           ("ANCH", "1", "Integer", "Five-prime anchor size"))
 
 
-def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n_alleles: int = 2, date: str | None = None) -> int:
+def _has_seqs(row: dict) -> bool:
+    return bool(row.get("call")) and bool((row.get("peaks") or {}).get("seqs"))
+
+
+def _alleles_of_row(row: dict, anchor: str, ref_seq: str, n_alleles: int):
+    """output/vcf.py:202-287 for a row with a call and allele sequences: (anchor offset, the alleles as (tract, anchor) pairs
+    with the reference first and None for "no alternative", the VCF allele strings, the genotype indices, the method per
+    distinct sequence), or None where the reference skips the record (a missing sequence, an allele it cannot index)."""
+    peaks = row["peaks"]
+    methods = {(seq.upper() if seq else seq): method for seq, method in peaks["seqs"]}
+    peak_seqs = tuple(methods)
+    anchors = [a for a, _ in peaks.get("start_anchor_seqs") or []]
+    if any(s is None for s in peak_seqs) or any(a is None for a in anchors):
+        return None
+    anchors = tuple(a.upper() for a in anchors)
+    # bases shared by the front of every anchor are cut; one base stays as the anchor VCF needs
+    offset = min(len(os.path.commonprefix([anchor, *anchors])), VCF_ANCHOR_SIZE - 1, max(len(anchor) - 1, 0))
+    ref_anchor = anchor[offset:]
+    with_anchors = list(zip(peak_seqs, (a[offset:] for a in anchors)))
+    if 0 < len(with_anchors) < n_alleles:
+        with_anchors = [with_anchors[0]] * n_alleles
+    alts = sorted({c for c in with_anchors if c[1] + c[0] != ref_anchor + ref_seq}, key=lambda c: c[1] + c[0])
+    raw = ((ref_seq, ref_anchor), *(alts or (None,)))
+    # a complete deletion, anchor included, is the symbolic "upstream deletion" allele
+    strings = [ref_anchor + ref_seq] + (["*" if not t and not a else a + t for t, a in alts] if alts else ["."])
+    try:
+        gt = tuple(raw.index(c) for c in with_anchors)
+    except ValueError:
+        return None
+    return offset, raw, strings, gt, methods
+
+
+def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n_alleles: int | dict | None = None,
+              date: str | None = None) -> int:
     """Writes the loci of a report as VCF 4.2 text; returns the number of records.  `ref` (a Fasta) supplies the contig
     lengths of the header.  Loci without reference data have no anchor and are skipped, as the reference does
-    (output/vcf.py:184-186)."""
+    (output/vcf.py:184-186).  `n_alleles` (one number, or a dict per contig): the report's own when not given, else 2."""
+    if n_alleles is None:
+        n_alleles = (report.get("parameters") or {}).get("n_alleles", 2)
+    formats = _FORMATS
+    if any(_has_seqs(r) for r in report["results"]):
+        formats = _FORMATS[:1] + _SEQ_FORMATS + _FORMATS[1:]
     sample = sample_id or report.get("sample_id") or "sample"
     now = datetime.now()  # noqa: DTZ005
     lines = ["##fileformat=VCFv4.2", "##fileDate=" + (date or f"{now.year}{now.month:02d}{now.day:02d}"), "##source=strkit_amd",
@@ -112,7 +157,7 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
              "##strkitAmdNote=rows without an allele call carry MCRL and SLR as ONE group over all kept reads (STRkit writes them per called allele only)"]
     if ref is not None:
         lines += [f"##contig=<ID={c},length={ref.get_reference_length(c)}>" for c in ref.references]
-    lines += [f'##FORMAT=<ID={i},Number={n},Type={t},Description="{d}">' for i, n, t, d in _FORMATS]
+    lines += [f'##FORMAT=<ID={i},Number={n},Type={t},Description="{d}">' for i, n, t, d in formats]
     lines += [f'##INFO=<ID={i},Number={n},Type={t},Description="{d}">' for i, n, t, d in _INFOS]
     lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + sample)
     n_rec = 0
@@ -126,16 +171,40 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
         reads = row.get("reads") or {}
         call = row.get("call")
         n_peaks = len(call) if call else None
+        n_al = n_alleles_of(n_alleles, row["contig"])
+        peaks = (row.get("peaks") or None) if call else None      # per-allele fields are keyed on what the row carries
+        alleles = None
+        ref_allele, alt, gt = anchor + ref_seq, ".", "/".join(["."] * n_al)
+        if peaks and peaks.get("seqs"):
+            alleles = _alleles_of_row(row, anchor, ref_seq, n_al)
+            if alleles is None:
+                continue
+            offset, raw, strings, gt_idx, methods = alleles
+            anchor = anchor[offset:]
+            start0 += offset
+            ref_allele, alt, gt = strings[0], ",".join(strings[1:]), "/".join(map(str, gt_idx))
+        if peaks:
+            n_peaks = int(peaks["modal_n"])
         info = f"VT=str;MOTIF={row['motif']};REFMC={row['ref_cn']};BED_START={row['start']};BED_END={row['end']};ANCH={len(anchor)}"
-        keys, vals = ["GT", "DP"], ["/".join(["."] * n_alleles), str(len(reads))]
+        keys, vals = ["GT", "DP"], [gt, str(len(reads))]
         if row.get("assign_method"):
             keys.append("PM"); vals.append(str(row["assign_method"]))
+        if peaks:
+            mmas = row.get("mean_model_align_score")
+            keys += ["MMAS", "DPS", "AD"]
+            vals += ["." if mmas is None else f"{mmas:.6g}", str(sum(peaks["n_reads"])), ",".join(map(str, peaks["n_reads"]))]
         if call:
             keys.append("MC"); vals.append(",".join(str(int(c)) for c in call))
+        if peaks:
+            keys.append("MCCI"); vals.append(",".join(f"{lo}-{hi}" for lo, hi in row["call_95_cis"]))
+        if alleles is not None:
+            cons = [methods[ar[0]] for ar in raw[1:] if ar is not None]
+            keys += ["ANCL", "CONS"]
+            vals += [",".join(str(len(ar[1])) for ar in raw if ar is not None), ",".join(cons) if cons else "."]
         if reads:
             keys += ["MCRL", "SLR"]
             vals += [",".join(mcrl_field(reads, n_peaks)), ",".join(slr_field(reads, n_peaks))]
-        lines.append("\t".join((row["contig"], str(start0 + 1), row["locus_id"], anchor + ref_seq, ".", ".", ".", info, ":".join(keys), ":".join(vals))))
+        lines.append("\t".join((row["contig"], str(start0 + 1), row["locus_id"], ref_allele, alt, ".", ".", info, ":".join(keys), ":".join(vals))))
         n_rec += 1
     with open(path, "w") as fh:
         fh.write("\n".join(lines) + "\n")
