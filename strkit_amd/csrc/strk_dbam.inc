@@ -191,8 +191,9 @@ __global__ void __launch_bounds__(256) k_dbam_names(const uint8_t* data, int n, 
 namespace {
 struct ParkedBuf { int device; DevBuf buf; };
 std::mutex g_park_mu;
-std::vector<ParkedBuf> g_parked;
-std::vector<std::pair<int, uint8_t*>> g_parked_rings;   // the pinned rings of closed readers (one per device is kept)
+// (never destroyed: what is parked when the process ends is left to the driver — no HIP call after main() has returned)
+std::vector<ParkedBuf>& g_parked = *new std::vector<ParkedBuf>();
+std::vector<std::pair<int, PinnedBuf>>& g_parked_rings = *new std::vector<std::pair<int, PinnedBuf>>();   // the pinned rings of closed readers (one per device is kept)
 
 void dbam_park(int device, DevBuf& b) {
     if (!b.p || b.cap < ((size_t)64 << 20)) { b.release(); return; }
@@ -206,8 +207,7 @@ void dbam_park(int device, DevBuf& b) {
         g_parked[smallest].buf.release();
         g_parked.erase(g_parked.begin() + (long)smallest);
     }
-    g_parked.push_back(ParkedBuf{device, b});
-    b.p = nullptr; b.cap = 0;
+    g_parked.push_back(ParkedBuf{device, std::move(b)});
 }
 
 // b can hold `bytes` afterwards: as it is, through a parked buffer (the smallest that fits), or through hipMalloc
@@ -219,8 +219,7 @@ int dbam_big_ensure(int device, DevBuf& b, size_t bytes) {
         for (size_t i = 0; i < g_parked.size(); ++i)
             if (g_parked[i].device == device && g_parked[i].buf.cap >= bytes && (best == (size_t)-1 || g_parked[i].buf.cap < g_parked[best].buf.cap)) best = i;
         if (best != (size_t)-1) {
-            b.release();
-            b = g_parked[best].buf;
+            b = std::move(g_parked[best].buf);
             g_parked.erase(g_parked.begin() + (long)best);
             return 0;
         }
@@ -235,13 +234,13 @@ struct strk_dbam {
     DevBuf w_a, w_b, w_c, w_d, w_e, w_f, seqs;   // scan / extraction work buffers, the extracted bases
     int64_t n_data = 0;    // bytes of `data` that are filled
     int64_t coff0 = 0;     // compressed offset of the inflated stretch
-    uint8_t* ring_mem = nullptr;            // strk_dbam_inflate_file: pinned pieces, their stream and events
-    hipStream_t ring_stream = nullptr;
-    hipEvent_t ring_ev[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    PinnedBuf ring_mem;                     // strk_dbam_inflate_file: pinned pieces, their stream and events
+    Stream ring_stream;
+    Event ring_ev[6];
     bool to_eof = true;    // the stretch runs to the end of its file / buffer (a record cut off at its end is then an error)
     std::vector<int64_t> blk_coff, blk_out;   // per inflated block: its compressed offset and where its bytes start in `data`
     std::vector<int32_t> blk_len;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Event ev0, ev1;
     double kernel_ms = 0.0;   // HIP-event time of every kernel this object has launched
     double file_ms[3] = {0.0, 0.0, 0.0};   // last strk_dbam_inflate_file: buffers, read + upload, inflation (wall clock)
     void tic() { if (ev0) (void)hipEventRecord(ev0, 0); }
@@ -321,8 +320,8 @@ int strk_dbam_open(int device, strk_dbam** out) {
     HIP_TRY(hipSetDevice(device));
     strk_dbam* d = new strk_dbam();
     d->device = device;
-    (void)hipEventCreate(&d->ev0);
-    (void)hipEventCreate(&d->ev1);
+    (void)hipEventCreate(&d->ev0.h);
+    (void)hipEventCreate(&d->ev1.h);
     *out = d;
     return 0;
 }
@@ -332,20 +331,13 @@ void strk_dbam_close(strk_dbam* d) {
     (void)hipSetDevice(d->device);
     dbam_park(d->device, d->data);
     dbam_park(d->device, d->comp);
-    d->blocks.release(); d->lens.release(); d->status.release();
-    d->w_a.release(); d->w_b.release(); d->w_c.release(); d->w_d.release(); d->w_e.release(); d->w_f.release(); d->seqs.release();
-    if (d->ring_stream) { (void)hipStreamSynchronize(d->ring_stream); (void)hipStreamDestroy(d->ring_stream); }
-    for (auto e : d->ring_ev) if (e) (void)hipEventDestroy(e);
-    if (d->ring_mem) {
+    if (d->ring_stream) (void)hipStreamSynchronize(d->ring_stream);
+    if (d->ring_mem.p) {   // one pinned ring per device is kept for the next reader
         std::lock_guard<std::mutex> lk(g_park_mu);
         bool have = false;
         for (auto& r : g_parked_rings) have = have || r.first == d->device;
-        if (have) (void)hipHostFree(d->ring_mem);
-        else g_parked_rings.emplace_back(d->device, d->ring_mem);
-        d->ring_mem = nullptr;
+        if (!have) g_parked_rings.emplace_back(d->device, std::move(d->ring_mem));
     }
-    if (d->ev0) (void)hipEventDestroy(d->ev0);
-    if (d->ev1) (void)hipEventDestroy(d->ev1);
     delete d;
 }
 
@@ -418,22 +410,22 @@ static int64_t dbam_inflate_file_impl(strk_dbam* d, const char* path, int64_t lo
     if (rc) { ::close(fd); return rc; }
     // the ring of pinned pieces, its stream and events belong to the object: a file walked span by span allocates them once
     hipError_t he = hipSuccess;
-    if (!d->ring_mem) {
+    if (!d->ring_mem.p) {
         std::lock_guard<std::mutex> lk(g_park_mu);
         for (size_t i = 0; i < g_parked_rings.size(); ++i)
             if (g_parked_rings[i].first == d->device) {
-                d->ring_mem = g_parked_rings[i].second;
+                d->ring_mem = std::move(g_parked_rings[i].second);
                 g_parked_rings.erase(g_parked_rings.begin() + (long)i);
                 break;
             }
     }
-    if (!d->ring_mem) he = hipHostMalloc((void**)&d->ring_mem, (size_t)kRing * kPiece, hipHostMallocDefault);
-    if (he == hipSuccess && !d->ring_stream) he = hipStreamCreateWithFlags(&d->ring_stream, hipStreamNonBlocking);
+    if (!d->ring_mem.p) he = d->ring_mem.alloc((size_t)kRing * kPiece);
+    if (he == hipSuccess && !d->ring_stream) he = hipStreamCreateWithFlags(&d->ring_stream.h, hipStreamNonBlocking);
     for (int i = 0; i < kRing && he == hipSuccess; ++i)
-        if (!d->ring_ev[i]) he = hipEventCreateWithFlags(&d->ring_ev[i], hipEventDisableTiming);
-    uint8_t* const pinned = d->ring_mem;
+        if (!d->ring_ev[i]) he = hipEventCreateWithFlags(&d->ring_ev[i].h, hipEventDisableTiming);
+    uint8_t* const pinned = d->ring_mem.as<uint8_t>();
     const hipStream_t stream = d->ring_stream;
-    hipEvent_t* const ev = d->ring_ev;
+    Event* const ev = d->ring_ev;
     std::mutex mu;
     std::condition_variable cv;
     std::vector<char> loaded((size_t)n_pieces, 0);
@@ -573,7 +565,7 @@ void strk_dbam_release_cache(void) {
     g_parked.clear();
     for (auto& r : g_parked_rings) {
         (void)hipSetDevice(r.first);
-        (void)hipHostFree(r.second);
+        r.second.release();
     }
     g_parked_rings.clear();
 }

@@ -40,7 +40,7 @@ int call_alleles_impl(strk_ctx* c, int32_t n_loci, const int32_t* read_off, cons
             if (!std::isfinite(w[r]) || !(w[r] > 0.0)) return fail(STRK_E_INVALID, "locus %d: read %d has weight %g", l, r, w[r]);
     }
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->al_stream) HIP_TRY(hipStreamCreateWithFlags(&c->al_stream, hipStreamNonBlocking));
+    if (!c->al_stream) HIP_TRY(hipStreamCreateWithFlags(&c->al_stream.h, hipStreamNonBlocking));
     hipStream_t st = c->al_stream;
     const int B = p->num_bootstrap;
     const int threads = std::min(256, (B + 63) / 64 * 64);

@@ -35,7 +35,7 @@ int best_rep_impl(strk_ctx* c, int32_t n_groups, const int32_t* group_off, const
     }
     if (n_seq_bytes > 0 && !seqs && !d_seqs && max_len > 0) return fail(STRK_E_INVALID, "seqs is NULL");
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->cs_stream) HIP_TRY(hipStreamCreateWithFlags(&c->cs_stream, hipStreamNonBlocking));
+    if (!c->cs_stream) HIP_TRY(hipStreamCreateWithFlags(&c->cs_stream.h, hipStreamNonBlocking));
     hipStream_t st = c->cs_stream;
     int rc;
     if ((rc = c->cs_off.ensure(((size_t)n_groups + 1) * 4))) return rc;

@@ -225,25 +225,13 @@ int resolve_misses(strk_ctx* c, const strk_batch* b, const strk_params& p, KArgs
         a2.band_mode = 0;   // window-miss rounds always score exactly
         a2.exact = nullptr;
         std::vector<int32_t> t2(tab2);
-        for (int attempt = 0;; ++attempt) {
-            HIP_TRY(hipMemsetAsync(c->counters.p, 0, kCountersBytes, st));
-            enqueue_scoring(c, a2, 1, c->items.as<int32_t>(), (int)items.size(), 0, st, false);
-            HIP_TRY(hipMemcpyAsync(c->h_counters, c->counters.p, kCountersBytes, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(t2.data(), c->table2.p, tab2 * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipStreamSynchronize(st));
-            HIP_TRY(hipGetLastError());
-            if (attempt < 3 && grow_scratch(c)) {   // (widened windows: hundreds of generic-kernel rows each, or a start far above the tract)
-                a.scratch = a2.scratch = c->scratch.as<int32_t>();
-                a.scratch_cap = a2.scratch_cap = (long long)c->scratch_ints;
-                a.long_slot = a2.long_slot = (long long)c->long_slot_ints;
-                continue;
-            }
-            break;
-        }
-        if ((rc = check_error_bits(c->h_counters[kCntError] & ~kErrEmpty))) return rc;
+        // (widened windows: hundreds of generic-kernel rows each, or a start far above the tract — the scratch may have to grow)
+        if ((rc = score_until_scratch_fits(c, a2, c->items.as<int32_t>(), (int)items.size(), 0, st, false, &a, t2.data(), c->table2.p, tab2 * 4)))
+            return rc;
+        if ((rc = check_error_bits(c->h_counters.cnt(kCntError) & ~kErrEmpty))) return rc;
         if (stats) {
-            stats->n_fallback += c->h_counters[kCntClass0 + kGenericClass];
-            stats->dp_cells += (int64_t) * reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(c->h_counters) + kCellsOff);
+            stats->n_fallback += c->h_counters.cnt(kCntClass0 + kGenericClass);
+            stats->dp_cells += (int64_t)c->h_counters.cells();
         }
         for (size_t i = 0; i < items.size(); ++i) {
             MissLocus* L = it_L[i];

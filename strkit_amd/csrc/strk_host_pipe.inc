@@ -1,6 +1,6 @@
 // Pipelined host-buffer entry point: count_loci_pipelined() behind strk_count_loci.
-// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, strk_ctx, submit_device /
-// finish_device defined there); not a stand-alone header.
+// Part of strk_api.hip: included inside its anonymous namespace (uses the owning types of strk_host.h, strk_ctx, check_batch_range,
+// submit_device / finish_device defined there); not a stand-alone header.
 //
 // What it replaces: upload of the whole batch from pageable memory, compute, four blocking downloads — one after the other
 // (65 M reads/s on the bench workload while the device-resident path ran at 216 M).  The reference's worker loop hands one
@@ -95,13 +95,14 @@ struct HostPipe {
     // band pass wait for the persistent band blocks of the other two — profiles/README.md round 3 — so two it is.)
     static constexpr int kSlots = 4, kCtx = 2;
     enum State { kFree = 0, kUploaded, kComputing };
+    // (members are destroyed last to first: the compute contexts, the slots, the copy stream, the copy threads)
+    size_t sub_bytes = 0;
+    std::unique_ptr<CopyPool> pool;
+    Stream copy_st;
     struct Slot {
-        uint8_t* h_in = nullptr;
-        size_t h_in_cap = 0;
-        int32_t* h_out = nullptr;
-        size_t h_out_cap = 0;
+        PinnedBuf h_in, h_out;   // the staged sub-batch; its four result arrays
         DevBuf d_in, d_out;
-        hipEvent_t ev_h2d = nullptr;
+        Event ev_h2d;
         State state = kFree;
         int ctx = -1;            // compute context while kComputing
         int seq = 0;             // submission order
@@ -110,67 +111,29 @@ struct HostPipe {
     } slot[kSlots];
     struct Ctx {
         strk_ctx* sub = nullptr;
-        hipStream_t st = nullptr;
+        Stream st;
         bool busy = false;
+        ~Ctx() { strk_destroy(sub); }
     } ctx[kCtx];
-    hipStream_t copy_st = nullptr;
-    CopyPool* pool = nullptr;
-    size_t sub_bytes = 0;
 };
-
-void pipe_destroy(HostPipe* p) {
-    if (!p) return;
-    for (auto& c : p->ctx) {
-        if (c.sub) strk_destroy(c.sub);
-        if (c.st) (void)hipStreamDestroy(c.st);
-    }
-    for (auto& s : p->slot) {
-        if (s.ev_h2d) (void)hipEventDestroy(s.ev_h2d);
-        if (s.h_in) (void)hipHostFree(s.h_in);
-        if (s.h_out) (void)hipHostFree(s.h_out);
-        s.d_in.release();
-        s.d_out.release();
-    }
-    if (p->copy_st) (void)hipStreamDestroy(p->copy_st);
-    delete p->pool;
-    delete p;
-}
 
 int pipe_get(strk_ctx* c, HostPipe** out) {
     if (c->pipe) { *out = c->pipe; return 0; }
-    HostPipe* p = new HostPipe();
+    std::unique_ptr<HostPipe> p(new HostPipe());
     p->sub_bytes = pipe_sub_bytes();
     const char* t = getenv("STRKIT_AMD_COPY_THREADS");
-    p->pool = new CopyPool(std::max(0, std::min(15, t ? atoi(t) : std::min(7, host_cpus() - 1))));
-    bool ok = hipStreamCreateWithFlags(&p->copy_st, hipStreamNonBlocking) == hipSuccess;
+    p->pool.reset(new CopyPool(std::max(0, std::min(15, t ? atoi(t) : std::min(7, host_cpus() - 1)))));
+    bool ok = hipStreamCreateWithFlags(&p->copy_st.h, hipStreamNonBlocking) == hipSuccess;
     for (auto& x : p->ctx) {
         if (!ok) break;
         const int rc = strk_init(c->device, &x.sub);
-        if (rc) { pipe_destroy(p); return rc; }
-        ok = hipStreamCreateWithFlags(&x.st, hipStreamNonBlocking) == hipSuccess;
+        if (rc) return rc;
+        ok = hipStreamCreateWithFlags(&x.st.h, hipStreamNonBlocking) == hipSuccess;
     }
     for (auto& s : p->slot)
-        if (ok) ok = hipEventCreateWithFlags(&s.ev_h2d, hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        pipe_destroy(p);
-        return fail(STRK_E_DEVICE, "host pipeline: stream / event creation failed");
-    }
-    c->pipe = p;
-    *out = p;
-    return 0;
-}
-
-int pinned_ensure(uint8_t** ptr, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return 0;
-    if (*ptr) (void)hipHostFree(*ptr);
-    *ptr = nullptr;
-    *cap = 0;
-    const size_t want = bytes + bytes / 4 + 4096;
-    if (hipHostMalloc(reinterpret_cast<void**>(ptr), want, hipHostMallocDefault) != hipSuccess) {
-        *ptr = nullptr;
-        return fail(STRK_E_NOMEM, "hipHostMalloc(%zu) failed", want);
-    }
-    *cap = want;
+        if (ok) ok = hipEventCreateWithFlags(&s.ev_h2d.h, hipEventDisableTiming) == hipSuccess;
+    if (!ok) return fail(STRK_E_DEVICE, "host pipeline: stream / event creation failed");
+    c->pipe = *out = p.release();
     return 0;
 }
 
@@ -188,20 +151,13 @@ bool host_range_pinned(const void* ptr, size_t bytes) {
     return true;
 }
 
-// Validates loci [l0, l1) of the host batch (the checks of upload_batch), stages them into the slot's pinned block and
+// Validates loci [l0, l1) of the host batch (check_batch_range), stages them into the slot's pinned block and
 // enqueues its upload on the copy stream.
 int pipe_upload(HostPipe* p, HostPipe::Slot& s, const strk_batch* b, int l0, int l1, bool direct) {
     const int r0 = b->read_off[l0], r1 = b->read_off[l1];
     const size_t nr = (size_t)(r1 - r0), nl = (size_t)(l1 - l0);
-    for (int l = l0; l < l1; ++l) {
-        if (b->read_off[l + 1] < b->read_off[l]) return fail(STRK_E_INVALID, "read_off must be non-decreasing");
-        if (b->motif_off[l + 1] <= b->motif_off[l]) return fail(STRK_E_INVALID, "locus %d has an empty motif", l);
-    }
-    for (int r = r0; r < r1; ++r) {
-        if (b->nfl[r] < 0 || b->ntr[r] < 0 || b->nfr[r] < 0) return fail(STRK_E_INVALID, "read %d has a negative length", r);
-        if (b->seq_off[r + 1] - b->seq_off[r] != (int64_t)b->nfl[r] + b->ntr[r] + b->nfr[r])
-            return fail(STRK_E_INVALID, "read %d: seq_off does not match nfl+ntr+nfr", r);
-    }
+    int rc;
+    if ((rc = check_batch_range(b, (size_t)l0, (size_t)l1))) return rc;
     const int64_t s0 = b->seq_off[r0], s1 = b->seq_off[r1];
     const int32_t m0 = b->motif_off[l0], m1 = b->motif_off[l1];
     const size_t nbases = (size_t)(s1 - s0), nmot = (size_t)(m1 - m0);
@@ -214,17 +170,17 @@ int pipe_upload(HostPipe* p, HostPipe::Slot& s, const strk_batch* b, int l0, int
     const size_t o_motifs = o_motif_off + up16((nl + 1) * 4);
     const size_t o_seqs = o_motifs + up16(nmot + 1);
     const size_t total = o_seqs + up16(nbases + 16);
-    int rc;
-    if ((rc = pinned_ensure(&s.h_in, &s.h_in_cap, total))) return rc;
+    if ((rc = s.h_in.ensure(total))) return rc;
     if ((rc = s.d_in.ensure(total))) return rc;
     if ((rc = s.d_out.ensure(std::max<size_t>(nr, 1) * 16))) return rc;
-    if ((rc = pinned_ensure(reinterpret_cast<uint8_t**>(&s.h_out), &s.h_out_cap, std::max<size_t>(nr, 1) * 16))) return rc;
+    if ((rc = s.h_out.ensure(std::max<size_t>(nr, 1) * 16))) return rc;
+    uint8_t* const h_in = s.h_in.as<uint8_t>();
     {
         std::vector<CopyPool::Piece> pieces;
         auto add = [&](size_t off, const void* src, size_t n) {
             const uint8_t* sp = static_cast<const uint8_t*>(src);
             constexpr size_t kPiece = (size_t)512 << 10;
-            for (size_t k = 0; k < n; k += kPiece) pieces.push_back({s.h_in + off + k, sp + k, std::min(kPiece, n - k)});
+            for (size_t k = 0; k < n; k += kPiece) pieces.push_back({h_in + off + k, sp + k, std::min(kPiece, n - k)});
         };
         add(o_seq_off, b->seq_off + r0, (nr + 1) * 8);
         add(o_nfl, b->nfl + r0, nr * 4);
@@ -233,8 +189,8 @@ int pipe_upload(HostPipe* p, HostPipe::Slot& s, const strk_batch* b, int l0, int
         add(o_est, b->est_cn + r0, nr * 4);
         add(o_motifs, b->motifs + m0, nmot);
         if (!direct) add(o_seqs, b->seqs + s0, nbases);
-        int32_t* ro = reinterpret_cast<int32_t*>(s.h_in + o_read_off);
-        int32_t* mo = reinterpret_cast<int32_t*>(s.h_in + o_motif_off);
+        int32_t* ro = reinterpret_cast<int32_t*>(h_in + o_read_off);
+        int32_t* mo = reinterpret_cast<int32_t*>(h_in + o_motif_off);
         for (size_t k = 0; k <= nl; ++k) {
             ro[k] = b->read_off[l0 + k] - r0;
             mo[k] = b->motif_off[l0 + k] - m0;
@@ -245,10 +201,10 @@ int pipe_upload(HostPipe* p, HostPipe::Slot& s, const strk_batch* b, int l0, int
     if (direct) {
         // the caller's bases are page-locked: DMA from where they lie (93 % of the bytes); the per-read arrays and the rebased
         // offsets (24 bytes per read) travel in the slot's block as before — two copies per sub-batch, not seven
-        HIP_TRY(hipMemcpyAsync(d, s.h_in, o_seqs, hipMemcpyHostToDevice, p->copy_st));
+        HIP_TRY(hipMemcpyAsync(d, h_in, o_seqs, hipMemcpyHostToDevice, p->copy_st));
         if (nbases) HIP_TRY(hipMemcpyAsync(d + o_seqs, b->seqs + s0, nbases, hipMemcpyHostToDevice, p->copy_st));
     } else {
-        HIP_TRY(hipMemcpyAsync(s.d_in.p, s.h_in, total, hipMemcpyHostToDevice, p->copy_st));
+        HIP_TRY(hipMemcpyAsync(s.d_in.p, h_in, total, hipMemcpyHostToDevice, p->copy_st));
     }
     HIP_TRY(hipEventRecord(s.ev_h2d, p->copy_st));
     strk_batch& db = s.db;
@@ -293,12 +249,13 @@ int pipe_complete(HostPipe* p, HostPipe::Slot& s, int32_t* out_cn, int32_t* out_
     if (rc && rc != STRK_E_EMPTY) return rc;
     const size_t nr = (size_t)s.nr, stride = std::max<size_t>(nr, 1);
     if (nr) {
-        HIP_TRY(hipMemcpyAsync(s.h_out, s.d_out.p, stride * 16, hipMemcpyDeviceToHost, c.st));
+        const int32_t* h_out = s.h_out.as<int32_t>();
+        HIP_TRY(hipMemcpyAsync(s.h_out.p, s.d_out.p, stride * 16, hipMemcpyDeviceToHost, c.st));
         HIP_TRY(hipStreamSynchronize(c.st));
-        if (out_cn) memcpy(out_cn + s.r0, s.h_out, nr * 4);
-        if (out_score) memcpy(out_score + s.r0, s.h_out + stride, nr * 4);
-        if (out_n) memcpy(out_n + s.r0, s.h_out + 2 * stride, nr * 4);
-        if (out_start) memcpy(out_start + s.r0, s.h_out + 3 * stride, nr * 4);
+        if (out_cn) memcpy(out_cn + s.r0, h_out, nr * 4);
+        if (out_score) memcpy(out_score + s.r0, h_out + stride, nr * 4);
+        if (out_n) memcpy(out_n + s.r0, h_out + 2 * stride, nr * 4);
+        if (out_start) memcpy(out_start + s.r0, h_out + 3 * stride, nr * 4);
     }
     if (agg) {
         agg->dp_cells += st.dp_cells; agg->n_fallback += st.n_fallback; agg->n_miss_reads += st.n_miss_reads;
@@ -327,9 +284,8 @@ int count_loci_pipelined(strk_ctx* c, const strk_batch* b, const strk_params* pa
     if (b->read_off[0] != 0 || b->read_off[b->n_loci] != b->n_reads) return 0;
     // the cutting loop below indexes seq_off / nfl / ... with read_off[l] of loci beyond the sub-batch being validated: one pass
     // over the offsets first (a violation: the direct path reports it as STRK_E_INVALID)
-    for (int l = 0; l < b->n_loci; ++l)
-        if (b->read_off[l] < 0 || b->read_off[l + 1] < b->read_off[l] || b->read_off[l + 1] > b->n_reads || b->motif_off[l + 1] <= b->motif_off[l])
-            return 0;
+    // (non-decreasing from read_off[0] = 0 to read_off[n_loci] = n_reads: every one of them is a read of the batch)
+    if (check_batch_loci(b, 0, (size_t)b->n_loci)) return 0;
     const int64_t total_bytes = b->seq_off[b->n_reads] - b->seq_off[0] + (int64_t)b->n_reads * 24;
     // (the decision needs the sub-batch size, which lives in the pipe: cheap to read before the pipe exists)
     if (total_bytes < (int64_t)(pipe_sub_bytes() / 2)) return 0;

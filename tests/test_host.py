@@ -470,3 +470,150 @@ int main() {
         assert g == w, (k, lines[k][:80], g, w)
         seen_kinds.add(w if isinstance(w, str) else "found")
     assert seen_kinds == {"miss", "found"} or seen_kinds == {"miss", "found", "empty"}
+
+
+def test_adaptive_policies_follow_their_scripted_trajectories(tmp_path):
+    """Host build of strk_policy.h (no HIP in it): the default-window policy, the band gate and the grid history driven through
+    scripted call sequences.  The expected trajectories are the rules the host side has applied since round 4 (window levels
+    +-4 5 6 8 11 15, start +-8, floor +-6 / +-8 for motifs of 1-2 bases; band cool-downs 32 .. 16 384; grids from the previous
+    call's queue lengths with 50 % head-room), written out here by hand."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no host C++ compiler")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = tmp_path / "policy_check.cpp"
+    src.write_text(r"""
+#include <cstdio>
+#include <cstring>
+#include "%s/strkit_amd/csrc/strk_policy.h"
+// one command per line, one line of output per command:
+//   w k reach               window of bucket k for local_search_range + step_size = reach
+//   u k loci miss reps      `reps` finished calls with `loci` loci and `miss` window misses in bucket k; prints the +-window of k
+//   r                       reset; prints the five windows
+//   b reads fallbacks reps  band gate: `reps` finished calls; prints cooldown penalty probation
+//   h prob bm reads exact wide long band_cells wide_cells    grid history of a finished call; prints valid tail_heavy
+//   p mode bm chunks reads full                              predicted blocks
+int main() {
+    strk_policy::WindowPolicy win;
+    strk_policy::BandGate gate;
+    strk_policy::GridHistory hist;
+    char cmd;
+    long long a[8];
+    while (scanf(" %%c", &cmd) == 1) {
+        if (cmd == 'w') { scanf("%%lld %%lld", a, a + 1); printf("%%d\n", win.window((int)a[0], (int)a[1])); }
+        else if (cmd == 'u') {
+            scanf("%%lld %%lld %%lld %%lld", a, a + 1, a + 2, a + 3);
+            for (long long i = 0; i < a[3]; ++i) win.update((int)a[0], (int)a[1], (int)a[2]);
+            printf("%%d\n", win.window((int)a[0], 0));
+        } else if (cmd == 'r') {
+            win.reset();
+            for (int k = 0; k < strk_policy::kWinBuckets; ++k) printf("%%d ", win.window(k, 0));
+            printf("\n");
+        } else if (cmd == 'b') {
+            scanf("%%lld %%lld %%lld", a, a + 1, a + 2);
+            for (long long i = 0; i < a[2]; ++i) gate.update((int)a[0], (int)a[1]);
+            printf("%%d %%d %%d\n", gate.cooldown, gate.penalty, (int)gate.probation);
+        } else if (cmd == 'h') {
+            for (int i = 0; i < 8; ++i) scanf("%%lld", a + i);
+            hist.update(a[0] != 0, (int)a[1], (int)a[2], (int)a[3], (int)a[4], (int)a[5], (uint64_t)a[6], (uint64_t)a[7]);
+            printf("%%d %%d\n", (int)hist.valid, (int)hist.tail_heavy);
+        } else if (cmd == 'p') {
+            for (int i = 0; i < 5; ++i) scanf("%%lld", a + i);
+            printf("%%d\n", hist.predicted_blocks(hist.usable((int)a[0], (int)a[1]), (int)a[2], (int)a[3], (int)a[4]));
+        }
+    }
+    return 0;
+}
+""" % root)
+    exe = tmp_path / "policy_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), str(src)], check=True)
+    script = []            # (command, expected output line)
+
+    def step(cmd, want):
+        script.append((cmd, " ".join(str(x) for x in want) if isinstance(want, (tuple, list)) else str(want)))
+
+    QUIET, MID, MISS = "1000 1", "1000 3", "1000 5"     # misses <= loci / 1000 | in between | > max(1, loci / 250)
+    # --- window -----------------------------------------------------------------------------------------------------------
+    step("r", "8 8 8 8 8 ")
+    for k in range(5):                                   # eight quiet calls: buckets 1-4 to +-6, bucket 0 stays at +-8
+        step(f"u {k} {QUIET} 7", 8)
+        step(f"u {k} {QUIET} 1", 8 if k == 0 else 6)
+    step(f"u 0 {QUIET} 5000", 8)                         # ... and nothing below the bucket's floor
+    step(f"u 1 {QUIET} 5000", 6)
+    # a step down followed by a call with misses is a failed probe: up at once, and the next step down needs 64, 128 ... 4 096
+    for failed in range(1, 10):
+        step(f"u 1 {MISS} 1", 8)
+        need = min(64 << (failed - 1), 4096)
+        step(f"u 1 {QUIET} {need - 1}", 8)
+        step(f"u 1 {QUIET} 1", 6)
+    step("r", "8 8 8 8 8 ")                              # reset restores all of it: eight quiet calls are enough again
+    step(f"u 1 {QUIET} 7", 8)
+    step(f"u 1 {QUIET} 1", 6)
+    step("r", "8 8 8 8 8 ")
+    step(f"u 2 {MISS} 1", 11)                            # one level up per call with misses, up to +-15
+    step(f"u 2 {MISS} 1", 15)
+    step(f"u 2 {MISS} 1", 15)
+    step("w 2 0", 15)
+    step(f"u 2 {QUIET} 63", 15)                          # above the start level a step down needs 64 quiet calls
+    step(f"u 2 {QUIET} 1", 11)
+    step(f"u 2 {QUIET} 63", 11)
+    step(f"u 2 {QUIET} 1", 8)
+    step(f"u 2 {QUIET} 7", 8)                            # (these were no failed probes: from the start level, eight)
+    step(f"u 2 {QUIET} 1", 6)
+    step(f"u 3 {QUIET} 7", 8)                            # a call in between only zeroes the quiet count
+    step(f"u 3 {MID} 1", 8)
+    step(f"u 3 {QUIET} 7", 8)
+    step(f"u 3 {QUIET} 1", 6)
+    step("u 4 100 1 1", 8)                               # small calls: one miss of 100 loci is "in between", two are misses
+    step("u 4 100 2 1", 11)
+    step("r", "8 8 8 8 8 ")
+    step(f"u 1 {QUIET} 7", 8)                            # a bucket with no loci in the call is not touched
+    step("u 1 0 0 10", 8)
+    step("u 1 0 5 10", 8)
+    step(f"u 1 {QUIET} 1", 6)
+    step("w 0 3", 8)                                     # never less than min(15, local_search_range + step_size)
+    step("w 0 10", 10)
+    step("w 0 20", 15)
+    step("w 1 3", 6)
+    step("w 1 7", 7)
+    step("w 1 99", 15)
+    # --- band gate --------------------------------------------------------------------------------------------------------
+    step("b 63 63 1", (0, 32, 1))                        # starts on probation; fewer than 64 band reads change nothing
+    step("b 0 0 5", (0, 32, 1))
+    penalty = 32
+    for _ in range(12):                                  # fall-backs > half: cool-down, probation, the next penalty doubled
+        nxt = min(2 * penalty, 16384)
+        step("b 64 33 1", (penalty, nxt, 1))
+        step("b 1000 0 1", (penalty - 1, nxt, 1))        # a cool-down counts down one per call whatever the call held
+        step(f"b 1000 1000 {penalty - 2}", (1, nxt, 1))
+        step("b 10 0 1", (0, nxt, 1))
+        penalty = nxt
+    assert penalty == 16384
+    step("b 64 32 1", (0, 32, 0))                        # a healthy call (half is not "more than half") ends probation
+    step("b 63 63 1", (0, 32, 0))
+    step("b 100 51 1", (32, 64, 1))
+    # --- grid history -----------------------------------------------------------------------------------------------------
+    step("p 0 1 100 1000 2000", 2000)                    # no history: the full grid
+    step("h 1 1 1000 40 100 0 1000 300", (0, 1))         # a call on probation: invalid
+    step("p 0 1 100 1000 2000", 2000)
+    step("h 0 1 1000 40 100 0 1000 300", (1, 1))
+    step("p 0 1 100 1000 2000", 39)                      # floor(100 * 1000 / 1000 * 1.5 / 4) + 2
+    step("p 0 1 100 2000 2000", 77)
+    step("p 0 1 100 0 2000", 2)                          # (an empty batch counts as one read)
+    step("p 0 0 100 1000 2000", 2000)                    # another band mode
+    step("p 1 1 100 1000 2000", 2000)                    # not a whole batched call
+    step("p 0 1 0 1000 2000", 1)                         # an empty queue
+    step("p 0 1 100000 1000 2000", 2000)                 # clamped to [1, full]
+    step("p 0 1 100 1000 10", 10)
+    step("h 0 0 0 4 4 4 1000 250", (1, 0))               # tail_heavy: each band kernel more than a quarter of the other's cells
+    step("p 0 0 4 3 100", 6)                             # (hist_reads = max(1, n_reads))
+    step("p 0 1 4 3 100", 100)
+    step("h 0 1 10 0 0 0 1000 4001", (1, 0))
+    step("h 0 1 10 0 0 0 1000 3999", (1, 1))
+    step("h 0 1 10 0 0 0 251 1000", (1, 1))
+    step("h 0 1 10 0 0 0 0 0", (1, 0))
+    out = subprocess.run([str(exe)], input="\n".join(c for c, _ in script) + "\n", check=True, capture_output=True, text=True).stdout.split("\n")
+    assert len(out) == len(script) + 1
+    for k, ((cmd, want), got) in enumerate(zip(script, out)):
+        assert got.rstrip() == want.rstrip(), (k, cmd, got, want)
