@@ -119,7 +119,10 @@ typedef struct strk_batch {
     const int32_t* motif_off; /* [n_loci + 1] */
 } strk_batch;
 
-/* Per-call statistics (all optional output). */
+/* Per-call statistics (all optional output).  The field comments describe strk_count_loci and its kin; the entry points that
+ * are not about reads (strk_realign, strk_call_alleles, strk_best_representatives, strk_count_kmers) fill a few of the fields
+ * with meanings of their own, named in each function's comment (strk_count_kmers: dp_cells = windows, n_fallback = groups
+ * that spilled, n_miss_reads = groups on the general path, n_sub_batches = launches of the sort kernel). */
 typedef struct strk_stats {
     int64_t dp_cells;      /* DP cell updates executed by the device kernels */
     int32_t n_fallback;    /* reads scored by the generic (non-systolic) kernel */
@@ -321,6 +324,40 @@ int strk_best_representatives(strk_ctx* ctx, int32_t n_groups, const int32_t* gr
 int strk_best_representatives_dseqs(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const void* d_seqs,
                                     int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len, int32_t* out_index,
                                     int32_t* out_method, int64_t* out_dist_sum, strk_stats* stats);
+
+/* ---- distinct windows (k-mers) of a group of sequences, counted ----------------------------------------------------
+ * Stands where the reference counts motif-sized k-mers per read (call_locus.py:1287) and per allele (:1526-1593, :1635).
+ * A group is an ordered list of byte strings with one window length k >= 1.  Its windows are the s[i : i+k],
+ * 0 <= i <= len(s) - k, of every string s (a string shorter than k has none).  The result holds one entry per distinct window:
+ * the count over all strings (duplicates as often as they occur) and the place of the first occurrence (smallest string
+ * index in the group, then smallest i).  Entries are in ascending unsigned lexicographic order of the window's bytes; raw
+ * bytes, case-sensitive, exact for arbitrary byte values.  A group without windows has no entries; a group's counts add up
+ * to its number of windows.  The result does not depend on launch geometry.  Unpinned against STRkit, whose counter is not
+ * in its tree.
+ *
+ * Groups and sequences as for strk_best_representatives (at most 250 per group, lengths 0 .. 65 535, slices inside
+ * n_seq_bytes, slices may overlap); k[g] >= 1 per group.  Returns the number of entries E of all groups, or a negative
+ * STRK_E_* code.  out_entry_off [n_groups + 1] is always written; out_pos [cap] (byte offset into `seqs` of the window's first
+ * occurrence) and out_count [cap] only if E <= cap: cap = 0 with NULL arrays is a size query (call again with larger
+ * arrays, as for strk_bam_scan).  All buffers are host buffers; every input is checked before the first launch.  stats
+ * (optional) receives kernel_ms, n_dp_launches, dp_cells = the windows, n_fallback = the groups whose distinct windows did
+ * not fit the on-chip table, n_miss_reads = the groups whose windows do not pack into 64 bits, n_sub_batches = the launches
+ * the workspace bound cut those groups into. */
+int64_t strk_count_kmers(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off /*[n_groups+1]*/, const uint8_t* seqs,
+                         int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len, const int32_t* k /*[n_groups]*/,
+                         int64_t cap, int64_t* out_entry_off /*[n_groups+1]*/, int64_t* out_pos /*[cap]*/,
+                         int32_t* out_count /*[cap]*/, strk_stats* stats);
+/* The same with the bases already in memory of the context's device; everything else on the host. */
+int64_t strk_count_kmers_dseqs(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const void* d_seqs, int64_t n_seq_bytes,
+                               const int64_t* seq_start, const int32_t* seq_len, const int32_t* k, int64_t cap,
+                               int64_t* out_entry_off, int64_t* out_pos, int32_t* out_count, strk_stats* stats);
+/* The general form: exactly one of seqs (host) and d_seqs (device) is not NULL, and workspace_bytes bounds the device
+ * workspace of one launch over the groups that the on-chip table cannot take (<= 0: the default, 1 GiB; a single group that
+ * needs more runs alone).  The result does not depend on it. */
+int64_t strk_count_kmers_ws(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const uint8_t* seqs, const void* d_seqs,
+                            int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len, const int32_t* k, int64_t cap,
+                            int64_t* out_entry_off, int64_t* out_pos, int32_t* out_count, int64_t workspace_bytes,
+                            strk_stats* stats);
 
 /* ---- host-side front end (CPU only; no context, thread-safe) ---------------------------------------------------
  * What the reference's Rust extension does before the counter runs: walk the alignment records

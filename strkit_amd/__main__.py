@@ -1,13 +1,14 @@
 """`python -m strkit_amd call <alignments.bam> --ref ref.fa --loci catalog.bed [--json out.json] [--realign]` — the
 subset of `strkit call` (strkit/entry.py:20-342) that the device backend covers: per-read copy numbers per locus and, with
-`--call-alleles`, a genotype per locus (`--consensus`: with the sequence of every allele, which a VCF with alleles needs)."""
+`--call-alleles`, a genotype per locus (`--consensus`: with the sequence of every allele, which a VCF with alleles needs);
+`--count-kmers`: the motif-sized k-mers of every tract, per read and per allele."""
 from __future__ import annotations
 
 import argparse
 import sys
 
 
-def main(argv=None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="strkit_amd")
     sub = ap.add_subparsers(dest="cmd", required=True)
     c = sub.add_parser("call", help="per-read repeat counts for every catalog locus")
@@ -31,6 +32,9 @@ def main(argv=None) -> int:
     c.add_argument("--consensus", action="store_true",
                    help="with --call-alleles: report the sequence of every allele (single / best_rep; no partial-order alignment)")
     c.add_argument("--n-alleles", type=int, choices=(1, 2), default=2, help="alleles per locus, all contigs")
+    c.add_argument("--count-kmers", "-k", nargs="?", type=str, default="none", const="peak", choices=("none", "peak", "read", "both"),
+                   help="count the motif-sized k-mers of every read's repeat tract (GPU): per read, summed per allele (peak; the "
+                        "default when the flag stands alone; needs --call-alleles), or both")
     # same names as `strkit call` (strkit/entry.py:20-342); --seed seeds the allele caller (the per-read path has no random
     # component), --processes sizes the locus blocks as the reference does (loci.py:193)
     c.add_argument("--sample-id", default=None)
@@ -39,9 +43,16 @@ def main(argv=None) -> int:
     c.add_argument("--rc-method", choices=("repalign",), default="repalign")
     c.add_argument("--max-rcn-iters", type=int, default=50)
     c.add_argument("--min-read-align-score", type=float, default=0.1)
+    return ap
+
+
+def main(argv=None) -> int:
+    ap = build_parser()
     a = ap.parse_args(argv)
     if a.consensus and not a.call_alleles:
         ap.error("--consensus needs --call-alleles")
+    if a.count_kmers in ("peak", "both") and not a.call_alleles:
+        ap.error(f"--count-kmers {a.count_kmers} needs --call-alleles")
     import os
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:   # python -m torch.distributed.run --nproc-per-node N -m strkit_amd call ...: one rank per GPU
@@ -58,6 +69,7 @@ def main(argv=None) -> int:
                       min_avg_phred=a.min_avg_phred, max_reads=a.max_reads, respect_ref=a.respect_ref,
                       sample_id=a.sample_id, processes=a.processes, rc_params=rc,
                       min_read_align_score=a.min_read_align_score, front_end=a.front_end, span_bytes=a.span_mb << 20,
+                      count_kmers=a.count_kmers,
                       **(dict(call_alleles=True, consensus=a.consensus or bool(a.vcf), seed=a.seed, n_alleles=a.n_alleles)
                          if a.call_alleles else {}))
     if world > 1:

@@ -6,6 +6,7 @@
 //   strk_host_miss.inc       window-miss rounds                       strk_host_pipe.inc       the pinned-slot host pipeline
 //   strk_host_ref.inc        reference side                           strk_host_realign.inc    realignment
 //   strk_host_alleles.inc    allele calling                           strk_host_consensus.inc  best representatives
+//   strk_host_kmers.inc      distinct windows (k-mer counts)
 //   strk_host_files.inc      the CPU-only file front end (its parser: strk_frontend.h)
 //   strk_dbam.inc            (at the end) the alignment file on the device: BGZF inflater, record scan, read extraction
 //
@@ -41,6 +42,7 @@
 #include "strk_inflate.h"
 #include "strk_alleles.h"
 #include "strk_consensus.h"
+#include "strk_kmers.h"
 
 namespace {
 
@@ -116,6 +118,9 @@ struct strk_ctx {
     // best representatives (strk_best_representatives), likewise
     DevBuf cs_off, cs_start, cs_len, cs_seqs, cs_bound, cs_out;
     Stream cs_stream;
+    // distinct windows (strk_count_kmers), likewise
+    DevBuf km_off, km_start, km_len, km_k, km_seqs, km_cnt, km_eoff, km_list, km_slist, km_wsoff, km_ws, km_out;
+    Stream km_stream;
     HostCounters h_counters;        // pinned: counters + cells + scratch_used
     // a chain of events along one call: start | after k_hash + k_plan | after k_dp_band | after k_dp_band_wide | after the
     // first k_replay pass | after k_dp_all / k_dp_ref | after k_dp_long | after k_dp_generic | end (after k_replay and the
@@ -756,6 +761,7 @@ int score_table_impl(strk_ctx* ctx, const strk_batch* batch, const int32_t* lo, 
 
 #include "strk_host_alleles.inc"
 #include "strk_host_consensus.inc"
+#include "strk_host_kmers.inc"
 
 }  // namespace
 
@@ -1008,6 +1014,42 @@ int strk_best_representatives_dseqs(strk_ctx* ctx, int32_t n_groups, const int32
     }
     return best_rep_impl(ctx, n_groups, group_off, nullptr, static_cast<const uint8_t*>(d_seqs), n_seq_bytes, seq_start, seq_len,
                          out_index, out_method, out_dist_sum, stats);
+}
+
+int64_t strk_count_kmers_ws(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const uint8_t* seqs, const void* d_seqs,
+                            int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len, const int32_t* k, int64_t cap,
+                            int64_t* out_entry_off, int64_t* out_pos, int32_t* out_count, int64_t workspace_bytes,
+                            strk_stats* stats) {
+    const char* fn = d_seqs ? "strk_count_kmers_dseqs" : "strk_count_kmers";
+    if (!ctx) return fail(STRK_E_INVALID, "%s: ctx is NULL", fn);
+    if (ctx->pending) return fail(STRK_E_INVALID, "%s: a submitted call is pending on this context", fn);
+    if (seqs && d_seqs) return fail(STRK_E_INVALID, "strk_count_kmers_ws: both seqs and d_seqs are given");
+    if (d_seqs) {
+        (void)hipSetDevice(ctx->device);
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, d_seqs) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+            (void)hipGetLastError();
+            return fail(STRK_E_INVALID, "%s: d_seqs is not device memory of device %d (the context's)", fn, ctx->device);
+        }
+    }
+    return count_kmers_impl(ctx, fn, n_groups, group_off, seqs, static_cast<const uint8_t*>(d_seqs), n_seq_bytes, seq_start,
+                            seq_len, k, cap, out_entry_off, out_pos, out_count, workspace_bytes, stats);
+}
+
+int64_t strk_count_kmers(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const uint8_t* seqs, int64_t n_seq_bytes,
+                         const int64_t* seq_start, const int32_t* seq_len, const int32_t* k, int64_t cap,
+                         int64_t* out_entry_off, int64_t* out_pos, int32_t* out_count, strk_stats* stats) {
+    return strk_count_kmers_ws(ctx, n_groups, group_off, seqs, nullptr, n_seq_bytes, seq_start, seq_len, k, cap, out_entry_off,
+                               out_pos, out_count, 0, stats);
+}
+
+int64_t strk_count_kmers_dseqs(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const void* d_seqs, int64_t n_seq_bytes,
+                               const int64_t* seq_start, const int32_t* seq_len, const int32_t* k, int64_t cap,
+                               int64_t* out_entry_off, int64_t* out_pos, int32_t* out_count, strk_stats* stats) {
+    if (!ctx) return fail(STRK_E_INVALID, "strk_count_kmers_dseqs: ctx is NULL");
+    if (!d_seqs) return fail(STRK_E_INVALID, "strk_count_kmers_dseqs: d_seqs is NULL");
+    return strk_count_kmers_ws(ctx, n_groups, group_off, nullptr, d_seqs, n_seq_bytes, seq_start, seq_len, k, cap, out_entry_off,
+                               out_pos, out_count, 0, stats);
 }
 
 int strk_ref_repeat_count_batch(strk_ctx* ctx, int32_t n_loci, const int32_t* start_count, const uint8_t* seqs,

@@ -29,7 +29,7 @@ from .bam import BamFile, read_bam
 from .extract import (LowMeanBaseQual, MIN_AVG_PHRED, get_read_coords_from_cigar, get_read_coords_from_matched_pairs,
                       get_sequence_data_for_locus)
 from .fasta import Fasta
-from .genotype import block_consensus, call_block_alleles, genotype_row
+from .genotype import block_consensus, block_kmers, call_block_alleles, genotype_row, kmers_row
 from .loci import Locus, load_loci, parse_loci_bed, resolve_contig
 from .native import DeviceBam, IndexedBam, NativeBam, extract_reads, host_header, realign_cigar_to_read_alignment
 from .output import read_weights
@@ -60,6 +60,18 @@ class CallOptions:
     allele_params: AlleleParams | None = None
     large_consensus_length: int = 1200
     max_n_large_consensus_reads: int = 20
+    # motif-sized k-mer counts of the tracts (strkit/call/params.py count_kmers): "none" | "peak" | "read" | "both"
+    count_kmers: str = "none"
+
+
+COUNT_KMERS_MODES = ("none", "peak", "read", "both")
+
+
+def _check_count_kmers(count_kmers, call_alleles: bool) -> None:
+    if count_kmers not in COUNT_KMERS_MODES:
+        raise ValueError(f"count_kmers must be one of {', '.join(COUNT_KMERS_MODES)}: got {count_kmers!r}")
+    if count_kmers in ("peak", "both") and not call_alleles:
+        raise ValueError(f"count_kmers={count_kmers!r} requires call_alleles=True: peak counts are those of called alleles")
 
 
 MAX_READS = 250                 # params.max_reads default (strkit/call/params.py:21)
@@ -253,11 +265,13 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, flank_size
                 span_bytes: int = 4 << 30, narrowing: int = _lib.STRK_NARROW_NONE, call_alleles: bool = False,
                 consensus: bool = False, seed: int | None = None, n_alleles: int | dict = 2,
                 allele_params: AlleleParams | None = None, large_consensus_length: int = 1200,
-                max_n_large_consensus_reads: int = 20) -> dict:
+                max_n_large_consensus_reads: int = 20, count_kmers: str = "none") -> dict:
     """`call_alleles`: a genotype per locus (call, intervals, peaks, a peak label `p` per read) from the GPU allele caller, with
     the locus seed alleles.locus_seed(seed, locus index); `seed=None` draws the run seed once and reports it.  `consensus`
     (needs call_alleles): the sequence of every allele and of its start anchor as peaks.seqs / peaks.start_anchor_seqs.
     `n_alleles`: 1 or 2, for all contigs or per contig in a dict.  Not available under torch.distributed yet.
+    `count_kmers`: "read" = every kept read record gets `kmers`, the counts of the motif-sized windows of its raw tract;
+    "peak" (needs call_alleles) = a called locus gets peaks.kmers, one dict per peak over all reads labelled with it; "both".
 
     `front_end` (for a `bam` given as a path): "device" = the file is inflated, scanned and cut on the GPU (DeviceBam) —
     whole when the compressed bytes plus their decompressed form (taken as `RESIDENT_FACTOR` times the file) fit into 90 % of
@@ -268,6 +282,10 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, flank_size
     when it has none.  Under torch.distributed every rank opens the file on its own GPU and calls its share of the blocks."""
     if consensus and not call_alleles:
         raise ValueError("consensus=True requires call_alleles=True: allele sequences are those of called alleles")
+    _check_count_kmers(count_kmers, call_alleles)
+    if count_kmers != "none" and _distributed():
+        raise NotImplementedError("count_kmers under torch.distributed: the fixed-size records that the ranks gather "
+                                  "(call_blocks_sharded) have no fields for k-mer counts yet; run one process")
     if call_alleles and _distributed():
         raise NotImplementedError("call_alleles=True under torch.distributed: the fixed-size records that the ranks gather "
                                   "(call_blocks_sharded) have no fields for calls and sequences yet; run one process")
@@ -324,7 +342,8 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, flank_size
             bam = IndexedBam(bam) if has_index else NativeBam(bam)
     t_open = time.perf_counter() - t_open       # (device reader: replaced below by the time its thread took)
     opts = CallOptions(flank_size, realign, min_avg_phred, max_reads, respect_ref, rc_params, min_read_align_score, tie_rule, end_flags, narrowing,
-                       call_alleles, consensus, seed, n_alleles, allele_params, large_consensus_length, max_n_large_consensus_reads)
+                       call_alleles, consensus, seed, n_alleles, allele_params, large_consensus_length, max_n_large_consensus_reads,
+                       count_kmers)
     try:
         ref = Fasta(ref) if isinstance(ref, str) else ref
         t0 = time.perf_counter()
@@ -398,7 +417,8 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, flank_size
                                "min_allele_reads": (allele_params or AlleleParams()).min_allele_reads,
                                "num_bootstrap": (allele_params or AlleleParams()).num_bootstrap} if call_alleles else {}),
                            **({"consensus": True, "large_consensus_length": large_consensus_length,
-                               "max_n_large_consensus_reads": max_n_large_consensus_reads} if consensus else {})},
+                               "max_n_large_consensus_reads": max_n_large_consensus_reads} if consensus else {}),
+                           **({"count_kmers": count_kmers} if count_kmers != "none" else {})},
             "contigs": sorted({r["contig"] for r in results}),
             "catalog": {"num_loci": len(results), "num_loci_unknown_contig": n_catalog - n_loaded},
             "results": results,
@@ -570,6 +590,7 @@ def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = Non
     opts = opts or CallOptions()
     if opts.consensus and not opts.call_alleles:
         raise ValueError("consensus=True requires call_alleles=True")
+    _check_count_kmers(opts.count_kmers, opts.call_alleles)
     if opts.call_alleles and opts.seed is None:
         raise ValueError("call_alleles=True needs a run seed (CallOptions.seed); call_sample draws one when none is given")
     ctx = ctx or _lib.default_context()
@@ -704,6 +725,7 @@ def _locus_row(locus: Locus, rd: dict, reads: dict, opts: CallOptions) -> dict:
 def _call_block_python(block, bam: BamFile, ref: Fasta, opts: CallOptions, ctx, tm, ref_data=None):
     """One block through bam.py / extract.py (the readable statement of the front end): (rows, reads kept)."""
     flank_size = opts.flank_size
+    want_kmers = opts.count_kmers != "none"
     results: list[dict] = []
     n_depth = 0
     prepared = []                     # (locus, ref data, [(segment, query_coords, ref_coords) ...])
@@ -758,7 +780,7 @@ def _call_block_python(block, bam: BamFile, ref: Fasta, opts: CallOptions, ctx, 
                 continue
             triples.append((sd.flank_left_seq_wc[-flank_size:], sd.tr_seq_wc, sd.flank_right_seq_wc[:flank_size]))
             names.append((seg.name, seg.strand, realigned, len(sd.tr_seq)))
-            if opts.consensus:   # the raw tract and the raw read bases in front of it (no wildcards), call_locus.py:1296-1299
+            if opts.consensus or want_kmers:   # the raw tract and the raw read bases in front of it (no wildcards), call_locus.py:1296-1299
                 raw.append((sd.tr_seq, seg.query_sequence[max(coords.left_flank_start, coords.left_flank_end - VCF_ANCHOR_SIZE):
                                                           coords.left_flank_end]))
         loci_reads.append((locus.motif, triples))
@@ -788,17 +810,19 @@ def _call_block_python(block, bam: BamFile, ref: Fasta, opts: CallOptions, ctx, 
         n_depth += len(row["reads"])
         results.append(row)
         rows_recs.append((row, kept if flt["locus_ok"][li] else []))
+    # (a read name that occurs twice at a locus keeps one record, as in the reference's read_dict: calls and k-mer counts are
+    # made from the records of the row)
+    recs_of = [list(row["reads"].values()) for row, _ in rows_recs]
+    pairs = al = None
+    if opts.consensus or want_kmers:     # (raw tract, raw anchor) of every record, in row order
+        by_name = [{meta[li][r - int(batch.read_off[li])][0]: raw[r] for r in kept} for li, (_, kept) in enumerate(rows_recs)]
+        pairs = [by_name[li][nm] for li, (row, _) in enumerate(rows_recs) for nm in row["reads"]]
     if opts.call_alleles:
-        # (a read name that occurs twice at a locus keeps one record, as in the reference's read_dict: the call is made
-        # from the records of the row)
-        recs_of = [list(row["reads"].values()) for row, _ in rows_recs]
         al = call_block_alleles([p[0] for p in prepared], np.array([len(x) for x in recs_of], np.int64),
                                 np.array([r["cn"] for x in recs_of for r in x], np.int32),
                                 np.array([r["w"] for x in recs_of for r in x], np.float64), opts, ctx, tm)
         cons = None
         if opts.consensus:
-            by_name = [{meta[li][r - int(batch.read_off[li])][0]: raw[r] for r in kept} for li, (_, kept) in enumerate(rows_recs)]
-            pairs = [by_name[li][nm] for li, (row, _) in enumerate(rows_recs) for nm in row["reads"]]
             text, t_start, t_len, a_start, a_len = [], [], [], [], []
             pos = 0
             for tr_raw, anchor in pairs:
@@ -810,6 +834,16 @@ def _call_block_python(block, bam: BamFile, ref: Fasta, opts: CallOptions, ctx, 
                                    seqs=np.frombuffer("".join(text).encode("ascii"), np.uint8))
         for li, (row, _) in enumerate(rows_recs):
             genotype_row(row, al, li, recs_of[li], cons)
+    if want_kmers and pairs:
+        t_len = np.array([len(tr_raw) for tr_raw, _ in pairs], np.int32)
+        t_start = np.concatenate(([0], np.cumsum(t_len[:-1]))).astype(np.int64)
+        locus_k = np.array([len(p[0].motif) for p in prepared], np.int32)
+        km = block_kmers(opts.count_kmers, al, t_start, t_len, np.repeat(locus_k, [len(x) for x in recs_of]), locus_k, opts, ctx, tm,
+                         seqs=np.frombuffer("".join(tr_raw for tr_raw, _ in pairs).encode("ascii"), np.uint8))
+        first = 0
+        for li, (row, _) in enumerate(rows_recs):
+            kmers_row(row, km, li, recs_of[li], first)
+            first += len(recs_of[li])
     return results, n_depth
 
 
@@ -899,7 +933,7 @@ def _block_device_stage(block, bam, ref: Fasta, opts: CallOptions, ctx, tm, ref_
           "minus": (bam.flag[kept_rec] & 16) != 0, "lens_all": bam.l_seq[rec].astype(np.int64), "cn": res["cn"], "sc": flt["sc"],
           "nfl": batch.nfl, "ntr": batch.ntr, "nfr": batch.nfr, "alt": alt}
     tm["names_s"] = tm.get("names_s", 0.0) + time.perf_counter() - t_a
-    if opts.call_alleles:
+    if opts.call_alleles or opts.count_kmers != "none":
         _block_genotype_stage(st, bam, coords, opts, ctx, tm)
     return st
 
@@ -923,15 +957,19 @@ def _kept_weights(st) -> np.ndarray:
 
 
 def _block_genotype_stage(st, bam, coords, opts: CallOptions, ctx, tm):
-    """Allele calls of the block's live loci over their kept reads and, with `consensus`, the allele sequences: a second
+    """Allele calls of the block's live loci over their kept reads and, with `consensus` or `count_kmers`, the allele sequences
+    and the k-mer counts: a second
     extraction of the kept items with the anchor as the flank and no wildcards leaves anchor | tract | ... of every kept read
     in one buffer (in HBM for a device reader: the bases are not uploaded), where the best-representative kernel reads the
     slices in place."""
     live, kept, read_locus = st["live"], st["kept"], st["read_locus"]
-    st["ws"] = _kept_weights(st)
-    n_kept = np.bincount(read_locus[kept], minlength=len(live))
-    al = st["al"] = call_block_alleles([l for l, _ in live], n_kept, st["cn"][kept], st["ws"], opts, ctx, tm)
-    if not opts.consensus or not kept.size:
+    want_kmers = opts.count_kmers != "none"
+    al = None
+    if opts.call_alleles:
+        st["ws"] = _kept_weights(st)
+        n_kept = np.bincount(read_locus[kept], minlength=len(live))
+        al = st["al"] = call_block_alleles([l for l, _ in live], n_kept, st["cn"][kept], st["ws"], opts, ctx, tm)
+    if not (opts.consensus or want_kmers) or not kept.size:
         return
     t_a = time.perf_counter()
     items = st["ok_items"][kept]
@@ -943,15 +981,24 @@ def _block_genotype_stage(st, bam, coords, opts: CallOptions, ctx, tm):
     tm["extract2_s"] = tm.get("extract2_s", 0.0) + time.perf_counter() - t_a
     start = ex["seq_off"][:-1]
     n_bytes = int(ex["seq_off"][-1])
-    if "d_seqs" in ex:
-        def fetch():
-            host = np.empty(max(n_bytes, 1), np.uint8)
-            _lib.check(_lib.load().strk_dbam_download_seqs(bam._h, n_bytes, host.ctypes.data))
-            return host[:n_bytes]
-        st["cons"] = block_consensus(al, start + ex["nfl"], ex["ntr"], start, ex["nfl"], opts, ctx, tm, d_seqs=ex["d_seqs"],
-                                     n_seq_bytes=n_bytes, fetch=fetch)
+    if "d_seqs" not in ex:
+        where = {"seqs": ex["seqs"]}
     else:
-        st["cons"] = block_consensus(al, start + ex["nfl"], ex["ntr"], start, ex["nfl"], opts, ctx, tm, seqs=ex["seqs"])
+        host_copy: list = []
+
+        def fetch():       # one download per block, shared by the consensus stage and the k-mer counts
+            if not host_copy:
+                host = np.empty(max(n_bytes, 1), np.uint8)
+                _lib.check(_lib.load().strk_dbam_download_seqs(bam._h, n_bytes, host.ctypes.data))
+                host_copy.append(host[:n_bytes])
+            return host_copy[0]
+        where = {"d_seqs": ex["d_seqs"], "n_seq_bytes": n_bytes, "fetch": fetch}
+    if opts.consensus:
+        st["cons"] = block_consensus(al, start + ex["nfl"], ex["ntr"], start, ex["nfl"], opts, ctx, tm, **where)
+    if want_kmers:
+        locus_k = np.array([len(l.motif) for l, _ in live], np.int32)
+        st["kmers"] = block_kmers(opts.count_kmers, al, start + ex["nfl"], ex["ntr"], locus_k[read_locus[kept]], locus_k, opts, ctx, tm,
+                                  **where)
 
 
 def _block_report_stage(st, opts: CallOptions, tm):
@@ -976,12 +1023,14 @@ def _block_report_stage(st, opts: CallOptions, tm):
         for k, r_ in enumerate(realn):
             if r_:
                 recs[k]["realn"] = True
-    al, cons = st.get("al"), st.get("cons")
+    al, cons, km = st.get("al"), st.get("cons"), st.get("kmers")
     for li, (locus, rd) in enumerate(live):
         a, b = first[li], first[li + 1]
         row = _locus_row(locus, rd, dict(zip(names[a:b], recs[a:b])), opts)
         if al is not None:
             genotype_row(row, al, li, recs[a:b], cons)
+        if km is not None:
+            kmers_row(row, km, li, recs[a:b], a)
         results.append(row)
     tm["report_s"] = tm.get("report_s", 0.0) + time.perf_counter() - t_a
     return results, int(len(kept))

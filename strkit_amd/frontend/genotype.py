@@ -11,8 +11,9 @@ import numpy as np
 
 from ..alleles import CALLED, TOO_FEW, AlleleParams, call_alleles_batch, call_data_from_batch, locus_seeds
 from ..consensus import METHOD_NAMES, best_representatives_packed
+from ..kmers import count_kmers_packed, dicts_of
 
-__all__ = ["n_alleles_of", "call_block_alleles", "peak_groups", "block_consensus", "genotype_row"]
+__all__ = ["n_alleles_of", "call_block_alleles", "peak_groups", "block_consensus", "genotype_row", "block_kmers", "kmers_row"]
 
 
 def n_alleles_of(n_alleles, contig: str) -> int:
@@ -119,6 +120,57 @@ def block_consensus(al: dict, tract_start, tract_len, anchor_start, anchor_len, 
         a.append(pair[1])
     tm["consensus_s"] = tm.get("consensus_s", 0.0) + time.perf_counter() - t_a
     return res
+
+
+def block_kmers(mode: str, al: dict | None, tract_start, tract_len, read_k, locus_k, opts, ctx, tm, seqs=None, d_seqs=None,
+                n_seq_bytes=None, fetch=None) -> dict:
+    """Motif-sized k-mer counts of a block (call_locus.py:1287,1526-1593,1635): ONE strk_count_kmers call whose groups are the
+    singleton groups of the kept reads (`mode` "read" / "both") followed by the groups of all reads of every called peak ("peak"
+    / "both"; the consensus stage's cut of long alleles does not apply).  tract_start / tract_len address every kept read's raw
+    tract inside one buffer (host `seqs`, or device `d_seqs` with `fetch()` returning its host copy, from which the strings are
+    cut); read_k is the window length per read, locus_k per locus (the catalog motif's length).  Returns
+    {"reads": [{kmer: count} per kept read] or None, "peaks": {locus: [{kmer: count} per peak]} or None}."""
+    t_a = time.perf_counter()
+    tract_start, tract_len = np.asarray(tract_start, np.int64), np.asarray(tract_len, np.int32)
+    read_k, locus_k = np.asarray(read_k, np.int32), np.asarray(locus_k, np.int32)
+    n_reads = tract_start.shape[0]
+    per_read, per_peak = mode in ("read", "both"), mode in ("peak", "both")
+    n_single = n_reads if per_read else 0
+    starts, lens, offs, ks = [], [], [np.zeros(1, np.int64)], []
+    if per_read:
+        starts.append(tract_start); lens.append(tract_len); ks.append(read_k)
+        offs.append(np.arange(1, n_reads + 1, dtype=np.int64))
+    g_locus = np.zeros(0, np.int64)
+    if per_peak:
+        g_locus, _g_peak, _t_reads, _t_off, reads, off = peak_groups(al, tract_len, opts)
+        starts.append(tract_start[reads]); lens.append(tract_len[reads]); ks.append(locus_k[g_locus])
+        offs.append(n_single + off[1:])
+    res = {"reads": [] if per_read else None, "peaks": {} if per_peak else None}
+    n_groups = n_single + g_locus.shape[0]
+    if n_groups == 0:
+        return res
+    ks = np.concatenate(ks)
+    out, st = count_kmers_packed(np.concatenate(offs).astype(np.int32), np.concatenate(starts), np.concatenate(lens), ks, seqs=seqs,
+                                 d_seqs=d_seqs, n_seq_bytes=n_seq_bytes, ctx=ctx, with_stats=True)
+    tm["kmers_device_s"] = tm.get("kmers_device_s", 0.0) + st["kernel_ms"] / 1e3
+    host = np.asarray(seqs, np.uint8) if seqs is not None else fetch()
+    dicts = dicts_of(out, ks, host.tobytes().decode("latin-1"))
+    if per_read:
+        res["reads"] = dicts[:n_single]
+    for g, d in zip(g_locus.tolist(), dicts[n_single:]):
+        res["peaks"].setdefault(g, []).append(d)
+    tm["kmers_s"] = tm.get("kmers_s", 0.0) + time.perf_counter() - t_a
+    return res
+
+
+def kmers_row(row: dict, km: dict, li: int, recs: list[dict], first: int) -> None:
+    """Adds the k-mer counts of locus `li` of the block to its row: `kmers` on every read record (recs = the block's records
+    first .. first + len(recs)), peaks.kmers on a called locus.  An uncalled locus and a nullified call have no peak counts."""
+    if km["reads"] is not None:
+        for k, r in enumerate(recs):
+            r["kmers"] = km["reads"][first + k]
+    if km["peaks"] is not None and li in km["peaks"] and row.get("peaks"):
+        row["peaks"]["kmers"] = km["peaks"][li]
 
 
 def genotype_row(row: dict, al: dict, li: int, recs: list[dict], cons: dict | None) -> None:
