@@ -4,6 +4,7 @@ strk_extract_reads): the per-read work of the front end in C++, as the reference
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import gzip
 import os
 import struct
@@ -687,3 +688,28 @@ def extract_reads(bam: NativeBam, rec_idx: np.ndarray, coords: np.ndarray, flank
         rc = call(seqs.ctypes.data, cap)
     _lib.check(rc)
     return {"status": status, "nfl": nfl, "ntr": ntr, "nfr": nfr, "seqs": seqs[:int(seq_off[-1])], "seq_off": seq_off}
+
+
+def extract_raw_slices(st, bam, coords, anchor_size: int, min_avg_phred: int, tm: dict):
+    """The raw tract and start anchor of every kept read of a block (`st`: block.BlockState): a second extraction of the kept
+    items with the anchor as the flank and no wildcards leaves anchor | tract | ... of every kept read in one buffer (in HBM for
+    a device reader: the bases are not uploaded), where the best-representative and k-mer kernels read the slices in place."""
+    t_a = time.perf_counter()
+    items = st.ok_items[st.kept]
+    alt2 = {k: st.alt[it] for k, it in enumerate(items.tolist()) if it in st.alt} if st.alt else None
+    ex = extract_reads(bam, st.rec[items], coords[items], anchor_size, min_avg_phred, -1, alt2)
+    # same records, same boundaries, same substitute alignments: both extractions cut the same read positions
+    assert not ex["status"].any() and np.array_equal(ex["ntr"], st.ntr[st.kept]), "the two extractions of a block disagree"
+    tm["extract2_s"] = tm.get("extract2_s", 0.0) + time.perf_counter() - t_a
+    start = ex["seq_off"][:-1]
+    n_bytes = int(ex["seq_off"][-1])
+    if "d_seqs" not in ex:
+        where = {"seqs": ex["seqs"]}
+    else:
+        @functools.cache
+        def fetch():       # one download per block, shared by the consensus stage and the k-mer counts
+            host = np.empty(max(n_bytes, 1), np.uint8)
+            _lib.check(_lib.load().strk_dbam_download_seqs(bam._h, n_bytes, host.ctypes.data))
+            return host[:n_bytes]
+        where = {"d_seqs": ex["d_seqs"], "n_seq_bytes": n_bytes, "fetch": fetch}
+    return start + ex["nfl"], ex["ntr"], start, ex["nfl"], where

@@ -1,0 +1,76 @@
+"""The options of a `call` run, written once: the dataclass, its checks, the constants of the reference's parameters, and
+the `parameters` block of the report."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+from .. import _lib
+from ..alleles import AlleleParams
+from ..batch import MIN_READ_ALIGN_SCORE
+from ..repeat_count_params import RepeatCountParams
+from .extract import MIN_AVG_PHRED
+
+MAX_READS = 250                 # params.max_reads default (strkit/call/params.py:21)
+DEFAULT_REF_MAX_ITERS = 250     # call_locus.py:71 default_ref_max_iters (100 there is only the "slow" warning level, :72)
+VCF_ANCHOR_SIZE = 5             # params.vcf_anchor_size default
+COUNT_KMERS_MODES = ("none", "peak", "read", "both")
+
+
+@dataclass
+class CallOptions:
+    """The knobs of `strkit call` this path honours (strkit/call/params.py:20-50) plus the two semantic switches of the
+    read-side counter that the reference's tree does not pin: tools/compare_strkit_json.py sweeps them."""
+    flank_size: int = 70
+    realign: bool = False
+    min_avg_phred: int = MIN_AVG_PHRED
+    max_reads: int = MAX_READS
+    respect_ref: bool = False
+    rc_params: RepeatCountParams | None = None
+    min_read_align_score: float = MIN_READ_ALIGN_SCORE
+    tie_rule: int = _lib.STRK_TIE_FIRST
+    end_flags: int = _lib.STRK_SG_ALL
+    narrowing: int = _lib.STRK_NARROW_NONE
+    # genotypes (off by default; not under torch.distributed yet).  `call_alleles`: a genotype per locus (call, intervals,
+    # peaks, a peak label `p` per read) from the GPU allele caller, with the locus seed alleles.locus_seed(seed, locus index).
+    # `consensus` (needs call_alleles): the sequence of every allele and of its start anchor as peaks.seqs /
+    # peaks.start_anchor_seqs.  `seed`: the run seed (an int once a run has started).  `n_alleles`: 1 or 2, for all contigs or
+    # per contig in a dict.  Then the caller's parameters and the two limits of strkit/call/params.py:67-68 for the tract
+    # groups of long alleles.
+    call_alleles: bool = False
+    consensus: bool = False
+    seed: int | None = None
+    n_alleles: int | dict = 2
+    allele_params: AlleleParams | None = None
+    large_consensus_length: int = 1200
+    max_n_large_consensus_reads: int = 20
+    # motif-sized k-mer counts (strkit/call/params.py count_kmers): "read" = every kept read record gets `kmers`, the counts of
+    # the motif-sized windows of its raw tract; "peak" (needs call_alleles) = a called locus gets peaks.kmers, one dict per
+    # peak over all reads labelled with it; "both"; "none"
+    count_kmers: str = "none"
+
+    def validate(self) -> None:
+        """What must hold before a block is called; needs no file and no device."""
+        if self.consensus and not self.call_alleles:
+            raise ValueError("consensus=True requires call_alleles=True: allele sequences are those of called alleles")
+        if self.count_kmers not in COUNT_KMERS_MODES:
+            raise ValueError(f"count_kmers must be one of {', '.join(COUNT_KMERS_MODES)}: got {self.count_kmers!r}")
+        if self.count_kmers in ("peak", "both") and not self.call_alleles:
+            raise ValueError(f"count_kmers={self.count_kmers!r} requires call_alleles=True: peak counts are those of called alleles")
+        if self.call_alleles and self.seed is None:
+            raise ValueError("call_alleles=True needs a run seed (CallOptions.seed); call_sample draws one when none is given")
+
+
+def report_parameters(opts: CallOptions, processes: int) -> dict:
+    """The `parameters` block of the report: the always-present keys, then those of every switch that is not at its default."""
+    ap = opts.allele_params or AlleleParams()
+    return {"flank_size": opts.flank_size, "realign": opts.realign, "min_avg_phred": opts.min_avg_phred,
+            "max_reads": opts.max_reads, "respect_ref": opts.respect_ref, "rc_method": "repalign",
+            "min_read_align_score": opts.min_read_align_score, "processes": processes,
+            **({"tie_rule": opts.tie_rule} if opts.tie_rule != _lib.STRK_TIE_FIRST else {}),
+            **({"end_flags": opts.end_flags} if opts.end_flags != _lib.STRK_SG_ALL else {}),
+            **({"narrowing": opts.narrowing} if opts.narrowing != _lib.STRK_NARROW_NONE else {}),
+            **({"call_alleles": True, "seed": opts.seed, "n_alleles": opts.n_alleles, "min_reads": ap.min_reads,
+                "min_allele_reads": ap.min_allele_reads, "num_bootstrap": ap.num_bootstrap} if opts.call_alleles else {}),
+            **({"consensus": True, "large_consensus_length": opts.large_consensus_length,
+                "max_n_large_consensus_reads": opts.max_n_large_consensus_reads} if opts.consensus else {}),
+            **({"count_kmers": opts.count_kmers} if opts.count_kmers != "none" else {})}

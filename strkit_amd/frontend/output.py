@@ -53,6 +53,21 @@ def read_weights(read_lengths_sorted: np.ndarray, tr_len_with_flank: np.ndarray,
         return (L + t - 2.0) / (L - t + 1.0)
 
 
+def block_read_weights(counts, item_locus, lens_all, read_locus, tlwf) -> np.ndarray:
+    """read_weights for the kept reads of all loci of a block at once.  `counts`: records fetched per locus; `item_locus`,
+    `lens_all`: locus and sequence length of every fetched record (ALL of them, sorted here inside the locus); `read_locus`,
+    `tlwf`: locus and flank + tract + flank of every kept read.  L = mean length of the records that could contain it."""
+    big = np.int64(1) << 40
+    order = np.lexsort((lens_all, item_locus))
+    key = item_locus[order] * big + lens_all[order]
+    csum = np.concatenate(([0], np.cumsum(lens_all[order])))
+    loc_end = np.cumsum(counts)                                   # end of each locus' run in `order`
+    part = np.searchsorted(key, read_locus * big + tlwf, side="left")
+    e_ = loc_end[read_locus]
+    L = (csum[e_] - csum[part]) / np.maximum(e_ - part, 1)
+    return (L + tlwf - 2.0) / (L - tlwf + 1.0)
+
+
 def allele_calling_inputs(row: dict) -> tuple[np.ndarray, np.ndarray]:
     """(read_cns int32, read_weights float64 summing to 1) of a result row, in read order — exactly what
     call_alleles_with_gmm derives from `read_dict` (call_locus.py:188-192) and passes as `repeats_fwd` /

@@ -175,3 +175,40 @@ def rescore_cigar(ref, read, cig, open_=7, ext=0):
             j += ln
         first = False
     return score, i, j
+
+
+# rows of the call driver's shape without a device: the two-rank gather test and the codec test share them
+def fake_rows(mine, ref):
+    """Stands in for the device path in the CPU test: rows of the real shape with made-up read records."""
+    from strkit_amd.frontend.call import CallOptions, _locus_dict, _locus_row
+    rows, errors = [], []
+    for blk in mine:
+        for l in blk:
+            if l.t_idx % 7 == 3:
+                rows.append(_locus_dict(l))                    # a skipped locus (no reference data)
+                continue
+            if l.t_idx % 11 == 5:
+                errors.append({"locus_index": l.t_idx, "error": "boom"})
+                continue
+            s_adj, e_adj = l.left_coord - (l.t_idx % 3), l.right_coord + (l.t_idx % 2)
+            rd = {"ref_cn": 5 + l.t_idx, "left_coord_adj": s_adj, "right_coord_adj": e_adj, "ref_seq": ref.fetch(l.contig, s_adj, e_adj),
+                  "ref_left_flank_seq": ref.fetch(l.contig, s_adj - 5, s_adj)}
+            n = l.t_idx % 4
+            reads = {f"read_{l.t_idx}_{k}" + "x" * (70 if k == 2 else 0): {"s": "+-"[k % 2], "cn": l.t_idx + k, "w": 1.0 / n,
+                                                                       "sc": None if k == 1 else 1.5 + 0.125 * k, "sl": 30 + k,
+                                                                       **({"realn": True} if k == 2 else {})} for k in range(n)}
+            rows.append(_locus_row(l, rd, reads, CallOptions()))
+    return rows, sum(len(r.get("reads") or {}) for r in rows), {"count_s": 0.1, "errors": errors}
+
+
+def gloo_blocks():
+    from strkit_amd.frontend.loci import Locus
+    return [[Locus(10 * k + i + 1, f"l{10 * k + i}", "chr1", 200 + 100 * (10 * k + i), 200 + 100 * (10 * k + i) + 6 * (1 + (k * 7 + i) % 9), "CAG")
+             for i in range(1 + k % 4)] for k in range(11)]
+
+
+class FakeRef:
+    seq = "ACGTTGCA" * 2000
+
+    def fetch(self, contig, a, b):
+        return self.seq[a:b]

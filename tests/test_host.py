@@ -6,7 +6,7 @@ import re
 import numpy as np
 import pytest
 
-from helpers import oracle_count
+from helpers import FakeRef, fake_rows, gloo_blocks, oracle_count
 from strkit_amd import _build, _lib
 from strkit_amd.repeat_count_params import RepeatCountParams, default_read_rc_params, get_reference_rc_params
 from strkit_amd.synth import CONFIGS, LocusBatch, make_config
@@ -196,53 +196,17 @@ def test_adjusted_score_and_read_filters_follow_the_callers_loop():
     assert (~got["locus_ok"]).any() and got["locus_ok"].any()
 
 
-def _fake_rows(mine, ref):
-    """Stands in for the device path in the CPU test: rows of the real shape with made-up read records."""
-    from strkit_amd.frontend.call import CallOptions, _locus_dict, _locus_row
-    rows, errors = [], []
-    for blk in mine:
-        for l in blk:
-            if l.t_idx % 7 == 3:
-                rows.append(_locus_dict(l))                    # a skipped locus (no reference data)
-                continue
-            if l.t_idx % 11 == 5:
-                errors.append({"locus_index": l.t_idx, "error": "boom"})
-                continue
-            s_adj, e_adj = l.left_coord - (l.t_idx % 3), l.right_coord + (l.t_idx % 2)
-            rd = {"ref_cn": 5 + l.t_idx, "left_coord_adj": s_adj, "right_coord_adj": e_adj, "ref_seq": ref.fetch(l.contig, s_adj, e_adj),
-                  "ref_left_flank_seq": ref.fetch(l.contig, s_adj - 5, s_adj)}
-            n = l.t_idx % 4
-            reads = {f"read_{l.t_idx}_{k}" + "x" * (70 if k == 2 else 0): {"s": "+-"[k % 2], "cn": l.t_idx + k, "w": 1.0 / n,
-                                                                       "sc": None if k == 1 else 1.5 + 0.125 * k, "sl": 30 + k,
-                                                                       **({"realn": True} if k == 3 else {})} for k in range(n)}
-            rows.append(_locus_row(l, rd, reads, CallOptions()))
-    return rows, sum(len(r.get("reads") or {}) for r in rows), {"count_s": 0.1, "errors": errors}
-
-
-def _gloo_blocks():
-    from strkit_amd.frontend.loci import Locus
-    return [[Locus(10 * k + i + 1, f"l{10 * k + i}", "chr1", 200 + 100 * (10 * k + i), 200 + 100 * (10 * k + i) + 6 * (1 + (k * 7 + i) % 9), "CAG")
-             for i in range(1 + k % 4)] for k in range(11)]
-
-
-class _Ref:
-    seq = "ACGTTGCA" * 2000
-
-    def fetch(self, contig, a, b):
-        return self.seq[a:b]
-
-
 def _gloo_call_worker(rank, world, port, q):
     import torch.distributed as dist
     from strkit_amd.frontend.call import call_blocks_sharded
     dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
-    ref = _Ref()
+    ref = FakeRef()
 
     def fake_call(mine):
-        rows, n, tm = _fake_rows(mine, ref)
+        rows, n, tm = fake_rows(mine, ref)
         return rows, n, {**tm, "count_s": 0.1 * (rank + 1)}
 
-    merged, n, tm = call_blocks_sharded(_gloo_blocks(), fake_call, ref)
+    merged, n, tm = call_blocks_sharded(gloo_blocks(), fake_call, ref)
     q.put((rank, merged, n, tm))
     dist.barrier()
     dist.destroy_process_group()
@@ -268,7 +232,7 @@ def test_call_driver_shards_locus_blocks_over_two_ranks():
     for p in procs:
         p.join(timeout=60)
         assert p.exitcode == 0
-    want_rows, want_n, want_tm = _fake_rows(_gloo_blocks(), _Ref())
+    want_rows, want_n, want_tm = fake_rows(gloo_blocks(), FakeRef())
     want_rows.sort(key=lambda r: r["locus_index"])
     assert any(len(nm) > 64 for r in want_rows for nm in (r.get("reads") or {}))       # a name longer than the default field
     for rank, merged, n, tm in got:
