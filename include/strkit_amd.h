@@ -304,7 +304,7 @@ int strk_call_alleles(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off /*[
 
 /* ---- best representative of a group of sequences ------------------------------------------------------------------
  * Stands where the reference calls strkit_rust_ext.consensus_seq (call_locus.py:1602-1613) for the methods `single` and
- * `best_rep`; partial-order alignment is not built.  A group is an ordered list of byte strings.  No string: index -1,
+ * `best_rep`; partial-order alignment is strk_consensus, below.  A group is an ordered list of byte strings.  No string: index -1,
  * STRK_CONS_NONE.  All strings byte-identical (a group of one included): index 0, STRK_CONS_SINGLE, distance sum 0.
  * Otherwise STRK_CONS_BEST_REP: the smallest i with minimal D(i) = sum over all j of the group of lev(s_i, s_j), lev the
  * unit-cost Levenshtein distance on raw bytes (case-sensitive; an empty string is legal).  Unpinned against STRkit, whose
@@ -324,6 +324,42 @@ int strk_best_representatives(strk_ctx* ctx, int32_t n_groups, const int32_t* gr
 int strk_best_representatives_dseqs(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const void* d_seqs,
                                     int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len, int32_t* out_index,
                                     int32_t* out_method, int64_t* out_dist_sum, strk_stats* stats);
+
+/* ---- allele sequence of a group: partial-order alignment where the reads differ --------------------------------------
+ * Stands where the reference calls strkit_rust_ext.consensus_seq with its default, POA (call_locus.py:1602-1613).  The
+ * method of a group is chosen in this order: no string: STRK_CONS_NONE; all strings byte-identical: STRK_CONS_SINGLE,
+ * string 0; the median length (element n / 2 of the ascending lengths) is greater than max_mdn_poa_length:
+ * STRK_CONS_BEST_REP, the rule above; the group exceeds a device limit (a string longer than 4 096 bytes, or a graph of more
+ * nodes than the node limit, 16 384): STRK_CONS_BEST_REP as well, counted in stats->n_fallback; otherwise STRK_CONS_POA: the
+ * heaviest path through the partial-order graph of the group's distinct strings (global alignment with linear gaps, match
+ * +5, mismatch -4, gap -8, ties by node number; DESIGN.md §12, the rule in full).  Raw bytes, case-sensitive, any byte value.
+ * Unpinned against STRkit, whose POA is not in its tree.
+ *
+ * Groups and sequences as for strk_best_representatives, and max_mdn_poa_length >= 0.  out_index [n_groups] is the index
+ * inside the group for SINGLE / BEST_REP and -1 for POA / NONE; out_method [n_groups]; the sequence of group g, whatever its
+ * method, is the bytes out_seq_off[g] .. out_seq_off[g+1] of out_seqs.  Returns the number of bytes B of all sequences, or a
+ * negative STRK_E_* code.  out_seq_off [n_groups + 1] is always written, out_seqs [cap] only if B <= cap: cap = 0 with NULL is
+ * a size query.  All buffers are host buffers; every input is checked before the first launch.  stats (optional) receives
+ * kernel_ms (device time of all kernels), dp_cells (graph nodes times string bytes, over all aligned strings),
+ * n_fallback, n_dp_launches and n_sub_batches = the launches of the POA kernel. */
+#define STRK_CONS_POA 3
+int64_t strk_consensus(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off /*[n_groups+1]*/, const uint8_t* seqs,
+                       int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len, int32_t max_mdn_poa_length,
+                       int64_t cap, int32_t* out_index, int32_t* out_method, int64_t* out_seq_off /*[n_groups+1]*/,
+                       uint8_t* out_seqs /*[cap]*/, strk_stats* stats);
+/* The same with the bases already in memory of the context's device; everything else on the host. */
+int64_t strk_consensus_dseqs(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const void* d_seqs, int64_t n_seq_bytes,
+                             const int64_t* seq_start, const int32_t* seq_len, int32_t max_mdn_poa_length, int64_t cap,
+                             int32_t* out_index, int32_t* out_method, int64_t* out_seq_off, uint8_t* out_seqs,
+                             strk_stats* stats);
+/* The general form: exactly one of seqs (host) and d_seqs (device) is not NULL; node_limit is the node limit (1 .. 16 384;
+ * <= 0: the default, 16 384), which is part of the rule; workspace_bytes bounds the device workspace of one launch of the
+ * POA kernel (<= 0: the default, 4 GiB; a single group that needs more runs alone), which is not: the result does not depend
+ * on it. */
+int64_t strk_consensus_ws(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const uint8_t* seqs, const void* d_seqs,
+                          int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len, int32_t max_mdn_poa_length,
+                          int64_t cap, int32_t* out_index, int32_t* out_method, int64_t* out_seq_off, uint8_t* out_seqs,
+                          int32_t node_limit, int64_t workspace_bytes, strk_stats* stats);
 
 /* ---- distinct windows (k-mers) of a group of sequences, counted ----------------------------------------------------
  * Stands where the reference counts motif-sized k-mers per read (call_locus.py:1287) and per allele (:1526-1593, :1635).

@@ -1,6 +1,7 @@
 """`python -m strkit_amd call <alignments.bam> --ref ref.fa --loci catalog.bed [--json out.json] [--realign]` — the
 subset of `strkit call` (strkit/entry.py:20-342) that the device backend covers: per-read copy numbers per locus and, with
-`--call-alleles`, a genotype per locus (`--consensus`: with the sequence of every allele, which a VCF with alleles needs);
+`--call-alleles`, a genotype per locus (`--consensus`: with the sequence of every allele, which a VCF with alleles needs;
+`--consensus-method poa`: by partial-order alignment where the reads of an allele differ);
 `--count-kmers`: the motif-sized k-mers of every tract, per read and per allele."""
 from __future__ import annotations
 
@@ -30,7 +31,12 @@ def build_parser() -> argparse.ArgumentParser:
     c.add_argument("--respect-ref", action="store_true")
     c.add_argument("--call-alleles", action="store_true", help="call a genotype per locus (GPU allele caller)")
     c.add_argument("--consensus", action="store_true",
-                   help="with --call-alleles: report the sequence of every allele (single / best_rep; no partial-order alignment)")
+                   help="with --call-alleles: report the sequence of every allele (single / best_rep, or poa with --consensus-method poa)")
+    c.add_argument("--consensus-method", choices=("best_rep", "poa"), default="best_rep",
+                   help="the sequence of an allele whose reads differ: its best representative read, or the consensus of its "
+                        "reads by partial-order alignment (GPU)")
+    c.add_argument("--max-mdn-poa-length", type=int, default=5000,
+                   help="--consensus-method poa: an allele whose median read length is above this keeps its best representative")
     c.add_argument("--n-alleles", type=int, choices=(1, 2), default=2, help="alleles per locus, all contigs")
     c.add_argument("--count-kmers", "-k", nargs="?", type=str, default="none", const="peak", choices=("none", "peak", "read", "both"),
                    help="count the motif-sized k-mers of every read's repeat tract (GPU): per read, summed per allele (peak; the "
@@ -51,6 +57,8 @@ def main(argv=None) -> int:
     a = ap.parse_args(argv)
     if a.consensus and not a.call_alleles:
         ap.error("--consensus needs --call-alleles")
+    if a.max_mdn_poa_length < 0:
+        ap.error("--max-mdn-poa-length must be >= 0")
     if a.count_kmers in ("peak", "both") and not a.call_alleles:
         ap.error(f"--count-kmers {a.count_kmers} needs --call-alleles")
     import os
@@ -69,7 +77,7 @@ def main(argv=None) -> int:
                       min_avg_phred=a.min_avg_phred, max_reads=a.max_reads, respect_ref=a.respect_ref,
                       sample_id=a.sample_id, processes=a.processes, rc_params=rc,
                       min_read_align_score=a.min_read_align_score, front_end=a.front_end, span_bytes=a.span_mb << 20,
-                      count_kmers=a.count_kmers,
+                      count_kmers=a.count_kmers, consensus_method=a.consensus_method, max_mdn_poa_length=a.max_mdn_poa_length,
                       **(dict(call_alleles=True, consensus=a.consensus or bool(a.vcf), seed=a.seed, n_alleles=a.n_alleles)
                          if a.call_alleles else {}))
     if world > 1:

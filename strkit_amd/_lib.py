@@ -66,7 +66,8 @@ EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk
            "strk_dbam_open", "strk_dbam_close", "strk_dbam_release_cache", "strk_dbam_inflate", "strk_dbam_inflate_file", "strk_dbam_inflate_file_range", "strk_dbam_file_ms", "strk_dbam_download", "strk_dbam_data", "strk_bgzf_inflate_sw",
            "strk_dbam_download_seqs", "strk_dbam_kernel_ms", "strk_dbam_voffsets", "strk_dbam_scan", "strk_dbam_extract", "strk_dbam_names", "strk_count_loci_dseqs", "strk_read_coords_both", "strk_call_alleles",
            "strk_best_representatives", "strk_best_representatives_dseqs",
-           "strk_count_kmers", "strk_count_kmers_dseqs", "strk_count_kmers_ws")
+           "strk_count_kmers", "strk_count_kmers_dseqs", "strk_count_kmers_ws",
+           "strk_consensus", "strk_consensus_dseqs", "strk_consensus_ws")
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -202,6 +203,13 @@ def load(build: bool = True):
         L.strk_count_kmers_ws.restype = C.c_int64
         L.strk_count_kmers_ws.argtypes = ([C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int64]
                                           + [C.c_void_p] * 3 + [C.c_int64, C.POINTER(StrkStats)])
+        for f in (L.strk_consensus, L.strk_consensus_dseqs):
+            f.restype = C.c_int64
+            f.argtypes = ([C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 2 + [C.c_int32, C.c_int64]
+                          + [C.c_void_p] * 4 + [C.POINTER(StrkStats)])
+        L.strk_consensus_ws.restype = C.c_int64
+        L.strk_consensus_ws.argtypes = ([C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 2
+                                        + [C.c_int32, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32, C.c_int64, C.POINTER(StrkStats)])
         L.strk_device_mem.restype = C.c_int
         L.strk_device_mem.argtypes = [C.c_int, _i64p, _i64p]
         L.strk_realign_i16_flags.restype = C.c_int

@@ -1,9 +1,11 @@
-"""Allele sequences on the GPU: the best representative of every group of reads (strk_best_representatives, kernel k_best_rep).
+"""Allele sequences on the GPU: the best representative of every group of reads (strk_best_representatives, kernel
+k_best_rep) and the consensus by partial-order alignment (strk_consensus, kernel k_poa).
 
-Stands where the reference calls strkit_rust_ext.consensus_seq (strkit/call/call_locus.py:1602-1613).  Two of its three
-methods exist here: `single` (all reads of the allele are identical) and `best_rep` (the read with the smallest summed
-Levenshtein distance to all reads of the allele, the first such read on a tie).  Partial-order alignment (`poa`) is not
-built: every allele whose reads differ is reported as `best_rep`.  The definition is ours and unpinned
+Stands where the reference calls strkit_rust_ext.consensus_seq (strkit/call/call_locus.py:1602-1613).  Its three methods:
+`single` (all reads of the allele are identical), `best_rep` (the read with the smallest summed Levenshtein distance to all
+reads of the allele, the first such read on a tie) and `poa` (the heaviest path through the partial-order graph of the
+reads).  best_representatives* never answer `poa`; consensus* do, for every group whose reads differ, whose median length
+is at most max_mdn_poa_length and which fits the device limits.  The definitions are ours and unpinned
 against STRkit, whose consensus code is not in its tree.  There is no CPU path.
 """
 from __future__ import annotations
@@ -15,7 +17,10 @@ import numpy as np
 from . import _lib
 
 NONE, SINGLE, BEST_REP = 0, 1, 2
-METHOD_NAMES = ("none", "single", "best_rep")
+POA = 3
+METHOD_NAMES = ("none", "single", "best_rep", "poa")
+MAX_POA_LEN = 4096       # a group with a longer string is not taken by POA
+MAX_POA_NODES = 16384    # nor one whose graph grows beyond this
 MAX_GROUP = 250
 MAX_LEN = 65535
 
@@ -86,9 +91,94 @@ def best_representatives(groups, ctx=None) -> list[tuple[str | None, str]]:
     return res
 
 
-def consensus_seq(seqs, logger_=None, max_mdn_poa_length: int = 0, poa: bool = False, ctx=None):
+def consensus_packed(group_off, seq_start, seq_len, seqs=None, d_seqs=None, n_seq_bytes: int | None = None,
+                     max_mdn_poa_length: int = 5000, ctx=None, with_stats: bool = False, node_limit: int = 0,
+                     workspace_bytes: int = 0, cap: int | None = None):
+    """One strk_consensus call for many groups, addressed as for best_representatives_packed.  Returns a dict of numpy arrays:
+    index [G] (inside the group for SINGLE / BEST_REP, -1 for POA / NONE), method [G], seq_off [G + 1] and seqs (uint8: group
+    g's sequence is seqs[seq_off[g]:seq_off[g+1]], whatever its method).  node_limit / workspace_bytes: the general form
+    (strk_consensus_ws), 0 = the library's defaults.  cap: the size of the byte buffer offered; None asks for the size first.
+    With a cap that is too small `seqs` is None and seq_off still tells the size."""
+    ctx = ctx or _lib.default_context()
+    group_off = np.ascontiguousarray(group_off, dtype=np.int32)
+    seq_start = np.ascontiguousarray(seq_start, dtype=np.int64)
+    seq_len = np.ascontiguousarray(seq_len, dtype=np.int32)
+    n_groups = group_off.shape[0] - 1
+    if n_groups < 0 or seq_start.shape != seq_len.shape or seq_start.ndim != 1:
+        raise ValueError("group_off needs at least one entry, and seq_start and seq_len one entry per sequence")
+    if n_groups and int(group_off[-1]) != seq_start.shape[0]:
+        raise ValueError("group_off must span seq_start / seq_len")
+    if (seqs is None) == (d_seqs is None):
+        raise ValueError("exactly one of seqs (host) and d_seqs (device) must be given")
+    if d_seqs is None:
+        buf = np.frombuffer(seqs, dtype=np.uint8) if isinstance(seqs, (bytes, bytearray, memoryview)) else \
+            np.ascontiguousarray(seqs, dtype=np.uint8)
+        n = buf.shape[0] if n_seq_bytes is None else int(n_seq_bytes)
+        if n > buf.shape[0]:
+            raise ValueError("n_seq_bytes exceeds the buffer")
+        h_ptr, d_ptr = _ptr(buf), None
+    else:
+        if n_seq_bytes is None:
+            raise ValueError("d_seqs needs n_seq_bytes")
+        n, h_ptr, d_ptr = int(n_seq_bytes), None, C.c_void_p(int(d_seqs))
+    out = dict(index=np.empty(n_groups, np.int32), method=np.empty(n_groups, np.int32),
+               seq_off=np.zeros(n_groups + 1, np.int64), seqs=None)
+    st = _lib.StrkStats()
+    L = _lib.load()
+
+    def call(cap_, arr):
+        rc = L.strk_consensus_ws(ctx.handle, n_groups, _ptr(group_off), h_ptr, d_ptr, n, _ptr(seq_start), _ptr(seq_len),
+                                 int(max_mdn_poa_length), int(cap_), _ptr(out["index"]), _ptr(out["method"]), _ptr(out["seq_off"]),
+                                 _ptr(arr) if arr is not None else None, int(node_limit), int(workspace_bytes), C.byref(st))
+        if rc < 0:
+            _lib.check(int(rc))
+        return int(rc)
+
+    if cap is None:
+        # a consensus has at most as many bytes as its graph has nodes, and the graph at most as many as the group has bytes
+        arr = np.empty(max(int(seq_len.sum(dtype=np.int64)), 1), np.uint8)
+        total = call(arr.shape[0], arr)
+        out["seqs"] = arr[:total]
+    else:
+        arr = np.empty(max(int(cap), 1), np.uint8) if cap > 0 else None
+        total = call(cap, arr)
+        out["seqs"] = arr[:total] if arr is not None and total <= cap else (np.empty(0, np.uint8) if total == 0 else None)
+    if with_stats:
+        return out, st.as_dict()
+    return out
+
+
+def _pack(groups):
+    flat = [[_as_bytes(s) for s in g] for g in groups]
+    lens = np.fromiter((len(s) for g in flat for s in g), dtype=np.int32, count=sum(len(g) for g in flat))
+    starts = np.zeros(lens.shape[0], np.int64)
+    if lens.shape[0]:
+        np.cumsum(lens[:-1], out=starts[1:])
+    group_off = np.zeros(len(flat) + 1, np.int32)
+    np.cumsum([len(g) for g in flat], out=group_off[1:])
+    return group_off, starts, lens, np.frombuffer(b"".join(s for g in flat for s in g), dtype=np.uint8)
+
+
+def consensus(groups, max_mdn_poa_length: int = 5000, ctx=None) -> list[tuple[str | None, str]]:
+    """(sequence, method) per group, method in "single" | "poa" | "best_rep"; (None, "none") for an empty group.  Sequences come
+    back as str (latin-1, so that every byte value survives)."""
+    group_off, starts, lens, buf = _pack(groups)
+    out = consensus_packed(group_off, starts, lens, seqs=buf, max_mdn_poa_length=max_mdn_poa_length, ctx=ctx)
+    text = out["seqs"].tobytes()
+    off = out["seq_off"].tolist()
+    return [(None, "none") if meth == NONE else (text[off[g]:off[g + 1]].decode("latin-1"), METHOD_NAMES[meth])
+            for g, meth in enumerate(out["method"].tolist())]
+
+
+def consensus_seq(seqs, logger_=None, max_mdn_poa_length: int = 0, poa: bool = False, ctx=None, method: str = "best_rep"):
     """The reference's call shape (call_locus.py:1610) for one group: (sequence, method) or None for no reads.
-    `logger_`, `max_mdn_poa_length` and `poa` are accepted and ignored: partial-order alignment is not built, an allele
-    whose reads differ is always its best representative."""
-    seq, method = best_representatives([list(seqs)], ctx=ctx)[0]
-    return None if seq is None else (seq, method)
+    `logger_`, `max_mdn_poa_length` and `poa` are accepted and ignored, as they were before partial-order alignment was built:
+    with the default method="best_rep" an allele whose reads differ is its best representative.  method="poa" takes the
+    consensus by partial-order alignment (consensus(), with the reference's default max_mdn_poa_length of 5000)."""
+    if method == "poa":
+        seq, meth = consensus([list(seqs)], ctx=ctx)[0]
+    elif method == "best_rep":
+        seq, meth = best_representatives([list(seqs)], ctx=ctx)[0]
+    else:
+        raise ValueError(f"method must be 'best_rep' or 'poa': got {method!r}")
+    return None if seq is None else (seq, meth)

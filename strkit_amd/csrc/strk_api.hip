@@ -43,6 +43,7 @@
 #include "strk_alleles.h"
 #include "strk_consensus.h"
 #include "strk_kmers.h"
+#include "strk_poa.h"
 
 namespace {
 
@@ -121,6 +122,9 @@ struct strk_ctx {
     // distinct windows (strk_count_kmers), likewise
     DevBuf km_off, km_start, km_len, km_k, km_seqs, km_cnt, km_eoff, km_list, km_slist, km_wsoff, km_ws, km_out;
     Stream km_stream;
+    // allele sequences by partial-order alignment (strk_consensus), likewise
+    DevBuf po_off, po_start, po_len, po_seqs, po_res, po_pool, po_poolof, po_list, po_ws, po_out, po_outoff;
+    Stream po_stream;
     HostCounters h_counters;        // pinned: counters + cells + scratch_used
     // a chain of events along one call: start | after k_hash + k_plan | after k_dp_band | after k_dp_band_wide | after the
     // first k_replay pass | after k_dp_all / k_dp_ref | after k_dp_long | after k_dp_generic | end (after k_replay and the
@@ -762,6 +766,7 @@ int score_table_impl(strk_ctx* ctx, const strk_batch* batch, const int32_t* lo, 
 #include "strk_host_alleles.inc"
 #include "strk_host_consensus.inc"
 #include "strk_host_kmers.inc"
+#include "strk_host_poa.inc"
 
 }  // namespace
 
@@ -1050,6 +1055,44 @@ int64_t strk_count_kmers_dseqs(strk_ctx* ctx, int32_t n_groups, const int32_t* g
     if (!d_seqs) return fail(STRK_E_INVALID, "strk_count_kmers_dseqs: d_seqs is NULL");
     return strk_count_kmers_ws(ctx, n_groups, group_off, nullptr, d_seqs, n_seq_bytes, seq_start, seq_len, k, cap, out_entry_off,
                                out_pos, out_count, 0, stats);
+}
+
+int64_t strk_consensus_ws(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const uint8_t* seqs, const void* d_seqs,
+                          int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len, int32_t max_mdn_poa_length,
+                          int64_t cap, int32_t* out_index, int32_t* out_method, int64_t* out_seq_off, uint8_t* out_seqs,
+                          int32_t node_limit, int64_t workspace_bytes, strk_stats* stats) {
+    const char* fn = d_seqs ? "strk_consensus_dseqs" : "strk_consensus";
+    if (!ctx) return fail(STRK_E_INVALID, "%s: ctx is NULL", fn);
+    if (ctx->pending) return fail(STRK_E_INVALID, "%s: a submitted call is pending on this context", fn);
+    if (seqs && d_seqs) return fail(STRK_E_INVALID, "strk_consensus_ws: both seqs and d_seqs are given");
+    static_assert(STRK_CONS_POA == kConsPoa, "include/strkit_amd.h <-> strk_poa.h");
+    if (d_seqs) {
+        (void)hipSetDevice(ctx->device);
+        hipPointerAttribute_t attr;
+        if (hipPointerGetAttributes(&attr, d_seqs) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
+            (void)hipGetLastError();
+            return fail(STRK_E_INVALID, "%s: d_seqs is not device memory of device %d (the context's)", fn, ctx->device);
+        }
+    }
+    return consensus_impl(ctx, fn, n_groups, group_off, seqs, static_cast<const uint8_t*>(d_seqs), n_seq_bytes, seq_start, seq_len,
+                          max_mdn_poa_length, cap, out_index, out_method, out_seq_off, out_seqs, node_limit, workspace_bytes, stats);
+}
+
+int64_t strk_consensus(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const uint8_t* seqs, int64_t n_seq_bytes,
+                       const int64_t* seq_start, const int32_t* seq_len, int32_t max_mdn_poa_length, int64_t cap,
+                       int32_t* out_index, int32_t* out_method, int64_t* out_seq_off, uint8_t* out_seqs, strk_stats* stats) {
+    return strk_consensus_ws(ctx, n_groups, group_off, seqs, nullptr, n_seq_bytes, seq_start, seq_len, max_mdn_poa_length, cap,
+                             out_index, out_method, out_seq_off, out_seqs, 0, 0, stats);
+}
+
+int64_t strk_consensus_dseqs(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const void* d_seqs, int64_t n_seq_bytes,
+                             const int64_t* seq_start, const int32_t* seq_len, int32_t max_mdn_poa_length, int64_t cap,
+                             int32_t* out_index, int32_t* out_method, int64_t* out_seq_off, uint8_t* out_seqs,
+                             strk_stats* stats) {
+    if (!ctx) return fail(STRK_E_INVALID, "strk_consensus_dseqs: ctx is NULL");
+    if (!d_seqs) return fail(STRK_E_INVALID, "strk_consensus_dseqs: d_seqs is NULL");
+    return strk_consensus_ws(ctx, n_groups, group_off, nullptr, d_seqs, n_seq_bytes, seq_start, seq_len, max_mdn_poa_length, cap,
+                             out_index, out_method, out_seq_off, out_seqs, 0, 0, stats);
 }
 
 int strk_ref_repeat_count_batch(strk_ctx* ctx, int32_t n_loci, const int32_t* start_count, const uint8_t* seqs,

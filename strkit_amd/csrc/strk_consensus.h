@@ -1,7 +1,7 @@
 // strk_consensus.h — best representative of every group of sequences on gfx950 (strk_best_representatives).
 //
 // Stands where the reference calls strkit_rust_ext.consensus_seq (strkit/call/call_locus.py:1602-1613) for the methods
-// `single` and `best_rep`; partial-order alignment is not built.  The definition (the CPU restatement
+// `single` and `best_rep`; partial-order alignment is strk_poa.h.  The definition (the CPU restatement
 // that the tests compare against is tests/consensus_restatement.py): all strings of a group byte-identical -> string 0,
 // `single`; otherwise the smallest i with minimal D(i) = sum_j lev(s_i, s_j), unit-cost Levenshtein on raw bytes.
 //

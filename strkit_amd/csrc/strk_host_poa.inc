@@ -1,0 +1,252 @@
+// Host side of strk_consensus / strk_consensus_dseqs / strk_consensus_ws: input checks, the method of every group, launches
+// of k_poa cut at a group count and at a workspace bound, the best-representative path for the rest, the bytes' gather.
+// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, strk_ctx, best_rep_impl and
+// kmer_timed defined there); not a stand-alone header.
+// ---------------------------------------------------------------------------------------------
+// Allele sequences by partial-order alignment: strk_consensus
+// ---------------------------------------------------------------------------------------------
+constexpr int64_t kPoaWsBytes = (int64_t)4 << 30;   // workspace of one launch of k_poa (a group beyond it runs alone)
+constexpr int kPoaPieceGroups = 8192;               // groups of one launch
+
+// `d_seqs` != nullptr: the bases are in device memory already and `seqs` is not read.  node_limit <= 0: kPoaMaxNodes;
+// ws_bytes <= 0: kPoaWsBytes.
+int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int32_t* group_off, const uint8_t* seqs,
+                       const uint8_t* d_seqs, int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len,
+                       int32_t max_mdn, int64_t cap, int32_t* out_index, int32_t* out_method, int64_t* out_seq_off,
+                       uint8_t* out_seqs, int32_t node_limit, int64_t ws_bytes, strk_stats* stats) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    if (n_groups < 0) return fail(STRK_E_INVALID, "%s: n_groups < 0", fn);
+    if (n_seq_bytes < 0) return fail(STRK_E_INVALID, "%s: n_seq_bytes < 0", fn);
+    if (max_mdn < 0) return fail(STRK_E_INVALID, "%s: max_mdn_poa_length < 0", fn);
+    if (cap < 0) return fail(STRK_E_INVALID, "%s: cap < 0", fn);
+    if (node_limit > kPoaMaxNodes) return fail(STRK_E_INVALID, "%s: node_limit %d (at most %d)", fn, node_limit, kPoaMaxNodes);
+    if (!out_seq_off) return fail(STRK_E_INVALID, "%s: out_seq_off is NULL", fn);
+    if (cap > 0 && !out_seqs) return fail(STRK_E_INVALID, "%s: cap > 0 with out_seqs NULL", fn);
+    if (n_groups > 0 && (!group_off || !out_index || !out_method)) return fail(STRK_E_INVALID, "%s: NULL argument", fn);
+    if (n_groups > 0 && group_off[0] != 0) return fail(STRK_E_INVALID, "%s: group_off[0] must be 0", fn);
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const int64_t n = (int64_t)group_off[g + 1] - group_off[g];
+        if (n < 0) return fail(STRK_E_INVALID, "%s: group %d: group_off is decreasing", fn, g);
+        if (n > kConsMaxGroup) return fail(STRK_E_INVALID, "%s: group %d: %lld sequences (at most %d)", fn, g, (long long)n, kConsMaxGroup);
+    }
+    const int32_t n_seqs = n_groups > 0 ? group_off[n_groups] : 0;
+    if (n_seqs > 0 && (!seq_start || !seq_len)) return fail(STRK_E_INVALID, "%s: NULL argument", fn);
+    int64_t total_len = 0;
+    for (int32_t i = 0; i < n_seqs; ++i) {
+        if (seq_len[i] < 0 || seq_len[i] > kConsMaxLen)
+            return fail(STRK_E_INVALID, "%s: sequence %d: length %d is outside 0..%d", fn, i, seq_len[i], kConsMaxLen);
+        if (seq_start[i] < 0 || seq_start[i] > n_seq_bytes - seq_len[i])
+            return fail(STRK_E_INVALID, "%s: sequence %d: bytes %lld..%lld lie outside the %lld given", fn, i,
+                        (long long)seq_start[i], (long long)(seq_start[i] + seq_len[i]), (long long)n_seq_bytes);
+        total_len += seq_len[i];
+    }
+    if (total_len > 0 && !seqs && !d_seqs) return fail(STRK_E_INVALID, "%s: seqs is NULL", fn);
+    static_assert(kPoaMaxGroup == kConsMaxGroup, "strk_poa.h <-> strk_consensus.h");
+    out_seq_off[0] = 0;
+    if (n_groups == 0) return 0;
+    if (node_limit <= 0) node_limit = kPoaMaxNodes;
+    if (ws_bytes <= 0) ws_bytes = kPoaWsBytes;
+    const int64_t ws_ints = std::max<int64_t>(1, ws_bytes / 4);
+
+    // The method of every group as far as lengths decide it.  route: 0 = k_poa, 1 = best representative by the median rule
+    // (or no string at all), 2 = best representative because a string is beyond the kernel's rows.
+    const size_t ng = (size_t)n_groups;
+    std::vector<uint8_t> route(ng, 0);
+    std::vector<int32_t> poa_list;
+    std::vector<int32_t> sorted_len;
+    struct Piece { int64_t ints; int32_t node_cap, edge_cap, row_len; };
+    std::vector<Piece> need;          // per entry of poa_list
+    std::vector<int64_t> pool_of(ng, -1);
+    int64_t pool_bytes = 0;
+    for (int32_t g = 0; g < n_groups; ++g) {
+        const int32_t a = group_off[g], n = group_off[g + 1] - a;
+        if (n == 0) {
+            route[(size_t)g] = 1;
+            continue;
+        }
+        sorted_len.assign(seq_len + a, seq_len + a + n);
+        std::nth_element(sorted_len.begin(), sorted_len.begin() + n / 2, sorted_len.end());
+        const int32_t mdn = sorted_len[(size_t)(n / 2)];
+        int64_t sum = 0;
+        int32_t longest = 0;
+        for (int32_t i = a; i < a + n; ++i) {
+            sum += seq_len[i];
+            longest = std::max(longest, seq_len[i]);
+        }
+        if (mdn > max_mdn) route[(size_t)g] = 1;
+        else if (longest > kPoaMaxLen) route[(size_t)g] = 2;
+        else {
+            Piece p;
+            p.node_cap = (int32_t)std::max<int64_t>(1, std::min<int64_t>(sum, node_limit));
+            p.edge_cap = (int32_t)std::max<int64_t>(1, sum);
+            p.row_len = longest + 1;
+            p.ints = (int64_t)p.node_cap * (kPoaNodeArrays + p.row_len) + (int64_t)p.edge_cap * kPoaEdgeArrays + p.row_len;
+            p.ints = (p.ints + 63) & ~(int64_t)63;
+            poa_list.push_back(g);
+            need.push_back(p);
+            pool_of[(size_t)g] = pool_bytes;
+            pool_bytes += p.node_cap;
+        }
+    }
+
+    HIP_TRY(hipSetDevice(c->device));
+    if (!c->po_stream) HIP_TRY(hipStreamCreateWithFlags(&c->po_stream.h, hipStreamNonBlocking));
+    hipStream_t st = c->po_stream;
+    int rc;
+    if ((rc = c->po_off.ensure((ng + 1) * 4))) return rc;
+    if ((rc = c->po_start.ensure(std::max<size_t>(n_seqs, 1) * 8))) return rc;
+    if ((rc = c->po_len.ensure(std::max<size_t>(n_seqs, 1) * 4))) return rc;
+    if ((rc = c->po_res.ensure(ng * 16 + 8))) return rc;              // cells | index | method | len | state
+    if ((rc = c->po_pool.ensure(std::max<size_t>((size_t)pool_bytes, 256)))) return rc;
+    if ((rc = c->po_poolof.ensure(ng * 8))) return rc;
+    if (!d_seqs) {
+        if ((rc = c->po_seqs.ensure(std::max<size_t>((size_t)n_seq_bytes, 256)))) return rc;
+        if (n_seq_bytes > 0 && total_len > 0) HIP_TRY(hipMemcpyAsync(c->po_seqs.p, seqs, (size_t)n_seq_bytes, hipMemcpyHostToDevice, st));
+    }
+    const uint8_t* dev_seqs = d_seqs ? d_seqs : c->po_seqs.as<uint8_t>();
+    HIP_TRY(hipMemcpyAsync(c->po_off.p, group_off, (ng + 1) * 4, hipMemcpyHostToDevice, st));
+    if (n_seqs > 0) {
+        HIP_TRY(hipMemcpyAsync(c->po_start.p, seq_start, (size_t)n_seqs * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(c->po_len.p, seq_len, (size_t)n_seqs * 4, hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(hipMemcpyAsync(c->po_poolof.p, pool_of.data(), ng * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(c->po_res.p, 0, ng * 16 + 8, st));
+    unsigned long long* d_cells = c->po_res.as<unsigned long long>();
+    int32_t* d_index = reinterpret_cast<int32_t*>(d_cells + 1);
+    int32_t* d_method = d_index + n_groups;
+    int32_t* d_len = d_method + n_groups;
+    int32_t* d_state = d_len + n_groups;
+
+    // k_poa over its groups, in pieces
+    std::vector<int64_t> ws_off, pool_off;
+    std::vector<int32_t> caps;
+    for (size_t p0 = 0; p0 < poa_list.size();) {
+        ws_off.clear();
+        pool_off.clear();
+        int64_t used = 0;
+        size_t p1 = p0;
+        while (p1 < poa_list.size() && p1 - p0 < (size_t)kPoaPieceGroups) {
+            if (p1 > p0 && used + need[p1].ints > ws_ints) break;
+            ws_off.push_back(used);
+            pool_off.push_back(pool_of[(size_t)poa_list[p1]]);
+            used += need[p1].ints;
+            ++p1;
+        }
+        const int32_t n_piece = (int32_t)(p1 - p0);
+        caps.resize((size_t)n_piece * 3);
+        for (int32_t k = 0; k < n_piece; ++k) {
+            caps[(size_t)k] = need[p0 + k].node_cap;
+            caps[(size_t)n_piece + k] = need[p0 + k].edge_cap;
+            caps[(size_t)2 * n_piece + k] = need[p0 + k].row_len;
+        }
+        if ((rc = c->po_ws.ensure((size_t)used * 4, false))) return rc;
+        if ((rc = c->po_list.ensure((size_t)n_piece * (4 + 8 + 8 + 12)))) return rc;   // ws_off | pool_off | list | caps
+        int64_t* d_wsoff = c->po_list.as<int64_t>();
+        int64_t* d_pooloff = d_wsoff + n_piece;
+        int32_t* d_list = reinterpret_cast<int32_t*>(d_pooloff + n_piece);
+        int32_t* d_caps = d_list + n_piece;
+        HIP_TRY(hipMemcpyAsync(d_wsoff, ws_off.data(), (size_t)n_piece * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_pooloff, pool_off.data(), (size_t)n_piece * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_list, poa_list.data() + p0, (size_t)n_piece * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(d_caps, caps.data(), (size_t)n_piece * 12, hipMemcpyHostToDevice, st));
+        PoaArgs a{};
+        a.list = d_list;
+        a.group_off = c->po_off.as<int32_t>();
+        a.seqs = dev_seqs;
+        a.seq_start = c->po_start.as<int64_t>();
+        a.seq_len = c->po_len.as<int32_t>();
+        a.ws = c->po_ws.as<int32_t>();
+        a.ws_off = d_wsoff;
+        a.node_cap = d_caps;
+        a.edge_cap = d_caps + n_piece;
+        a.row_len = d_caps + 2 * n_piece;
+        a.pool = c->po_pool.as<uint8_t>();
+        a.pool_off = d_pooloff;
+        a.out_index = d_index;
+        a.out_method = d_method;
+        a.out_len = d_len;
+        a.out_state = d_state;
+        a.cells = d_cells;
+        a.n_list = n_piece;
+        if ((rc = kmer_timed(c, st, stats, fn, "POA kernel", 1, [&] {
+                hipLaunchKernelGGL(k_poa, dim3(n_piece), dim3(kPoaThreads), 0, st, a);
+            }))) return rc;
+        if (stats) stats->n_sub_batches += 1;
+        p0 = p1;
+    }
+    std::vector<int32_t> res(ng * 4);   // index | method | len | state
+    unsigned long long cells = 0;
+    HIP_TRY(hipMemcpyAsync(&cells, d_cells, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(res.data(), d_index, ng * 16, hipMemcpyDeviceToHost, st));
+    {
+        const hipError_t q = hipStreamSynchronize(st);   // (the bases are on the device now as well)
+        if (q != hipSuccess) return fail(STRK_E_DEVICE, "%s: POA results: %s", fn, hipGetErrorString(q));
+    }
+    if (stats) stats->dp_cells = (int64_t)cells;
+    int32_t* r_index = res.data();
+    int32_t* r_method = r_index + ng;
+    int32_t* r_len = r_method + ng;
+    const int32_t* r_state = r_len + ng;
+    for (int32_t g : poa_list) {
+        if (r_state[g] == kPoaBroken) return fail(STRK_E_DEVICE, "%s: group %d: the POA kernel lost its trace-back", fn, g);
+        if (r_state[g] == kPoaOverflow) route[(size_t)g] = 2;
+    }
+    // the best representatives of the rest: the existing path, over a packed copy of those groups
+    std::vector<int32_t> rest;
+    for (int32_t g = 0; g < n_groups; ++g)
+        if (route[(size_t)g]) rest.push_back(g);
+    if (!rest.empty()) {
+        std::vector<int32_t> b_off(rest.size() + 1, 0), b_len, b_index(rest.size()), b_method(rest.size());
+        std::vector<int64_t> b_start, b_dist(rest.size());
+        for (size_t k = 0; k < rest.size(); ++k) {
+            const int32_t a = group_off[rest[k]], b = group_off[rest[k] + 1];
+            b_start.insert(b_start.end(), seq_start + a, seq_start + b);
+            b_len.insert(b_len.end(), seq_len + a, seq_len + b);
+            b_off[k + 1] = (int32_t)b_len.size();
+        }
+        strk_stats bs;
+        if ((rc = best_rep_impl(c, (int32_t)rest.size(), b_off.data(), nullptr, dev_seqs, n_seq_bytes, b_start.data(), b_len.data(),
+                                b_index.data(), b_method.data(), b_dist.data(), &bs))) return rc;
+        if (stats) {
+            stats->kernel_ms += bs.kernel_ms;
+            stats->n_dp_launches += bs.n_dp_launches;
+        }
+        for (size_t k = 0; k < rest.size(); ++k) {
+            const int32_t g = rest[k];
+            r_index[g] = b_index[k];
+            r_method[g] = b_method[k];
+            r_len[g] = b_method[k] == kConsNone ? 0 : seq_len[group_off[g] + b_index[k]];
+            if (stats && route[(size_t)g] == 2 && b_method[k] == kConsBestRep) stats->n_fallback += 1;
+        }
+    }
+    for (int32_t g = 0; g < n_groups; ++g) {
+        out_index[g] = r_index[g];
+        out_method[g] = r_method[g];
+        out_seq_off[g + 1] = out_seq_off[g] + r_len[g];
+    }
+    const int64_t n_bytes = out_seq_off[n_groups];
+    if (n_bytes > cap || n_bytes == 0) return n_bytes;
+    // the bytes of every group, gathered on the device
+    if ((rc = c->po_out.ensure((size_t)n_bytes))) return rc;
+    if ((rc = c->po_outoff.ensure((ng + 1) * 8))) return rc;
+    HIP_TRY(hipMemcpyAsync(c->po_outoff.p, out_seq_off, (ng + 1) * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d_index, r_index, ng * 8, hipMemcpyHostToDevice, st));   // index | method
+    PoaGatherArgs ga{};
+    ga.group_off = c->po_off.as<int32_t>();
+    ga.seqs = dev_seqs;
+    ga.seq_start = c->po_start.as<int64_t>();
+    ga.index = d_index;
+    ga.method = d_method;
+    ga.out_off = c->po_outoff.as<int64_t>();
+    ga.pool = c->po_pool.as<uint8_t>();
+    ga.pool_of = c->po_poolof.as<int64_t>();
+    ga.out = c->po_out.as<uint8_t>();
+    ga.n_groups = n_groups;
+    if ((rc = kmer_timed(c, st, stats, fn, "gather kernel", 1, [&] {
+            hipLaunchKernelGGL(k_poa_gather, dim3(n_groups), dim3(256), 0, st, ga);
+        }))) return rc;
+    HIP_TRY(hipMemcpyAsync(out_seqs, c->po_out.p, (size_t)n_bytes, hipMemcpyDeviceToHost, st));
+    const hipError_t q = hipStreamSynchronize(st);
+    if (q != hipSuccess) return fail(STRK_E_DEVICE, "%s: results: %s", fn, hipGetErrorString(q));
+    return n_bytes;
+}

@@ -21,32 +21,32 @@ from .fasta import Fasta
 from .gather import _distributed, call_blocks_sharded, deal_locus_blocks
 from .loci import Locus, load_loci, resolve_contig
 from .native import DeviceBam, IndexedBam, NativeBam
-from .options import DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, report_parameters
+from .options import DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, PoaCallOptions, report_parameters, with_keywords
 from .reader import open_path
 from .refside import get_loci_with_ref_data, get_locus_with_ref_data, ref_side_of_blocks
 
 # (what moved to the other modules is still offered here under the names it had)
-__all__ = ["CallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
+__all__ = ["CallOptions", "PoaCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
 
 
 def call_locus(locus: Locus, bam: BamFile, ref: Fasta, *, ctx: _lib.Context | None = None, opts: CallOptions | None = None,
                **option_keywords) -> dict:
     """The per-locus entry point (strkit/call/call_locus.py:974-995) over this backend: one locus, its LocusResult
     record up to the read records (a block of one through the same path as call_sample).  Options as for call_sample."""
-    return call_blocks([[locus]], bam, ref, dataclasses.replace(opts or CallOptions(), **option_keywords), ctx)[0][0]
+    return call_blocks([[locus]], bam, ref, with_keywords(opts, **option_keywords), ctx)[0][0]
 
 
 def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, *, sample_id: str | None = None,
                 ctx: _lib.Context | None = None, processes: int = 1, front_end: str = "auto", span_bytes: int = 4 << 30,
                 opts: CallOptions | None = None, **option_keywords) -> dict:
-    """The report of one sample.  Options: the fields of `CallOptions` (described there), by name (an unknown one is a
-    TypeError) and / or as `opts`; `seed=None` with `call_alleles` draws the run seed once and reports it.
+    """The report of one sample.  Options: the fields of `CallOptions` and of `PoaCallOptions` (described there), by name (an
+    unknown one is a TypeError) and / or as `opts`; `seed=None` with `call_alleles` draws the run seed once and reports it.
 
     `front_end` (for a `bam` given as a path): "device" = the file is inflated, scanned and cut on the GPU (DeviceBam), whole or
     in spans of at most `span_bytes` compressed bytes; "host" = on the host cores (IndexedBam, or NativeBam without an index);
     "auto" = "device" where that is possible (reader.choose_reader has the rule, reader.BackgroundOpener the retry when device
     memory runs out).  Under torch.distributed every rank opens the file on its own GPU and calls its share of the blocks."""
-    opts = dataclasses.replace(opts or CallOptions(), **option_keywords)
+    opts = with_keywords(opts, **option_keywords)
     if opts.call_alleles and opts.seed is None:
         opts = dataclasses.replace(opts, seed=int(np.random.default_rng().integers(0, 1 << 63)))
     opts.validate()

@@ -10,7 +10,7 @@ import time
 import numpy as np
 
 from ..alleles import CALLED, TOO_FEW, AlleleParams, call_alleles_batch, call_data_from_batch, locus_seeds
-from ..consensus import METHOD_NAMES, best_representatives_packed
+from ..consensus import METHOD_NAMES, best_representatives_packed, consensus_packed
 from ..kmers import count_kmers_packed, dicts_of
 
 __all__ = ["n_alleles_of", "call_block_alleles", "peak_groups", "block_consensus", "genotype_row", "block_kmers", "kmers_row"]
@@ -84,9 +84,10 @@ def peak_groups(al: dict, tract_len: np.ndarray, opts):
 
 def block_consensus(al: dict, tract_start, tract_len, anchor_start, anchor_len, opts, ctx, tm, seqs=None, d_seqs=None,
                     n_seq_bytes=None, fetch=None) -> dict:
-    """Allele sequences of a block: one strk_best_representatives call over the tract groups and the anchor groups of all
-    called peaks.  The four arrays address every kept read's raw tract and raw start anchor inside one buffer (host `seqs`, or
-    device `d_seqs` with `fetch()` returning its host copy for the few strings that are reported).  Returns
+    """Allele sequences of a block: one strk_best_representatives call (opts.consensus_method "best_rep") or one strk_consensus
+    call ("poa") over the tract groups and the anchor groups of all called peaks.  The four arrays address every kept read's raw
+    tract and raw start anchor inside one buffer (host `seqs`, or device `d_seqs` with `fetch()` returning its host copy for
+    the few strings that are reported; strk_consensus returns the strings themselves, so nothing is fetched).  Returns
     {locus: ([[sequence, method] per peak], [[anchor, method] per peak])}."""
     t_a = time.perf_counter()
     tract_start, tract_len = np.asarray(tract_start, np.int64), np.asarray(tract_len, np.int32)
@@ -98,6 +99,18 @@ def block_consensus(al: dict, tract_start, tract_len, anchor_start, anchor_len, 
     starts = np.concatenate((tract_start[t_reads], anchor_start[a_reads]))
     lens = np.concatenate((tract_len[t_reads], anchor_len[a_reads]))
     group_off = np.concatenate((t_off, t_off[-1] + a_off[1:])).astype(np.int32)
+    if opts.consensus_method == "poa":
+        out, st = consensus_packed(group_off, starts, lens, seqs=seqs, d_seqs=d_seqs, n_seq_bytes=n_seq_bytes,
+                                   max_mdn_poa_length=opts.max_mdn_poa_length, ctx=ctx, with_stats=True)
+        tm["consensus_device_s"] = tm.get("consensus_device_s", 0.0) + st["kernel_ms"] / 1e3
+        text, off, meth = out["seqs"].tobytes(), out["seq_off"].tolist(), out["method"].tolist()
+        res = {}
+        for g in range(n_groups):
+            t, a = res.setdefault(int(g_locus[g]), ([], []))
+            for k, dest in ((g, t), (n_groups + g, a)):
+                dest.append([None if meth[k] == 0 else text[off[k]:off[k + 1]].decode("ascii"), METHOD_NAMES[meth[k]]])
+        tm["consensus_s"] = tm.get("consensus_s", 0.0) + time.perf_counter() - t_a
+        return res
     out, st = best_representatives_packed(group_off, starts, lens, seqs=seqs, d_seqs=d_seqs, n_seq_bytes=n_seq_bytes, ctx=ctx,
                                           with_stats=True)
     tm["consensus_device_s"] = tm.get("consensus_device_s", 0.0) + st["kernel_ms"] / 1e3

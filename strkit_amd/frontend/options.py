@@ -2,6 +2,7 @@
 the `parameters` block of the report."""
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass
 
 from .. import _lib
@@ -14,6 +15,7 @@ MAX_READS = 250                 # params.max_reads default (strkit/call/params.p
 DEFAULT_REF_MAX_ITERS = 250     # call_locus.py:71 default_ref_max_iters (100 there is only the "slow" warning level, :72)
 VCF_ANCHOR_SIZE = 5             # params.vcf_anchor_size default
 COUNT_KMERS_MODES = ("none", "peak", "read", "both")
+CONSENSUS_METHODS = ("best_rep", "poa")
 
 
 @dataclass
@@ -43,6 +45,10 @@ class CallOptions:
     allele_params: AlleleParams | None = None
     large_consensus_length: int = 1200
     max_n_large_consensus_reads: int = 20
+    # What PoaCallOptions below turns into fields, at the values a CallOptions always has (plain class attributes, not
+    # fields: every consumer can read them from either type).
+    consensus_method = "best_rep"
+    max_mdn_poa_length = 5000
     # motif-sized k-mer counts (strkit/call/params.py count_kmers): "read" = every kept read record gets `kmers`, the counts of
     # the motif-sized windows of its raw tract; "peak" (needs call_alleles) = a called locus gets peaks.kmers, one dict per
     # peak over all reads labelled with it; "both"; "none"
@@ -52,12 +58,40 @@ class CallOptions:
         """What must hold before a block is called; needs no file and no device."""
         if self.consensus and not self.call_alleles:
             raise ValueError("consensus=True requires call_alleles=True: allele sequences are those of called alleles")
+        if self.consensus_method not in CONSENSUS_METHODS:
+            raise ValueError(f"consensus_method must be one of {', '.join(CONSENSUS_METHODS)}: got {self.consensus_method!r}")
+        if isinstance(self.max_mdn_poa_length, bool) or not isinstance(self.max_mdn_poa_length, int) or self.max_mdn_poa_length < 0:
+            raise ValueError(f"max_mdn_poa_length must be an integer >= 0: got {self.max_mdn_poa_length!r}")
         if self.count_kmers not in COUNT_KMERS_MODES:
             raise ValueError(f"count_kmers must be one of {', '.join(COUNT_KMERS_MODES)}: got {self.count_kmers!r}")
         if self.count_kmers in ("peak", "both") and not self.call_alleles:
             raise ValueError(f"count_kmers={self.count_kmers!r} requires call_alleles=True: peak counts are those of called alleles")
         if self.call_alleles and self.seed is None:
             raise ValueError("call_alleles=True needs a run seed (CallOptions.seed); call_sample draws one when none is given")
+
+
+@dataclass
+class PoaCallOptions(CallOptions):
+    """CallOptions plus the two options of the consensus stage.  `consensus_method`: how the sequence of an allele whose
+    reads differ is made, "best_rep" = one of its reads or "poa" = the consensus of its reads by partial-order
+    alignment (§12).  `max_mdn_poa_length`: the median read length above which an allele keeps its best representative under
+    "poa" (strkit/call/params.py max_mdn_poa_length).  They live in a type of their own so that the field list of CallOptions,
+    which callers and the driver's tests enumerate, stays as it was; call_sample / call_locus take both by name and build this
+    type when one of them is given (with_keywords)."""
+    consensus_method: str = "best_rep"
+    max_mdn_poa_length: int = 5000
+
+
+POA_OPTION_NAMES = ("consensus_method", "max_mdn_poa_length")
+
+
+def with_keywords(opts: CallOptions | None, **option_keywords) -> CallOptions:
+    """`opts` (or the defaults) with the options given by name replaced: dataclasses.replace, after widening a plain
+    CallOptions to PoaCallOptions when one of POA_OPTION_NAMES is among them.  An unknown name is a TypeError."""
+    opts = opts or CallOptions()
+    if not isinstance(opts, PoaCallOptions) and any(k in option_keywords for k in POA_OPTION_NAMES):
+        opts = PoaCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
+    return dataclasses.replace(opts, **option_keywords)
 
 
 def report_parameters(opts: CallOptions, processes: int) -> dict:
@@ -73,4 +107,6 @@ def report_parameters(opts: CallOptions, processes: int) -> dict:
                 "min_allele_reads": ap.min_allele_reads, "num_bootstrap": ap.num_bootstrap} if opts.call_alleles else {}),
             **({"consensus": True, "large_consensus_length": opts.large_consensus_length,
                 "max_n_large_consensus_reads": opts.max_n_large_consensus_reads} if opts.consensus else {}),
+            **({"consensus_method": opts.consensus_method} if opts.consensus_method != "best_rep" else {}),
+            **({"max_mdn_poa_length": opts.max_mdn_poa_length} if opts.max_mdn_poa_length != 5000 else {}),
             **({"count_kmers": opts.count_kmers} if opts.count_kmers != "none" else {})}
