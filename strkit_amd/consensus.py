@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._groups import group_args, pack_groups
 
 NONE, SINGLE, BEST_REP = 0, 1, 2
 POA = 3
@@ -36,58 +37,33 @@ def best_representatives_packed(group_off, seq_start, seq_len, seqs=None, d_seqs
     n_seq_bytes its size).  Returns a dict of numpy arrays over the groups: index (inside the group, -1 for an empty one),
     method (NONE / SINGLE / BEST_REP) and dist_sum."""
     ctx = ctx or _lib.default_context()
-    group_off = np.ascontiguousarray(group_off, dtype=np.int32)
-    seq_start = np.ascontiguousarray(seq_start, dtype=np.int64)
-    seq_len = np.ascontiguousarray(seq_len, dtype=np.int32)
-    n_groups = group_off.shape[0] - 1
-    if n_groups < 0 or seq_start.shape != seq_len.shape or seq_start.ndim != 1:
-        raise ValueError("group_off needs at least one entry, and seq_start and seq_len one entry per sequence")
-    if n_groups and int(group_off[-1]) != seq_start.shape[0]:
-        raise ValueError("group_off must span seq_start / seq_len")
-    if (seqs is None) == (d_seqs is None):
-        raise ValueError("exactly one of seqs (host) and d_seqs (device) must be given")
+    group_off, seq_start, seq_len, n_groups, n, h_ptr, d_ptr, _buf = group_args(group_off, seq_start, seq_len, seqs, d_seqs,
+                                                                               n_seq_bytes)
     out = dict(index=np.empty(n_groups, np.int32), method=np.empty(n_groups, np.int32),
                dist_sum=np.empty(n_groups, np.int64))
     st = _lib.StrkStats()
     L = _lib.load()
-    tail = (_ptr(seq_start), _ptr(seq_len), _ptr(out["index"]), _ptr(out["method"]), _ptr(out["dist_sum"]), C.byref(st))
+    tail = (n, _ptr(seq_start), _ptr(seq_len), _ptr(out["index"]), _ptr(out["method"]), _ptr(out["dist_sum"]), C.byref(st))
     if d_seqs is None:
-        buf = np.frombuffer(seqs, dtype=np.uint8) if isinstance(seqs, (bytes, bytearray, memoryview)) else \
-            np.ascontiguousarray(seqs, dtype=np.uint8)
-        n = buf.shape[0] if n_seq_bytes is None else int(n_seq_bytes)
-        if n > buf.shape[0]:
-            raise ValueError("n_seq_bytes exceeds the buffer")
-        _lib.check(L.strk_best_representatives(ctx.handle, n_groups, _ptr(group_off), _ptr(buf), n, *tail))
+        _lib.check(L.strk_best_representatives(ctx.handle, n_groups, _ptr(group_off), h_ptr, *tail))
     else:
-        if n_seq_bytes is None:
-            raise ValueError("d_seqs needs n_seq_bytes")
-        _lib.check(L.strk_best_representatives_dseqs(ctx.handle, n_groups, _ptr(group_off), C.c_void_p(int(d_seqs)),
-                                                     int(n_seq_bytes), *tail))
+        _lib.check(L.strk_best_representatives_dseqs(ctx.handle, n_groups, _ptr(group_off), d_ptr, *tail))
     if with_stats:
         return out, st.as_dict()
     return out
-
-
-def _as_bytes(s) -> bytes:
-    return s.encode("ascii") if isinstance(s, str) else bytes(s)
 
 
 def best_representatives(groups, ctx=None) -> list[tuple[str | None, str]]:
     """(sequence, method) per group, method in "single" | "best_rep"; (None, "none") for an empty group — the pair shape of
     peaks.seqs in the reference's JSON report (docs/output_formats.md:151-153).  Strings come back as str, bytes as str
     too (ASCII)."""
-    flat = [[_as_bytes(s) for s in g] for g in groups]
-    lens = np.fromiter((len(s) for g in flat for s in g), dtype=np.int32, count=sum(len(g) for g in flat))
-    starts = np.zeros(lens.shape[0], np.int64)
-    if lens.shape[0]:
-        np.cumsum(lens[:-1], out=starts[1:])
-    group_off = np.zeros(len(flat) + 1, np.int32)
-    np.cumsum([len(g) for g in flat], out=group_off[1:])
-    buf = np.frombuffer(b"".join(s for g in flat for s in g), dtype=np.uint8)
+    group_off, starts, lens, buf = pack_groups(groups)
     out = best_representatives_packed(group_off, starts, lens, seqs=buf, ctx=ctx)
     res: list[tuple[str | None, str]] = []
-    for g, idx, meth in zip(flat, out["index"].tolist(), out["method"].tolist()):
-        res.append((None, "none") if meth == NONE else (g[idx].decode("ascii"), METHOD_NAMES[meth]))
+    for first, idx, meth in zip(group_off.tolist(), out["index"].tolist(), out["method"].tolist()):
+        i = first + idx
+        res.append((None, "none") if meth == NONE else
+                   (buf[starts[i]:starts[i] + lens[i]].tobytes().decode("ascii"), METHOD_NAMES[meth]))
     return res
 
 
@@ -100,27 +76,8 @@ def consensus_packed(group_off, seq_start, seq_len, seqs=None, d_seqs=None, n_se
     (strk_consensus_ws), 0 = the library's defaults.  cap: the size of the byte buffer offered; None asks for the size first.
     With a cap that is too small `seqs` is None and seq_off still tells the size."""
     ctx = ctx or _lib.default_context()
-    group_off = np.ascontiguousarray(group_off, dtype=np.int32)
-    seq_start = np.ascontiguousarray(seq_start, dtype=np.int64)
-    seq_len = np.ascontiguousarray(seq_len, dtype=np.int32)
-    n_groups = group_off.shape[0] - 1
-    if n_groups < 0 or seq_start.shape != seq_len.shape or seq_start.ndim != 1:
-        raise ValueError("group_off needs at least one entry, and seq_start and seq_len one entry per sequence")
-    if n_groups and int(group_off[-1]) != seq_start.shape[0]:
-        raise ValueError("group_off must span seq_start / seq_len")
-    if (seqs is None) == (d_seqs is None):
-        raise ValueError("exactly one of seqs (host) and d_seqs (device) must be given")
-    if d_seqs is None:
-        buf = np.frombuffer(seqs, dtype=np.uint8) if isinstance(seqs, (bytes, bytearray, memoryview)) else \
-            np.ascontiguousarray(seqs, dtype=np.uint8)
-        n = buf.shape[0] if n_seq_bytes is None else int(n_seq_bytes)
-        if n > buf.shape[0]:
-            raise ValueError("n_seq_bytes exceeds the buffer")
-        h_ptr, d_ptr = _ptr(buf), None
-    else:
-        if n_seq_bytes is None:
-            raise ValueError("d_seqs needs n_seq_bytes")
-        n, h_ptr, d_ptr = int(n_seq_bytes), None, C.c_void_p(int(d_seqs))
+    group_off, seq_start, seq_len, n_groups, n, h_ptr, d_ptr, _buf = group_args(group_off, seq_start, seq_len, seqs, d_seqs,
+                                                                               n_seq_bytes)
     out = dict(index=np.empty(n_groups, np.int32), method=np.empty(n_groups, np.int32),
                seq_off=np.zeros(n_groups + 1, np.int64), seqs=None)
     st = _lib.StrkStats()
@@ -148,21 +105,10 @@ def consensus_packed(group_off, seq_start, seq_len, seqs=None, d_seqs=None, n_se
     return out
 
 
-def _pack(groups):
-    flat = [[_as_bytes(s) for s in g] for g in groups]
-    lens = np.fromiter((len(s) for g in flat for s in g), dtype=np.int32, count=sum(len(g) for g in flat))
-    starts = np.zeros(lens.shape[0], np.int64)
-    if lens.shape[0]:
-        np.cumsum(lens[:-1], out=starts[1:])
-    group_off = np.zeros(len(flat) + 1, np.int32)
-    np.cumsum([len(g) for g in flat], out=group_off[1:])
-    return group_off, starts, lens, np.frombuffer(b"".join(s for g in flat for s in g), dtype=np.uint8)
-
-
 def consensus(groups, max_mdn_poa_length: int = 5000, ctx=None) -> list[tuple[str | None, str]]:
     """(sequence, method) per group, method in "single" | "poa" | "best_rep"; (None, "none") for an empty group.  Sequences come
     back as str (latin-1, so that every byte value survives)."""
-    group_off, starts, lens, buf = _pack(groups)
+    group_off, starts, lens, buf = pack_groups(groups)
     out = consensus_packed(group_off, starts, lens, seqs=buf, max_mdn_poa_length=max_mdn_poa_length, ctx=ctx)
     text = out["seqs"].tobytes()
     off = out["seq_off"].tolist()

@@ -2,6 +2,7 @@
 // The batched counting path is here.  It stands on two host-only headers:
 //   strk_host.h     the calling thread's error message (fail, HIP_TRY) and the owning types: DevBuf, PinnedBuf, Stream, Event
 //   strk_policy.h   the adaptive policies as plain state machines: default window, band gate, grid history (no HIP in it)
+//   strk_groups.h   groups of byte strings as three calls take them: the view, its one check, the piece cutter (no HIP in it)
 // and the other parts live in include fragments spliced into this file:
 //   strk_host_miss.inc       window-miss rounds                       strk_host_pipe.inc       the pinned-slot host pipeline
 //   strk_host_ref.inc        reference side                           strk_host_realign.inc    realignment
@@ -18,6 +19,7 @@
 // device, replay that locus on the host with the same search_replay() the device uses.
 #include "strk_host.h"
 #include "strk_policy.h"
+#include "strk_groups.h"
 
 #include <algorithm>
 #include <array>
@@ -56,6 +58,7 @@ std::atomic<int> g_calls_in_flight{0};
 // default candidate window of this process, per motif-length bucket (strk_policy.h)
 strk_policy::WindowPolicy g_window;
 static_assert(strk_policy::kWinBuckets == strk::kWinBuckets, "strk_policy.h <-> strk_kernels.h");
+static_assert(strk_groups::kInvalid == STRK_E_INVALID, "strk_groups.h <-> include/strkit_amd.h");
 
 // The band pass most recently enqueued by any context of this process (its kEvBand event): in whole-grid mode the next call's
 // band pass waits for it (enqueue_scoring), so that two calls in flight run half a period apart whatever their submit times.
@@ -99,6 +102,30 @@ struct HostCounters {
     }
 };
 
+// The device copy of a view of groups (strk_groups.h), one per family of calls that takes one.
+struct GroupStage {
+    DevBuf off, start, len, seqs;
+    const uint8_t* bases = nullptr;   // the bases of the view uploaded last: the caller's d_seqs, or `seqs`
+    // Sizes the buffers and enqueues the copies of a checked view on `st`.  The bases are not copied when they are on the
+    // device already (d_seqs) or when no sequence has a byte.
+    int upload(const strk_groups::View& v, const strk_groups::Totals& t, const uint8_t* h_seqs, const uint8_t* d_seqs, hipStream_t st) {
+        const size_t ng = (size_t)v.n_groups, ns = (size_t)t.n_seqs;
+        int rc;
+        if ((rc = off.ensure((ng + 1) * 4))) return rc;
+        if ((rc = start.ensure(std::max<size_t>(ns, 1) * 8))) return rc;
+        if ((rc = len.ensure(std::max<size_t>(ns, 1) * 4))) return rc;
+        if (!d_seqs && (rc = seqs.ensure(std::max<size_t>((size_t)v.n_seq_bytes, 256)))) return rc;
+        bases = d_seqs ? d_seqs : seqs.as<uint8_t>();
+        if (!d_seqs && t.total_len > 0) HIP_TRY(hipMemcpyAsync(seqs.p, h_seqs, (size_t)v.n_seq_bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(off.p, v.group_off, (ng + 1) * 4, hipMemcpyHostToDevice, st));
+        if (ns > 0) {
+            HIP_TRY(hipMemcpyAsync(start.p, v.seq_start, ns * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(len.p, v.seq_len, ns * 4, hipMemcpyHostToDevice, st));
+        }
+        return 0;
+    }
+};
+
 }  // namespace
 
 struct strk_ctx {
@@ -113,18 +140,21 @@ struct strk_ctx {
     DevBuf out_cn, out_score, out_n, out_start;
     // realignment (strk_realign)
     DevBuf rl_s1, rl_s2, rl_pairs, rl_trace, rl_edge, rl_out, rl_cigar, rl_queue;
-    // allele calling (strk_call_alleles), on a stream of its own (created by the first call)
+    // The stream of the four calls below (side_stream creates it on first use).  One serves them all: each of these calls
+    // synchronises before it returns and leaves no work in flight, and a context serves one host thread at a time.
+    Stream side;
+    // allele calling (strk_call_alleles)
     DevBuf al_off, al_cn, al_w, al_meta, al_ws, al_out, al_rp;
-    Stream al_stream;
-    // best representatives (strk_best_representatives), likewise
-    DevBuf cs_off, cs_start, cs_len, cs_seqs, cs_bound, cs_out;
-    Stream cs_stream;
-    // distinct windows (strk_count_kmers), likewise
-    DevBuf km_off, km_start, km_len, km_k, km_seqs, km_cnt, km_eoff, km_list, km_slist, km_wsoff, km_ws, km_out;
-    Stream km_stream;
-    // allele sequences by partial-order alignment (strk_consensus), likewise
-    DevBuf po_off, po_start, po_len, po_seqs, po_res, po_pool, po_poolof, po_list, po_ws, po_out, po_outoff;
-    Stream po_stream;
+    // best representatives (strk_best_representatives)
+    GroupStage cs_in;
+    DevBuf cs_bound, cs_out;
+    // distinct windows (strk_count_kmers)
+    GroupStage km_in;
+    DevBuf km_k, km_cnt, km_eoff, km_list, km_slist, km_wsoff, km_ws, km_out;
+    // allele sequences by partial-order alignment (strk_consensus); its own stage, because the call runs the best-representative
+    // pass on some of its groups while its own arrays are still in use
+    GroupStage po_in;
+    DevBuf po_res, po_pool, po_poolof, po_list, po_ws, po_out, po_outoff;
     HostCounters h_counters;        // pinned: counters + cells + scratch_used
     // a chain of events along one call: start | after k_hash + k_plan | after k_dp_band | after k_dp_band_wide | after the
     // first k_replay pass | after k_dp_all / k_dp_ref | after k_dp_long | after k_dp_generic | end (after k_replay and the
@@ -763,6 +793,50 @@ int score_table_impl(strk_ctx* ctx, const strk_batch* batch, const int32_t* lo, 
 
 #include "strk_host_realign.inc"
 
+// The stream of strk_call_alleles, strk_best_representatives, strk_count_kmers and strk_consensus (strk_ctx::side).
+int side_stream(strk_ctx* c, hipStream_t* st) {
+    if (!c->side) HIP_TRY(hipStreamCreateWithFlags(&c->side.h, hipStreamNonBlocking));
+    *st = c->side;
+    return 0;
+}
+
+// one timed launch sequence on `st`: the events of the context bracket it, the call waits for it
+template <class F>
+int timed_launch(strk_ctx* c, hipStream_t st, strk_stats* stats, const char* fn, const char* what, int n_launches, F&& launch) {
+    hipEvent_t ev0 = c->ev[0], ev1 = c->ev[kNumEvents - 1];
+    HIP_TRY(hipEventRecord(ev0, st));
+    launch();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev1, st));
+    const hipError_t q = hipStreamSynchronize(st);
+    if (q != hipSuccess) return fail(STRK_E_DEVICE, "%s: %s: %s", fn, what, hipGetErrorString(q));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    if (stats) {
+        stats->kernel_ms += ms;
+        stats->n_dp_launches += n_launches;
+    }
+    return 0;
+}
+
+// strk_groups::check with the refusal as this library reports one: "<function>: <what is wrong>"
+int check_groups(const char* fn, const strk_groups::View& v, int max_group, int max_len, strk_groups::Totals* t) {
+    strk_groups::Message m;
+    const int rc = strk_groups::check(v, max_group, max_len, t, &m);
+    return rc ? fail(rc, "%s: %s", fn, m.text) : 0;
+}
+
+// bases that are on the device already must be on THIS context's device (no peer access is set up)
+int check_dseqs(strk_ctx* c, const char* fn, const void* d_seqs) {
+    (void)hipSetDevice(c->device);
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, d_seqs) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != c->device) {
+        (void)hipGetLastError();
+        return fail(STRK_E_INVALID, "%s: d_seqs is not device memory of device %d (the context's)", fn, c->device);
+    }
+    return 0;
+}
+
 #include "strk_host_alleles.inc"
 #include "strk_host_consensus.inc"
 #include "strk_host_kmers.inc"
@@ -997,27 +1071,24 @@ int strk_call_alleles(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off, co
 int strk_best_representatives(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const uint8_t* seqs, int64_t n_seq_bytes,
                               const int64_t* seq_start, const int32_t* seq_len, int32_t* out_index, int32_t* out_method,
                               int64_t* out_dist_sum, strk_stats* stats) {
-    if (!ctx) return fail(STRK_E_INVALID, "ctx is NULL");
-    if (ctx->pending) return fail(STRK_E_INVALID, "a submitted call is pending on this context");
+    const char* fn = "strk_best_representatives";
+    if (!ctx) return fail(STRK_E_INVALID, "%s: ctx is NULL", fn);
+    if (ctx->pending) return fail(STRK_E_INVALID, "%s: a submitted call is pending on this context", fn);
     static_assert(STRK_CONS_NONE == kConsNone && STRK_CONS_SINGLE == kConsSingle && STRK_CONS_BEST_REP == kConsBestRep,
                   "include/strkit_amd.h <-> strk_consensus.h");
-    return best_rep_impl(ctx, n_groups, group_off, seqs, nullptr, n_seq_bytes, seq_start, seq_len, out_index, out_method,
+    return best_rep_impl(ctx, fn, n_groups, group_off, seqs, nullptr, n_seq_bytes, seq_start, seq_len, out_index, out_method,
                          out_dist_sum, stats);
 }
 
 int strk_best_representatives_dseqs(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const void* d_seqs,
                                     int64_t n_seq_bytes, const int64_t* seq_start, const int32_t* seq_len, int32_t* out_index,
                                     int32_t* out_method, int64_t* out_dist_sum, strk_stats* stats) {
-    if (!ctx) return fail(STRK_E_INVALID, "ctx is NULL");
-    if (ctx->pending) return fail(STRK_E_INVALID, "a submitted call is pending on this context");
-    if (!d_seqs) return fail(STRK_E_INVALID, "d_seqs is NULL");
-    (void)hipSetDevice(ctx->device);
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_seqs) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-        (void)hipGetLastError();
-        return fail(STRK_E_INVALID, "d_seqs is not device memory of device %d (the context's)", ctx->device);
-    }
-    return best_rep_impl(ctx, n_groups, group_off, nullptr, static_cast<const uint8_t*>(d_seqs), n_seq_bytes, seq_start, seq_len,
+    const char* fn = "strk_best_representatives_dseqs";
+    if (!ctx) return fail(STRK_E_INVALID, "%s: ctx is NULL", fn);
+    if (ctx->pending) return fail(STRK_E_INVALID, "%s: a submitted call is pending on this context", fn);
+    if (!d_seqs) return fail(STRK_E_INVALID, "%s: d_seqs is NULL", fn);
+    if (const int rc = check_dseqs(ctx, fn, d_seqs)) return rc;
+    return best_rep_impl(ctx, fn, n_groups, group_off, nullptr, static_cast<const uint8_t*>(d_seqs), n_seq_bytes, seq_start, seq_len,
                          out_index, out_method, out_dist_sum, stats);
 }
 
@@ -1029,14 +1100,7 @@ int64_t strk_count_kmers_ws(strk_ctx* ctx, int32_t n_groups, const int32_t* grou
     if (!ctx) return fail(STRK_E_INVALID, "%s: ctx is NULL", fn);
     if (ctx->pending) return fail(STRK_E_INVALID, "%s: a submitted call is pending on this context", fn);
     if (seqs && d_seqs) return fail(STRK_E_INVALID, "strk_count_kmers_ws: both seqs and d_seqs are given");
-    if (d_seqs) {
-        (void)hipSetDevice(ctx->device);
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, d_seqs) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-            (void)hipGetLastError();
-            return fail(STRK_E_INVALID, "%s: d_seqs is not device memory of device %d (the context's)", fn, ctx->device);
-        }
-    }
+    if (const int rc = d_seqs ? check_dseqs(ctx, fn, d_seqs) : 0) return rc;
     return count_kmers_impl(ctx, fn, n_groups, group_off, seqs, static_cast<const uint8_t*>(d_seqs), n_seq_bytes, seq_start,
                             seq_len, k, cap, out_entry_off, out_pos, out_count, workspace_bytes, stats);
 }
@@ -1066,14 +1130,7 @@ int64_t strk_consensus_ws(strk_ctx* ctx, int32_t n_groups, const int32_t* group_
     if (ctx->pending) return fail(STRK_E_INVALID, "%s: a submitted call is pending on this context", fn);
     if (seqs && d_seqs) return fail(STRK_E_INVALID, "strk_consensus_ws: both seqs and d_seqs are given");
     static_assert(STRK_CONS_POA == kConsPoa, "include/strkit_amd.h <-> strk_poa.h");
-    if (d_seqs) {
-        (void)hipSetDevice(ctx->device);
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, d_seqs) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-            (void)hipGetLastError();
-            return fail(STRK_E_INVALID, "%s: d_seqs is not device memory of device %d (the context's)", fn, ctx->device);
-        }
-    }
+    if (const int rc = d_seqs ? check_dseqs(ctx, fn, d_seqs) : 0) return rc;
     return consensus_impl(ctx, fn, n_groups, group_off, seqs, static_cast<const uint8_t*>(d_seqs), n_seq_bytes, seq_start, seq_len,
                           max_mdn_poa_length, cap, out_index, out_method, out_seq_off, out_seqs, node_limit, workspace_bytes, stats);
 }

@@ -1,6 +1,6 @@
 // Host side of strk_call_alleles (strkit/call/allele.py:176-336 + call_locus.py:1536-1600): input checks, pieces, launches.
-// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, strk_ctx defined there);
-// not a stand-alone header.
+// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, strk_ctx and side_stream
+// defined there); not a stand-alone header.
 // ---------------------------------------------------------------------------------------------
 // Allele calling: strk_call_alleles
 // ---------------------------------------------------------------------------------------------
@@ -40,27 +40,23 @@ int call_alleles_impl(strk_ctx* c, int32_t n_loci, const int32_t* read_off, cons
             if (!std::isfinite(w[r]) || !(w[r] > 0.0)) return fail(STRK_E_INVALID, "locus %d: read %d has weight %g", l, r, w[r]);
     }
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->al_stream) HIP_TRY(hipStreamCreateWithFlags(&c->al_stream.h, hipStreamNonBlocking));
-    hipStream_t st = c->al_stream;
+    hipStream_t st;
+    if (const int rc = side_stream(c, &st)) return rc;
     const int B = p->num_bootstrap;
     const int threads = std::min(256, (B + 63) / 64 * 64);
     std::vector<int64_t> ws_off;
     std::vector<int32_t> off_rel, oi;
     std::vector<double> od;
     hipEvent_t ev0 = c->ev[0], ev1 = c->ev[kNumEvents - 1];
-    for (int32_t l0 = 0; l0 < n_loci;) {
+    auto locus_ws = [&](size_t l) {
+        const int n = read_off[l + 1] - read_off[l];
+        return (int64_t)(n >= p->min_reads ? allele_ws_bytes(n, B) : 0);
+    };
+    for (int32_t l0 = 0, l1; l0 < n_loci; l0 = l1) {
         // one piece: loci in caller order while their workspace fits the budget
-        int32_t l1 = l0;
-        size_t wsum = 0;
-        ws_off.clear();
-        while (l1 < n_loci && l1 - l0 < kAllelePieceLoci) {
-            const int n = read_off[l1 + 1] - read_off[l1];
-            const size_t b = n >= p->min_reads ? allele_ws_bytes(n, B) : 0;
-            if (l1 > l0 && wsum + b > kAlleleWsBudget) break;
-            ws_off.push_back((int64_t)wsum);
-            wsum += b;
-            ++l1;
-        }
+        int64_t wsum = 0;
+        l1 = (int32_t)strk_groups::cut_piece((size_t)l0, (size_t)n_loci, locus_ws, (int64_t)kAlleleWsBudget, kAllelePieceLoci,
+                                             ws_off, &wsum);
         const int32_t nl = l1 - l0, r0 = read_off[l0], nr = read_off[l1] - r0;
         off_rel.resize((size_t)nl + 1);
         for (int32_t l = 0; l <= nl; ++l) off_rel[l] = read_off[l0 + l] - r0;
@@ -70,7 +66,7 @@ int call_alleles_impl(strk_ctx* c, int32_t n_loci, const int32_t* read_off, cons
         if ((rc = c->al_w.ensure(std::max<size_t>(nr, 1) * 8))) return rc;
         const size_t nal_bytes = ((size_t)nl * 4 + 7) & ~(size_t)7;   // n_alleles, padded so that the seeds are 8-aligned
         if ((rc = c->al_meta.ensure(nal_bytes + (size_t)nl * 16))) return rc;
-        if ((rc = c->al_ws.ensure(std::max<size_t>(wsum, 256)))) return rc;
+        if ((rc = c->al_ws.ensure(std::max<size_t>((size_t)wsum, 256)))) return rc;
         if ((rc = c->al_out.ensure((size_t)nl * (kAlleleOutI * 4 + kAlleleOutD * 8)))) return rc;
         if ((rc = c->al_rp.ensure(std::max<size_t>(nr, 1) * 4))) return rc;
         char* meta = c->al_meta.as<char>();
@@ -140,7 +136,6 @@ int call_alleles_impl(strk_ctx* c, int32_t n_loci, const int32_t* read_off, cons
                 out_ci99[4 * g + e] = s[8 + e];
             }
         }
-        l0 = l1;
     }
     return 0;
 }

@@ -1,29 +1,10 @@
 // Host side of strk_count_kmers / strk_count_kmers_dseqs / strk_count_kmers_ws: input checks, launch lists, pieces, prefix sums.
-// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, strk_ctx defined there);
-// not a stand-alone header.
+// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, strk_ctx, check_groups,
+// side_stream and timed_launch defined there); not a stand-alone header.
 // ---------------------------------------------------------------------------------------------
 // Distinct windows of every group: strk_count_kmers
 // ---------------------------------------------------------------------------------------------
 constexpr int64_t kKmerWsBytes = (int64_t)1 << 30;   // elements of one launch of k_kmers_sort (a group beyond it runs alone)
-
-// one timed launch sequence on `st`: the events of the context bracket it, the call waits for it
-template <class F>
-int kmer_timed(strk_ctx* c, hipStream_t st, strk_stats* stats, const char* fn, const char* what, int n_launches, F&& launch) {
-    hipEvent_t ev0 = c->ev[0], ev1 = c->ev[kNumEvents - 1];
-    HIP_TRY(hipEventRecord(ev0, st));
-    launch();
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev1, st));
-    const hipError_t q = hipStreamSynchronize(st);
-    if (q != hipSuccess) return fail(STRK_E_DEVICE, "%s: %s: %s", fn, what, hipGetErrorString(q));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-    if (stats) {
-        stats->kernel_ms += ms;
-        stats->n_dp_launches += n_launches;
-    }
-    return 0;
-}
 
 // `d_seqs` != nullptr: the bases are in device memory already and `seqs` is not read.  ws_bytes <= 0: kKmerWsBytes.
 int64_t count_kmers_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int32_t* group_off, const uint8_t* seqs,
@@ -31,28 +12,16 @@ int64_t count_kmers_impl(strk_ctx* c, const char* fn, int32_t n_groups, const in
                          const int32_t* k, int64_t cap, int64_t* out_entry_off, int64_t* out_pos, int32_t* out_count,
                          int64_t ws_bytes, strk_stats* stats) {
     if (stats) memset(stats, 0, sizeof *stats);
-    if (n_groups < 0) return fail(STRK_E_INVALID, "%s: n_groups < 0", fn);
-    if (n_seq_bytes < 0) return fail(STRK_E_INVALID, "%s: n_seq_bytes < 0", fn);
+    const strk_groups::View view{n_groups, group_off, n_seq_bytes, seq_start, seq_len};
+    strk_groups::Totals tot;
+    int rc;
+    if ((rc = check_groups(fn, view, kKmerMaxGroup, kKmerMaxLen, &tot))) return rc;
     if (cap < 0) return fail(STRK_E_INVALID, "%s: cap < 0", fn);
     if (!out_entry_off) return fail(STRK_E_INVALID, "%s: out_entry_off is NULL", fn);
     if (cap > 0 && (!out_pos || !out_count)) return fail(STRK_E_INVALID, "%s: cap > 0 with a NULL output array", fn);
-    if (n_groups > 0 && (!group_off || !k)) return fail(STRK_E_INVALID, "%s: NULL argument", fn);
-    if (n_groups > 0 && group_off[0] != 0) return fail(STRK_E_INVALID, "%s: group_off[0] must be 0", fn);
-    for (int32_t g = 0; g < n_groups; ++g) {
-        const int64_t n = (int64_t)group_off[g + 1] - group_off[g];
-        if (n < 0) return fail(STRK_E_INVALID, "%s: group %d: group_off is decreasing", fn, g);
-        if (n > kKmerMaxGroup) return fail(STRK_E_INVALID, "%s: group %d: %lld sequences (at most %d)", fn, g, (long long)n, kKmerMaxGroup);
+    if (n_groups > 0 && !k) return fail(STRK_E_INVALID, "%s: NULL argument", fn);
+    for (int32_t g = 0; g < n_groups; ++g)
         if (k[g] < 1) return fail(STRK_E_INVALID, "%s: group %d: window length %d (at least 1)", fn, g, k[g]);
-    }
-    const int32_t n_seqs = n_groups > 0 ? group_off[n_groups] : 0;
-    if (n_seqs > 0 && (!seq_start || !seq_len)) return fail(STRK_E_INVALID, "%s: NULL argument", fn);
-    for (int32_t i = 0; i < n_seqs; ++i) {
-        if (seq_len[i] < 0 || seq_len[i] > kKmerMaxLen)
-            return fail(STRK_E_INVALID, "%s: sequence %d: length %d is outside 0..%d", fn, i, seq_len[i], kKmerMaxLen);
-        if (seq_start[i] < 0 || seq_start[i] > n_seq_bytes - seq_len[i])
-            return fail(STRK_E_INVALID, "%s: sequence %d: bytes %lld..%lld lie outside the %lld given", fn, i,
-                        (long long)seq_start[i], (long long)(seq_start[i] + seq_len[i]), (long long)n_seq_bytes);
-    }
     // windows per group; the launch lists of the table kernel (a group without windows has no entries and no workgroup)
     std::vector<int64_t> windows((size_t)n_groups, 0);
     std::vector<int32_t> lists;   // small | large
@@ -79,33 +48,23 @@ int64_t count_kmers_impl(strk_ctx* c, const char* fn, int32_t n_groups, const in
     const int64_t ws_elems = std::max<int64_t>(1, ws_bytes / (int64_t)sizeof(KmerElem));
 
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->km_stream) HIP_TRY(hipStreamCreateWithFlags(&c->km_stream.h, hipStreamNonBlocking));
-    hipStream_t st = c->km_stream;
-    int rc;
+    hipStream_t st;
+    if ((rc = side_stream(c, &st))) return rc;
     const size_t ng = (size_t)n_groups;
-    if ((rc = c->km_off.ensure((ng + 1) * 4))) return rc;
-    if ((rc = c->km_start.ensure((size_t)n_seqs * 8))) return rc;
-    if ((rc = c->km_len.ensure((size_t)n_seqs * 4))) return rc;
     if ((rc = c->km_k.ensure(ng * 4))) return rc;
     if ((rc = c->km_cnt.ensure(ng * 8))) return rc;               // cnt | state
     if ((rc = c->km_eoff.ensure((ng + 1) * 8))) return rc;
     if ((rc = c->km_list.ensure(lists.size() * 4))) return rc;
-    if (!d_seqs) {
-        if ((rc = c->km_seqs.ensure(std::max<size_t>((size_t)n_seq_bytes, 256)))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->km_seqs.p, seqs, (size_t)n_seq_bytes, hipMemcpyHostToDevice, st));
-    }
-    HIP_TRY(hipMemcpyAsync(c->km_off.p, group_off, (ng + 1) * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->km_start.p, seq_start, (size_t)n_seqs * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->km_len.p, seq_len, (size_t)n_seqs * 4, hipMemcpyHostToDevice, st));
+    if ((rc = c->km_in.upload(view, tot, seqs, d_seqs, st))) return rc;
     HIP_TRY(hipMemcpyAsync(c->km_k.p, k, ng * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(c->km_list.p, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(c->km_cnt.p, 0, ng * 8, st));
 
     KmerArgs a{};
-    a.group_off = c->km_off.as<int32_t>();
-    a.seqs = d_seqs ? d_seqs : c->km_seqs.as<uint8_t>();
-    a.seq_start = c->km_start.as<int64_t>();
-    a.seq_len = c->km_len.as<int32_t>();
+    a.group_off = c->km_in.off.as<int32_t>();
+    a.seqs = c->km_in.bases;
+    a.seq_start = c->km_in.start.as<int64_t>();
+    a.seq_len = c->km_in.len.as<int32_t>();
     a.k = c->km_k.as<int32_t>();
     a.cnt = c->km_cnt.as<int32_t>();
     a.state = a.cnt + n_groups;
@@ -126,7 +85,7 @@ int64_t count_kmers_impl(strk_ctx* c, const char* fn, int32_t n_groups, const in
         }
     };
     // pass 1: the entries of every group the table takes
-    if ((rc = kmer_timed(c, st, stats, fn, "table kernel (count)", (n_small > 0) + (n_large > 0), [&] { table_pass(kKmerCount); }))) return rc;
+    if ((rc = timed_launch(c, st, stats, fn, "table kernel (count)", (n_small > 0) + (n_large > 0), [&] { table_pass(kKmerCount); }))) return rc;
     std::vector<int32_t> cnt(ng * 2);
     HIP_TRY(hipMemcpyAsync(cnt.data(), c->km_cnt.p, ng * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -155,18 +114,14 @@ int64_t count_kmers_impl(strk_ctx* c, const char* fn, int32_t n_groups, const in
         for (; done < g_end; ++done) out_entry_off[done + 1] = out_entry_off[done] + cnt[(size_t)done];
     };
     std::vector<int64_t> ws_off;
-    for (size_t p0 = 0; p0 < sorted.size();) {
-        ws_off.clear();
+    auto sort_elems = [&](size_t p) {   // the power of two above the group's window count
+        int64_t pow2 = 1;
+        while (pow2 < windows[(size_t)sorted[p]]) pow2 <<= 1;
+        return pow2;
+    };
+    for (size_t p0 = 0, p1; p0 < sorted.size(); p0 = p1) {
         int64_t used = 0;
-        size_t p1 = p0;
-        while (p1 < sorted.size()) {
-            int64_t pow2 = 1;
-            while (pow2 < windows[(size_t)sorted[p1]]) pow2 <<= 1;
-            if (p1 > p0 && used + pow2 > ws_elems) break;
-            ws_off.push_back(used);
-            used += pow2;
-            ++p1;
-        }
+        p1 = strk_groups::cut_piece(p0, sorted.size(), sort_elems, ws_elems, strk_groups::kNoItemCap, ws_off, &used);
         const int32_t n_piece = (int32_t)(p1 - p0);
         if ((rc = c->km_ws.ensure((size_t)used * sizeof(KmerElem)))) return rc;
         if ((rc = c->km_wsoff.ensure((size_t)n_piece * 8))) return rc;
@@ -179,7 +134,7 @@ int64_t count_kmers_impl(strk_ctx* c, const char* fn, int32_t n_groups, const in
         s.ws = c->km_ws.as<KmerElem>();
         s.ws_off = c->km_wsoff.as<int64_t>();
         s.mode = kKmerCount;
-        if ((rc = kmer_timed(c, st, stats, fn, "sort kernel", 1, [&] {
+        if ((rc = timed_launch(c, st, stats, fn, "sort kernel", 1, [&] {
                 hipLaunchKernelGGL(k_kmers_sort, dim3(n_piece), dim3(kKmerSortThreads), 0, st, s);
             }))) return rc;
         HIP_TRY(hipMemcpyAsync(cnt.data(), c->km_cnt.p, ng * 4, hipMemcpyDeviceToHost, st));
@@ -189,19 +144,18 @@ int64_t count_kmers_impl(strk_ctx* c, const char* fn, int32_t n_groups, const in
         if (out_entry_off[g_end] <= n_out) {
             HIP_TRY(hipMemcpyAsync(c->km_eoff.p, out_entry_off, (size_t)g_end * 8, hipMemcpyHostToDevice, st));
             s.mode = kKmerWrite;
-            if ((rc = kmer_timed(c, st, stats, fn, "sort kernel (write)", 1, [&] {
+            if ((rc = timed_launch(c, st, stats, fn, "sort kernel (write)", 1, [&] {
                     hipLaunchKernelGGL(k_kmers_sort, dim3(n_piece), dim3(kKmerSortThreads), 0, st, s);
                 }))) return rc;
         }
         if (stats) stats->n_sub_batches += 1;
-        p0 = p1;
     }
     prefix_to(n_groups);
     const int64_t n_entries = out_entry_off[n_groups];
     if (n_entries > cap) return n_entries;
     // pass 2: the table kernel writes its groups' entries
     HIP_TRY(hipMemcpyAsync(c->km_eoff.p, out_entry_off, ng * 8, hipMemcpyHostToDevice, st));
-    if ((rc = kmer_timed(c, st, stats, fn, "table kernel (write)", (n_small > 0) + (n_large > 0), [&] { table_pass(kKmerWrite); }))) return rc;
+    if ((rc = timed_launch(c, st, stats, fn, "table kernel (write)", (n_small > 0) + (n_large > 0), [&] { table_pass(kKmerWrite); }))) return rc;
     HIP_TRY(hipMemcpyAsync(out_pos, a.out_pos, (size_t)n_entries * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out_count, a.out_count, (size_t)n_entries * 4, hipMemcpyDeviceToHost, st));
     const hipError_t q = hipStreamSynchronize(st);

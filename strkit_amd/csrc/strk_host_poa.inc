@@ -1,7 +1,7 @@
 // Host side of strk_consensus / strk_consensus_dseqs / strk_consensus_ws: input checks, the method of every group, launches
 // of k_poa cut at a group count and at a workspace bound, the best-representative path for the rest, the bytes' gather.
-// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, strk_ctx, best_rep_impl and
-// kmer_timed defined there); not a stand-alone header.
+// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, strk_ctx, check_groups,
+// side_stream, timed_launch and best_rep_impl defined there); not a stand-alone header.
 // ---------------------------------------------------------------------------------------------
 // Allele sequences by partial-order alignment: strk_consensus
 // ---------------------------------------------------------------------------------------------
@@ -15,32 +15,17 @@ int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int3
                        int32_t max_mdn, int64_t cap, int32_t* out_index, int32_t* out_method, int64_t* out_seq_off,
                        uint8_t* out_seqs, int32_t node_limit, int64_t ws_bytes, strk_stats* stats) {
     if (stats) memset(stats, 0, sizeof *stats);
-    if (n_groups < 0) return fail(STRK_E_INVALID, "%s: n_groups < 0", fn);
-    if (n_seq_bytes < 0) return fail(STRK_E_INVALID, "%s: n_seq_bytes < 0", fn);
+    const strk_groups::View view{n_groups, group_off, n_seq_bytes, seq_start, seq_len};
+    strk_groups::Totals tot;
+    int rc;
+    if ((rc = check_groups(fn, view, kConsMaxGroup, kConsMaxLen, &tot))) return rc;
     if (max_mdn < 0) return fail(STRK_E_INVALID, "%s: max_mdn_poa_length < 0", fn);
     if (cap < 0) return fail(STRK_E_INVALID, "%s: cap < 0", fn);
     if (node_limit > kPoaMaxNodes) return fail(STRK_E_INVALID, "%s: node_limit %d (at most %d)", fn, node_limit, kPoaMaxNodes);
     if (!out_seq_off) return fail(STRK_E_INVALID, "%s: out_seq_off is NULL", fn);
     if (cap > 0 && !out_seqs) return fail(STRK_E_INVALID, "%s: cap > 0 with out_seqs NULL", fn);
-    if (n_groups > 0 && (!group_off || !out_index || !out_method)) return fail(STRK_E_INVALID, "%s: NULL argument", fn);
-    if (n_groups > 0 && group_off[0] != 0) return fail(STRK_E_INVALID, "%s: group_off[0] must be 0", fn);
-    for (int32_t g = 0; g < n_groups; ++g) {
-        const int64_t n = (int64_t)group_off[g + 1] - group_off[g];
-        if (n < 0) return fail(STRK_E_INVALID, "%s: group %d: group_off is decreasing", fn, g);
-        if (n > kConsMaxGroup) return fail(STRK_E_INVALID, "%s: group %d: %lld sequences (at most %d)", fn, g, (long long)n, kConsMaxGroup);
-    }
-    const int32_t n_seqs = n_groups > 0 ? group_off[n_groups] : 0;
-    if (n_seqs > 0 && (!seq_start || !seq_len)) return fail(STRK_E_INVALID, "%s: NULL argument", fn);
-    int64_t total_len = 0;
-    for (int32_t i = 0; i < n_seqs; ++i) {
-        if (seq_len[i] < 0 || seq_len[i] > kConsMaxLen)
-            return fail(STRK_E_INVALID, "%s: sequence %d: length %d is outside 0..%d", fn, i, seq_len[i], kConsMaxLen);
-        if (seq_start[i] < 0 || seq_start[i] > n_seq_bytes - seq_len[i])
-            return fail(STRK_E_INVALID, "%s: sequence %d: bytes %lld..%lld lie outside the %lld given", fn, i,
-                        (long long)seq_start[i], (long long)(seq_start[i] + seq_len[i]), (long long)n_seq_bytes);
-        total_len += seq_len[i];
-    }
-    if (total_len > 0 && !seqs && !d_seqs) return fail(STRK_E_INVALID, "%s: seqs is NULL", fn);
+    if (n_groups > 0 && (!out_index || !out_method)) return fail(STRK_E_INVALID, "%s: NULL argument", fn);
+    if (tot.total_len > 0 && !seqs && !d_seqs) return fail(STRK_E_INVALID, "%s: seqs is NULL", fn);
     static_assert(kPoaMaxGroup == kConsMaxGroup, "strk_poa.h <-> strk_consensus.h");
     out_seq_off[0] = 0;
     if (n_groups == 0) return 0;
@@ -90,25 +75,13 @@ int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int3
     }
 
     HIP_TRY(hipSetDevice(c->device));
-    if (!c->po_stream) HIP_TRY(hipStreamCreateWithFlags(&c->po_stream.h, hipStreamNonBlocking));
-    hipStream_t st = c->po_stream;
-    int rc;
-    if ((rc = c->po_off.ensure((ng + 1) * 4))) return rc;
-    if ((rc = c->po_start.ensure(std::max<size_t>(n_seqs, 1) * 8))) return rc;
-    if ((rc = c->po_len.ensure(std::max<size_t>(n_seqs, 1) * 4))) return rc;
+    hipStream_t st;
+    if ((rc = side_stream(c, &st))) return rc;
     if ((rc = c->po_res.ensure(ng * 16 + 8))) return rc;              // cells | index | method | len | state
     if ((rc = c->po_pool.ensure(std::max<size_t>((size_t)pool_bytes, 256)))) return rc;
     if ((rc = c->po_poolof.ensure(ng * 8))) return rc;
-    if (!d_seqs) {
-        if ((rc = c->po_seqs.ensure(std::max<size_t>((size_t)n_seq_bytes, 256)))) return rc;
-        if (n_seq_bytes > 0 && total_len > 0) HIP_TRY(hipMemcpyAsync(c->po_seqs.p, seqs, (size_t)n_seq_bytes, hipMemcpyHostToDevice, st));
-    }
-    const uint8_t* dev_seqs = d_seqs ? d_seqs : c->po_seqs.as<uint8_t>();
-    HIP_TRY(hipMemcpyAsync(c->po_off.p, group_off, (ng + 1) * 4, hipMemcpyHostToDevice, st));
-    if (n_seqs > 0) {
-        HIP_TRY(hipMemcpyAsync(c->po_start.p, seq_start, (size_t)n_seqs * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(c->po_len.p, seq_len, (size_t)n_seqs * 4, hipMemcpyHostToDevice, st));
-    }
+    if ((rc = c->po_in.upload(view, tot, seqs, d_seqs, st))) return rc;
+    const uint8_t* dev_seqs = c->po_in.bases;
     HIP_TRY(hipMemcpyAsync(c->po_poolof.p, pool_of.data(), ng * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemsetAsync(c->po_res.p, 0, ng * 16 + 8, st));
     unsigned long long* d_cells = c->po_res.as<unsigned long long>();
@@ -120,21 +93,15 @@ int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int3
     // k_poa over its groups, in pieces
     std::vector<int64_t> ws_off, pool_off;
     std::vector<int32_t> caps;
-    for (size_t p0 = 0; p0 < poa_list.size();) {
-        ws_off.clear();
-        pool_off.clear();
+    for (size_t p0 = 0, p1; p0 < poa_list.size(); p0 = p1) {
         int64_t used = 0;
-        size_t p1 = p0;
-        while (p1 < poa_list.size() && p1 - p0 < (size_t)kPoaPieceGroups) {
-            if (p1 > p0 && used + need[p1].ints > ws_ints) break;
-            ws_off.push_back(used);
-            pool_off.push_back(pool_of[(size_t)poa_list[p1]]);
-            used += need[p1].ints;
-            ++p1;
-        }
+        p1 = strk_groups::cut_piece(p0, poa_list.size(), [&](size_t p) { return need[p].ints; }, ws_ints, kPoaPieceGroups,
+                                    ws_off, &used);
         const int32_t n_piece = (int32_t)(p1 - p0);
+        pool_off.resize((size_t)n_piece);
         caps.resize((size_t)n_piece * 3);
         for (int32_t k = 0; k < n_piece; ++k) {
+            pool_off[(size_t)k] = pool_of[(size_t)poa_list[p0 + k]];
             caps[(size_t)k] = need[p0 + k].node_cap;
             caps[(size_t)n_piece + k] = need[p0 + k].edge_cap;
             caps[(size_t)2 * n_piece + k] = need[p0 + k].row_len;
@@ -151,10 +118,10 @@ int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int3
         HIP_TRY(hipMemcpyAsync(d_caps, caps.data(), (size_t)n_piece * 12, hipMemcpyHostToDevice, st));
         PoaArgs a{};
         a.list = d_list;
-        a.group_off = c->po_off.as<int32_t>();
+        a.group_off = c->po_in.off.as<int32_t>();
         a.seqs = dev_seqs;
-        a.seq_start = c->po_start.as<int64_t>();
-        a.seq_len = c->po_len.as<int32_t>();
+        a.seq_start = c->po_in.start.as<int64_t>();
+        a.seq_len = c->po_in.len.as<int32_t>();
         a.ws = c->po_ws.as<int32_t>();
         a.ws_off = d_wsoff;
         a.node_cap = d_caps;
@@ -168,11 +135,10 @@ int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int3
         a.out_state = d_state;
         a.cells = d_cells;
         a.n_list = n_piece;
-        if ((rc = kmer_timed(c, st, stats, fn, "POA kernel", 1, [&] {
+        if ((rc = timed_launch(c, st, stats, fn, "POA kernel", 1, [&] {
                 hipLaunchKernelGGL(k_poa, dim3(n_piece), dim3(kPoaThreads), 0, st, a);
             }))) return rc;
         if (stats) stats->n_sub_batches += 1;
-        p0 = p1;
     }
     std::vector<int32_t> res(ng * 4);   // index | method | len | state
     unsigned long long cells = 0;
@@ -205,7 +171,7 @@ int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int3
             b_off[k + 1] = (int32_t)b_len.size();
         }
         strk_stats bs;
-        if ((rc = best_rep_impl(c, (int32_t)rest.size(), b_off.data(), nullptr, dev_seqs, n_seq_bytes, b_start.data(), b_len.data(),
+        if ((rc = best_rep_impl(c, fn, (int32_t)rest.size(), b_off.data(), nullptr, dev_seqs, n_seq_bytes, b_start.data(), b_len.data(),
                                 b_index.data(), b_method.data(), b_dist.data(), &bs))) return rc;
         if (stats) {
             stats->kernel_ms += bs.kernel_ms;
@@ -232,9 +198,9 @@ int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int3
     HIP_TRY(hipMemcpyAsync(c->po_outoff.p, out_seq_off, (ng + 1) * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(d_index, r_index, ng * 8, hipMemcpyHostToDevice, st));   // index | method
     PoaGatherArgs ga{};
-    ga.group_off = c->po_off.as<int32_t>();
+    ga.group_off = c->po_in.off.as<int32_t>();
     ga.seqs = dev_seqs;
-    ga.seq_start = c->po_start.as<int64_t>();
+    ga.seq_start = c->po_in.start.as<int64_t>();
     ga.index = d_index;
     ga.method = d_method;
     ga.out_off = c->po_outoff.as<int64_t>();
@@ -242,7 +208,7 @@ int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int3
     ga.pool_of = c->po_poolof.as<int64_t>();
     ga.out = c->po_out.as<uint8_t>();
     ga.n_groups = n_groups;
-    if ((rc = kmer_timed(c, st, stats, fn, "gather kernel", 1, [&] {
+    if ((rc = timed_launch(c, st, stats, fn, "gather kernel", 1, [&] {
             hipLaunchKernelGGL(k_poa_gather, dim3(n_groups), dim3(256), 0, st, ga);
         }))) return rc;
     HIP_TRY(hipMemcpyAsync(out_seqs, c->po_out.p, (size_t)n_bytes, hipMemcpyDeviceToHost, st));

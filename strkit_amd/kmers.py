@@ -14,6 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._groups import group_args, pack_groups
 
 MAX_GROUP = 250
 MAX_LEN = 65535
@@ -33,29 +34,12 @@ def count_kmers_packed(group_off, seq_start, seq_len, k, seqs=None, d_seqs=None,
     entry_off[g]:entry_off[g+1], in ascending byte order of their windows.  `workspace_bytes` bounds the device workspace of one
     launch (None: the library's default); the result does not depend on it."""
     ctx = ctx or _lib.default_context()
-    group_off = np.ascontiguousarray(group_off, dtype=np.int32)
-    seq_start = np.ascontiguousarray(seq_start, dtype=np.int64)
-    seq_len = np.ascontiguousarray(seq_len, dtype=np.int32)
+    shapes = "group_off needs at least one entry, seq_start and seq_len one entry per sequence, k one per group"
+    group_off, seq_start, seq_len, n_groups, n, h_seqs, dev, _buf = group_args(group_off, seq_start, seq_len, seqs, d_seqs,
+                                                                               n_seq_bytes, shapes=shapes)
     k = np.ascontiguousarray(k, dtype=np.int32)
-    n_groups = group_off.shape[0] - 1
-    if n_groups < 0 or seq_start.shape != seq_len.shape or seq_start.ndim != 1 or k.shape != (n_groups,):
-        raise ValueError("group_off needs at least one entry, seq_start and seq_len one entry per sequence, k one per group")
-    if n_groups and int(group_off[-1]) != seq_start.shape[0]:
-        raise ValueError("group_off must span seq_start / seq_len")
-    if (seqs is None) == (d_seqs is None):
-        raise ValueError("exactly one of seqs (host) and d_seqs (device) must be given")
-    if d_seqs is None:
-        buf = np.frombuffer(seqs, dtype=np.uint8) if isinstance(seqs, (bytes, bytearray, memoryview)) else \
-            np.ascontiguousarray(seqs, dtype=np.uint8)
-        n = buf.shape[0] if n_seq_bytes is None else int(n_seq_bytes)
-        if n > buf.shape[0]:
-            raise ValueError("n_seq_bytes exceeds the buffer")
-        h_seqs, dev = _ptr(buf), C.c_void_p(None)
-    else:
-        if n_seq_bytes is None:
-            raise ValueError("d_seqs needs n_seq_bytes")
-        n = int(n_seq_bytes)
-        h_seqs, dev = C.c_void_p(None), C.c_void_p(int(d_seqs))
+    if k.shape != (n_groups,):
+        raise ValueError(shapes)
     entry_off = np.zeros(n_groups + 1, np.int64)
     st = _lib.StrkStats()
     L = _lib.load()
@@ -87,24 +71,13 @@ def count_kmers_packed(group_off, seq_start, seq_len, k, seqs=None, d_seqs=None,
     return out
 
 
-def _as_bytes(s) -> bytes:
-    return s.encode("ascii") if isinstance(s, str) else bytes(s)
-
-
 def count_kmers(groups, k, ctx=None) -> list[dict[bytes, int]]:
     """{window: count} per group, the keys in ascending byte order.  `groups`: lists of bytes (or ASCII str); `k`: one window
     length for all groups or one per group."""
-    flat = [[_as_bytes(s) for s in g] for g in groups]
-    ks = np.full(len(flat), k, np.int32) if np.isscalar(k) else np.asarray(k, np.int32)
-    lens = np.fromiter((len(s) for g in flat for s in g), dtype=np.int32, count=sum(len(g) for g in flat))
-    starts = np.zeros(lens.shape[0], np.int64)
-    if lens.shape[0]:
-        np.cumsum(lens[:-1], out=starts[1:])
-    group_off = np.zeros(len(flat) + 1, np.int32)
-    np.cumsum([len(g) for g in flat], out=group_off[1:])
-    text = b"".join(s for g in flat for s in g)
-    out = count_kmers_packed(group_off, starts, lens, ks, seqs=np.frombuffer(text, dtype=np.uint8), ctx=ctx)
-    return dicts_of(out, ks, text)
+    group_off, starts, lens, buf = pack_groups(groups)
+    ks = np.full(group_off.shape[0] - 1, k, np.int32) if np.isscalar(k) else np.asarray(k, np.int32)
+    out = count_kmers_packed(group_off, starts, lens, ks, seqs=buf, ctx=ctx)
+    return dicts_of(out, ks, buf.tobytes())
 
 
 def dicts_of(out: dict, k, text, first: int = 0, last: int | None = None) -> list[dict]:

@@ -212,3 +212,20 @@ class FakeRef:
 
     def fetch(self, contig, a, b):
         return self.seq[a:b]
+
+
+def hip_runtime():
+    """The HIP runtime the library itself is linked against (for a device buffer of a test's own)."""
+    import ctypes
+    import os
+
+    import pytest
+
+    from strkit_amd import _lib
+    _lib.load()
+    for name in ("libamdhip64.so", "libamdhip64.so.7", "libamdhip64.so.6", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "libamdhip64.so")):
+        try:
+            return ctypes.CDLL(name)
+        except OSError:
+            continue
+    pytest.fail("the HIP runtime library was not found")

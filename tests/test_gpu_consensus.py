@@ -1,14 +1,15 @@
 """GPU: strk_best_representatives (k_best_rep) against the CPU restatement (tests/consensus_restatement.py), exactly:
 index, method and distance sum of every group are integers, so there is no tolerance."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import consensus_restatement as R
+from helpers import hip_runtime
 from strkit_amd import _lib
 from strkit_amd import consensus as CS
+from strkit_amd._groups import pack_groups
 
 pytestmark = pytest.mark.gpu
 
@@ -97,17 +98,6 @@ def _corpus():
     return groups
 
 
-def _pack(groups):
-    lens = np.array([len(s) for g in groups for s in g], dtype=np.int32)
-    starts = np.zeros(lens.shape[0], np.int64)
-    if lens.shape[0]:
-        np.cumsum(lens[:-1], out=starts[1:])
-    off = np.zeros(len(groups) + 1, np.int32)
-    np.cumsum([len(g) for g in groups], out=off[1:])
-    buf = np.frombuffer(b"".join(s for g in groups for s in g), dtype=np.uint8)
-    return off, starts, lens, buf
-
-
 def _expect(groups):
     exp = [R.best_representative(g) for g in groups]
     return (np.array([e[0] for e in exp], np.int32), np.array([METHOD[e[1]] for e in exp], np.int32),
@@ -124,7 +114,7 @@ def _assert_equal(out, exp, what):
 def test_corpus_equals_restatement(gpu_ctx):
     groups = _corpus()
     assert len(groups) > 2000 and {len(g) for g in groups} >= set(range(251))
-    off, starts, lens, buf = _pack(groups)
+    off, starts, lens, buf = pack_groups(groups)
     out, stats = CS.best_representatives_packed(off, starts, lens, seqs=buf, ctx=gpu_ctx, with_stats=True)
     _assert_equal(out, _expect(groups), "corpus")
     assert stats["kernel_ms"] > 0
@@ -160,21 +150,10 @@ def test_long_groups_equal_restatement(gpu_ctx):
     groups = _long_groups()
     lens = sorted(len(s) for g in groups for s in g)
     assert lens[-1] > 3 * 4096 - 200 and any(4096 < n for n in lens)
-    off, starts, ln, buf = _pack(groups)
+    off, starts, ln, buf = pack_groups(groups)
     out = CS.best_representatives_packed(off, starts, ln, seqs=buf, ctx=gpu_ctx)
     _assert_equal(out, _expect(groups), "long")
     assert (out["method"] == CS.BEST_REP).all()
-
-
-def _hip_runtime():
-    """The HIP runtime the library itself is linked against (for a device buffer of the test's own)."""
-    _lib.load()
-    for name in ("libamdhip64.so", "libamdhip64.so.7", "libamdhip64.so.6", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "libamdhip64.so")):
-        try:
-            return C.CDLL(name)
-        except OSError:
-            continue
-    pytest.fail("the HIP runtime library was not found")
 
 
 def test_slices_host_and_device(gpu_ctx):
@@ -197,7 +176,7 @@ def test_slices_host_and_device(gpu_ctx):
     np.cumsum([len(g) for g in groups], out=off[1:])
     out = CS.best_representatives_packed(off, starts, lens, seqs=buf, ctx=gpu_ctx)
     _assert_equal(out, exp, "host slices")
-    hip = _hip_runtime()
+    hip = hip_runtime()
     dev = C.c_void_p()
     assert hip.hipSetDevice(gpu_ctx.device) == 0 and hip.hipMalloc(C.byref(dev), C.c_size_t(buf.shape[0])) == 0
     try:

@@ -1,14 +1,15 @@
 """GPU: strk_count_kmers (k_kmers_hash, k_kmers_sort) against the CPU restatement (tests/kmers_restatement.py), exactly: every
 entry's offset, count and order are integers, so there is no tolerance."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 import kmers_restatement as R
+from helpers import hip_runtime
 from strkit_amd import _lib
 from strkit_amd import kmers as KM
+from strkit_amd._groups import pack_groups
 
 pytestmark = pytest.mark.gpu
 
@@ -39,19 +40,9 @@ def _tract(rng, motif, copies, rate):
     return _mutate(rng, motif * copies, rate)
 
 
-def _pack(groups):
-    flat = [s for g in groups for s in g]
-    lens = np.array([len(s) for s in flat], np.int32)
-    starts = np.zeros(len(flat), np.int64)
-    if len(flat):
-        np.cumsum(lens[:-1], out=starts[1:])
-    group_off = np.concatenate(([0], np.cumsum([len(g) for g in groups]))).astype(np.int32)
-    return group_off, starts, lens, np.frombuffer(b"".join(flat), np.uint8)
-
-
 def _check(groups, ks, ctx, **kw):
     """Library == restatement for every group: entry offsets, first-occurrence offsets, counts, in order."""
-    group_off, starts, lens, buf = _pack(groups)
+    group_off, starts, lens, buf = pack_groups(groups)
     ks = np.asarray(ks, np.int32)
     out, st = KM.count_kmers_packed(group_off, starts, lens, ks, seqs=buf, ctx=ctx, with_stats=True, **kw)
     eo, pos, cnt = R.count_packed(group_off, starts, lens, ks, buf.tobytes())
@@ -163,17 +154,6 @@ def test_long_reads_spill_and_launch_cuts(gpu_ctx):
         assert np.array_equal(out[key], cut[key])
 
 
-def _hip_runtime():
-    """The HIP runtime the library itself is linked against (for a device buffer of the test's own)."""
-    _lib.load()
-    for name in ("libamdhip64.so", "libamdhip64.so.7", "libamdhip64.so.6", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "libamdhip64.so")):
-        try:
-            return C.CDLL(name)
-        except OSError:
-            continue
-    pytest.fail("the HIP runtime library was not found")
-
-
 def test_host_and_device_buffers_and_overlapping_slices(gpu_ctx):
     rng = np.random.default_rng(21)
     buf = np.frombuffer(_tract(rng, b"CAG", 400, 0.02) + _rand(rng, bytes(range(256)), 600), np.uint8)
@@ -188,7 +168,7 @@ def test_host_and_device_buffers_and_overlapping_slices(gpu_ctx):
     host = KM.count_kmers_packed(group_off, starts, lens, ks, seqs=buf, ctx=gpu_ctx)
     eo, pos, cnt = R.count_packed(group_off, starts, lens, ks, buf.tobytes())
     assert (host["entry_off"].tolist(), host["pos"].tolist(), host["count"].tolist()) == (eo, pos, cnt)
-    hip = _hip_runtime()
+    hip = hip_runtime()
     d = C.c_void_p()
     assert hip.hipSetDevice(gpu_ctx.device) == 0 and hip.hipMalloc(C.byref(d), C.c_size_t(buf.shape[0])) == 0
     try:
@@ -212,7 +192,7 @@ def _raw(ctx, group_off, starts, lens, ks, buf, cap, pos, cnt, fn="strk_count_km
 def test_size_query_and_retry(gpu_ctx):
     rng = np.random.default_rng(8)
     groups = [[_tract(rng, b"CAG", 30, 0.02) for _ in range(5)], [], [_rand(rng, b"ACGT", 50)]]
-    group_off, starts, lens, buf = _pack(groups)
+    group_off, starts, lens, buf = pack_groups(groups)
     ks = np.array([3, 3, 4], np.int32)
     eo_ref, pos_ref, cnt_ref = R.count_packed(group_off, starts, lens, ks, buf.tobytes())
     E = eo_ref[-1]
@@ -228,7 +208,7 @@ def test_size_query_and_retry(gpu_ctx):
 
 def test_bad_input_is_rejected_before_any_launch(gpu_ctx):
     L = _lib.load()
-    group_off, starts, lens, buf = _pack([[b"CAGCAG", b"CAG"], [b"ACGT"]])
+    group_off, starts, lens, buf = pack_groups([[b"CAGCAG", b"CAG"], [b"ACGT"]])
     ks = np.array([3, 2], np.int32)
     pos, cnt = np.zeros(16, np.int64), np.zeros(16, np.int32)
 

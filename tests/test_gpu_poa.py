@@ -2,15 +2,16 @@
 bytes of every group are integers and bytes, so there is no tolerance."""
 import ctypes as C
 import functools
-import os
 
 import numpy as np
 import pytest
 
 import consensus_restatement as BR
 import poa_restatement as P
+from helpers import hip_runtime
 from strkit_amd import _lib
 from strkit_amd import consensus as CS
+from strkit_amd._groups import pack_groups
 
 pytestmark = pytest.mark.gpu
 
@@ -23,17 +24,6 @@ SPAN = 256   # columns one pass of the workgroup covers (kPoaThreads); a string 
 
 def _rand(rng, alpha, n):
     return bytes(alpha[int(k)] for k in rng.integers(0, len(alpha), n))
-
-
-def _pack(groups):
-    lens = np.array([len(s) for g in groups for s in g], dtype=np.int32)
-    starts = np.zeros(lens.shape[0], np.int64)
-    if lens.shape[0]:
-        np.cumsum(lens[:-1], out=starts[1:])
-    off = np.zeros(len(groups) + 1, np.int32)
-    np.cumsum([len(g) for g in groups], out=off[1:])
-    buf = np.frombuffer(b"".join(s for g in groups for s in g), dtype=np.uint8)
-    return off, starts, lens, buf
 
 
 def _expect(groups, **kw):
@@ -88,7 +78,7 @@ def _corpus_expect():
 def test_hand_vectors(gpu_ctx):
     groups = [[s.encode() for s in g.split()] for g, _e, _n in VECTORS] + [list(g) for g, _e in EMPTY_VECTORS]
     want = [e.encode() for _g, e, _n in VECTORS] + [e for _g, e in EMPTY_VECTORS]
-    out = CS.consensus_packed(*_pack(groups)[:3], seqs=_pack(groups)[3], ctx=gpu_ctx)
+    out = CS.consensus_packed(*pack_groups(groups)[:3], seqs=pack_groups(groups)[3], ctx=gpu_ctx)
     off = out["seq_off"].tolist()
     text = out["seqs"].tobytes()
     assert [text[off[g]:off[g + 1]] for g in range(len(groups))] == want
@@ -104,7 +94,7 @@ def test_hand_vectors(gpu_ctx):
 def test_corpus_equals_restatement(gpu_ctx):
     groups = _corpus()
     assert len(groups) >= 150 and max(len(g) for g in groups) == 30
-    off, starts, lens, buf = _pack(groups)
+    off, starts, lens, buf = pack_groups(groups)
     out, stats = CS.consensus_packed(off, starts, lens, seqs=buf, ctx=gpu_ctx, with_stats=True)
     exp = _corpus_expect()
     _assert_equal(out, exp, "corpus")
@@ -123,7 +113,7 @@ def test_lengths_around_the_wave_and_the_workgroup_span(gpu_ctx):
         groups.append([bytes(s) for s in (hap[:L], bytes(reversed(hap[:L])), mutate(rng, hap[:L], 0.03, 0.0))])
     lens = {len(s) for g in groups for s in g}
     assert {63, 64, 65, SPAN - 2, SPAN - 1, SPAN, 2 * SPAN - 1, 2 * SPAN} <= lens   # SPAN - 1 bytes fill one pass exactly
-    _assert_equal(CS.consensus_packed(*_pack(groups)[:3], seqs=_pack(groups)[3], ctx=gpu_ctx), _expect(groups), "spans")
+    _assert_equal(CS.consensus_packed(*pack_groups(groups)[:3], seqs=pack_groups(groups)[3], ctx=gpu_ctx), _expect(groups), "spans")
 
 
 def test_graph_shapes(gpu_ctx):
@@ -145,7 +135,7 @@ def test_graph_shapes(gpu_ctx):
     long_group = [mutate(rng, hap, 0.02) for _ in range(6)]
     assert all(2000 < len(s) < 2200 for s in long_group)
     groups = [fan, ends, many, long_group]
-    out, stats = CS.consensus_packed(*_pack(groups)[:3], seqs=_pack(groups)[3], ctx=gpu_ctx, with_stats=True)
+    out, stats = CS.consensus_packed(*pack_groups(groups)[:3], seqs=pack_groups(groups)[3], ctx=gpu_ctx, with_stats=True)
     exp = _expect(groups)
     _assert_equal(out, exp, "shapes")
     assert [e[1] for e in exp] == ["poa"] * 4 and stats["n_fallback"] == 0
@@ -155,7 +145,7 @@ def test_median_rule(gpu_ctx):
     g = [b"CAGCAG", b"CAGCAT", b"CAGCAT", b"CAG", b"CAGCAGCAGC"]      # ascending 3 6 6 6 10: the median is 6
     same = [b"CAGCAGCAG"] * 3
     for mdn, method in ((6, "poa"), (5, "best_rep"), (0, "best_rep"), (5000, "poa")):
-        out, stats = CS.consensus_packed(*_pack([g, same, []])[:3], seqs=_pack([g, same, []])[3], max_mdn_poa_length=mdn,
+        out, stats = CS.consensus_packed(*pack_groups([g, same, []])[:3], seqs=pack_groups([g, same, []])[3], max_mdn_poa_length=mdn,
                                          ctx=gpu_ctx, with_stats=True)
         exp = _expect([g, same, []], max_mdn_poa_length=mdn)
         assert [e[1] for e in exp] == [method, "single", "none"]
@@ -165,7 +155,7 @@ def test_median_rule(gpu_ctx):
 
 def test_node_limit_and_launch_cutting(gpu_ctx):
     groups = list(_corpus()[:70])
-    off, starts, lens, buf = _pack(groups)
+    off, starts, lens, buf = pack_groups(groups)
     ref = CS.consensus_packed(off, starts, lens, seqs=buf, ctx=gpu_ctx)
     limit = 60
     exp = _expect(groups, node_limit=limit)
@@ -183,7 +173,7 @@ def test_node_limit_and_launch_cutting(gpu_ctx):
     rng = np.random.default_rng(8)
     hap = _rand(rng, b"ACGT", CS.MAX_POA_LEN + 1)
     edge = [[hap, hap[:-1], hap[:-1]], [hap[:-1], hap[:-2], hap[:40]], [hap, hap]]
-    o2, s2 = CS.consensus_packed(*_pack(edge)[:3], seqs=_pack(edge)[3], ctx=gpu_ctx, with_stats=True)
+    o2, s2 = CS.consensus_packed(*pack_groups(edge)[:3], seqs=pack_groups(edge)[3], ctx=gpu_ctx, with_stats=True)
     e2 = _expect(edge)
     assert [e[1] for e in e2] == ["best_rep", "poa", "single"] and e2[0][3]
     _assert_equal(o2, e2, "row limit")
@@ -194,16 +184,6 @@ def test_node_limit_and_launch_cutting(gpu_ctx):
     assert st_cut["n_sub_batches"] == n_kernel
     for key in ("index", "method", "seq_off", "seqs"):
         assert np.array_equal(cut[key], ref[key]), key
-
-
-def _hip_runtime():
-    _lib.load()
-    for name in ("libamdhip64.so", "libamdhip64.so.7", "libamdhip64.so.6", os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "libamdhip64.so")):
-        try:
-            return C.CDLL(name)
-        except OSError:
-            continue
-    pytest.fail("the HIP runtime library was not found")
 
 
 def test_slices_host_and_device_and_the_size_query(gpu_ctx):
@@ -227,7 +207,7 @@ def test_slices_host_and_device_and_the_size_query(gpu_ctx):
     _assert_equal(out, exp, "host slices")
     total = int(out["seq_off"][-1])
     assert total > 100
-    hip = _hip_runtime()
+    hip = hip_runtime()
     dev = C.c_void_p()
     assert hip.hipSetDevice(gpu_ctx.device) == 0 and hip.hipMalloc(C.byref(dev), C.c_size_t(buf.shape[0])) == 0
     try:

@@ -581,3 +581,174 @@ int main() {
     assert len(out) == len(script) + 1
     for k, ((cmd, want), got) in enumerate(zip(script, out)):
         assert got.rstrip() == want.rstrip(), (k, cmd, got, want)
+
+
+def _check_groups_restated(max_group, max_len, n_groups, n_bytes, off, starts, lens):
+    """strk_groups::check in plain Python: (rc, n_seqs, longest, sum, message); None stands for a NULL array."""
+    def bad(msg):
+        return (-22, 0, 0, 0, msg)
+    if n_groups < 0:
+        return bad("n_groups < 0")
+    if n_bytes < 0:
+        return bad("n_seq_bytes < 0")
+    if n_groups == 0:
+        return (0, 0, 0, 0, "")
+    if off is None:
+        return bad("NULL argument")
+    if off[0] != 0:
+        return bad("group_off[0] must be 0")
+    for g in range(n_groups):
+        n = off[g + 1] - off[g]
+        if n < 0:
+            return bad(f"group {g}: group_off is decreasing")
+        if n > max_group:
+            return bad(f"group {g}: {n} sequences (at most {max_group})")
+    n_seqs = off[n_groups]
+    if n_seqs > 0 and (starts is None or lens is None):
+        return bad("NULL argument")
+    for i in range(n_seqs):
+        if lens[i] < 0 or lens[i] > max_len:
+            return bad(f"sequence {i}: length {lens[i]} is outside 0..{max_len}")
+        if starts[i] < 0 or starts[i] + lens[i] > n_bytes:
+            return bad(f"sequence {i}: bytes {starts[i]}..{starts[i] + lens[i]} lie outside the {n_bytes} given")
+    lens = (lens or [])[:n_seqs]
+    return (0, n_seqs, max(lens, default=0), sum(lens), "")
+
+
+def _cut_pieces_restated(costs, budget, max_items):
+    """strk_groups::cut_piece over a whole list: in order while it fits, at least one item, at most max_items (None: no cap)."""
+    pieces, p0 = [], 0
+    while p0 < len(costs):
+        p1, used, off = p0, 0, []
+        while p1 < len(costs) and (max_items is None or p1 - p0 < max_items):
+            if p1 > p0 and used + costs[p1] > budget:
+                break
+            off.append(used)
+            used += costs[p1]
+            p1 += 1
+        pieces.append((p0, p1, used, off))
+        p0 = p1
+    return pieces
+
+
+def test_group_view_checks_and_piece_cutting_equal_their_plain_restatement(tmp_path):
+    """Host build of strk_groups.h (no HIP in it): the one check of a view of groups, and the cutting of a list into pieces by a
+    workspace bound, over scripted cases; the expectation is the plain Python restatement above."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no host C++ compiler")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    src = tmp_path / "groups_check.cpp"
+    src.write_text(r"""
+#include <cstdio>
+#include <vector>
+#include "%s/strkit_amd/csrc/strk_groups.h"
+// one command per line, one line of output per command:
+//   c max_group max_len n_groups n_seq_bytes n_off off... n_seqs start... len...   (n_off / n_seqs = -1: that array is NULL)
+//       prints rc n_seqs max_len total_len message
+//   p budget max_items n cost...    (max_items = -1: no cap)    prints every piece as "p0 p1 used off...;"
+static long long rd() {
+    long long x = 0;
+    return scanf("%%lld", &x) == 1 ? x : 0;
+}
+int main() {
+    char cmd;
+    while (scanf(" %%c", &cmd) == 1) {
+        if (cmd == 'c') {
+            const long long max_group = rd(), max_len = rd(), n_groups = rd(), n_bytes = rd(), n_off = rd();
+            // arrays of exactly the size given, so that a read past an end is one a sanitizer build sees
+            std::vector<int32_t> off(n_off < 0 ? 0 : (size_t)n_off);
+            for (auto& o : off) o = (int32_t)rd();
+            const long long n_seqs = rd();
+            std::vector<int64_t> start(n_seqs < 0 ? 0 : (size_t)n_seqs);
+            std::vector<int32_t> len(start.size());
+            for (auto& x : start) x = rd();
+            for (auto& x : len) x = (int32_t)rd();
+            strk_groups::View v{(int32_t)n_groups, n_off < 0 ? nullptr : off.data(), n_bytes, n_seqs < 0 ? nullptr : start.data(),
+                                n_seqs < 0 ? nullptr : len.data()};
+            strk_groups::Totals t;
+            strk_groups::Message m;
+            m.text[0] = 0;
+            const int rc = strk_groups::check(v, (int)max_group, (int)max_len, &t, &m);
+            printf("%%d %%d %%d %%lld %%s\n", rc, t.n_seqs, t.max_len, (long long)t.total_len, rc ? m.text : "");
+        } else if (cmd == 'p') {
+            const long long budget = rd(), max_items = rd(), n = rd();
+            std::vector<int64_t> cost((size_t)n), off;
+            for (auto& x : cost) x = rd();
+            for (size_t p0 = 0, p1; p0 < cost.size(); p0 = p1) {
+                int64_t used = -1;
+                p1 = strk_groups::cut_piece(p0, cost.size(), [&](size_t p) { return cost[p]; }, budget,
+                                            max_items < 0 ? strk_groups::kNoItemCap : (size_t)max_items, off, &used);
+                printf("%%zu %%zu %%lld", p0, p1, (long long)used);
+                for (int64_t o : off) printf(" %%lld", (long long)o);
+                printf(";");
+            }
+            printf("\n");
+        }
+    }
+    return 0;
+}
+""" % root)
+    exe = tmp_path / "groups_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), str(src)], check=True)
+    script = []            # (command, expected output line)
+
+    def view(n_groups, n_bytes, off, starts, lens, max_group=250, max_len=65535):
+        cmd = [max_group, max_len, n_groups, n_bytes, -1 if off is None else len(off), *(off or []),
+               -1 if starts is None else len(starts), *(starts or []), *(lens or [])]
+        rc, n_seqs, longest, total, msg = _check_groups_restated(max_group, max_len, n_groups, n_bytes, off, starts, lens)
+        script.append(("c " + " ".join(str(x) for x in cmd), f"{rc} {n_seqs} {longest} {total} {msg}".rstrip()))
+        return rc, n_seqs, longest, total
+
+    assert view(3, 20, [0, 2, 2, 5], [0, 3, 9, 9, 15], [3, 6, 0, 6, 5]) == (0, 5, 6, 20)     # a good view, slices end to end
+    assert view(0, 0, None, None, None) == (0, 0, 0, 0)                                      # no groups: nothing is looked at
+    assert view(0, 7, [5], [-1], [-1]) == (0, 0, 0, 0)
+    assert view(-1, 0, [0], [], [])[0] == -22
+    assert view(1, -1, [0, 0], [], [])[0] == -22
+    assert view(2, 9, None, [0], [1])[0] == -22                                              # NULL group_off
+    assert view(2, 9, [1, 2, 3], [0, 1, 2], [1, 1, 1])[0] == -22                             # group_off[0] != 0
+    assert view(3, 9, [0, 2, 1, 3], [0, 1, 2], [1, 1, 1])[0] == -22                          # decreasing offsets
+    assert view(1, 300, [0, 251], [0] * 251, [1] * 251)[0] == -22                            # a group of 251
+    assert view(1, 300, [0, 250], [0] * 250, [1] * 250) == (0, 250, 1, 250)                  # ... and of 250
+    assert view(2, 9, [0, 1, 4], [0, 0, 0, 0], [3, 3, 3, 3], max_group=2)[0] == -22          # the limit is the caller's
+    assert view(1, 9, [0, 1], [0], [-1])[0] == -22                                           # a length of -1
+    assert view(1, 70000, [0, 1], [0], [65536])[0] == -22                                    # ... of 65 536
+    assert view(1, 70000, [0, 1], [0], [65535]) == (0, 1, 65535, 65535)                      # ... of 65 535
+    assert view(1, 70000, [0, 1], [0], [4097], max_len=4096)[0] == -22
+    assert view(1, 9, [0, 1], [-1], [3])[0] == -22                                           # a start of -1
+    assert view(2, 9, [0, 1, 2], [0, 7], [3, 3])[0] == -22                                   # one byte past n_seq_bytes
+    assert view(2, 9, [0, 1, 2], [0, 6], [3, 3]) == (0, 2, 3, 6)                             # ending exactly at it
+    assert view(1, 0, [0, 2], [0, 0], [0, 0]) == (0, 2, 0, 0)                                # empty strings of an empty buffer
+    assert view(1, 0, [0, 1], [1], [0])[0] == -22
+    assert view(1, 2 ** 40, [0, 1], [2 ** 40 - 5], [5]) == (0, 1, 5, 5)                      # 64-bit offsets
+    assert view(1, 2 ** 40, [0, 1], [2 ** 62], [5])[0] == -22
+    assert view(1, 9, [0, 2], None, None)[0] == -22                                          # NULL seq_start, sequences present
+    assert view(2, 9, [0, 0, 0], None, None) == (0, 0, 0, 0)                                 # ... and none present
+    assert view(5, 9, [0, 0, 2, 2, 2, 3], [0, 2, 4], [2, 2, 5]) == (0, 3, 5, 9)              # empty groups between full ones
+    assert len({want.split(" ", 4)[-1] for _c, want in script if want.startswith("-22")}) >= 10   # every refusal has its own text
+
+    def cut(costs, budget, max_items=None):
+        pieces = _cut_pieces_restated(costs, budget, max_items)
+        script.append((f"p {budget} {-1 if max_items is None else max_items} {len(costs)} " + " ".join(str(c) for c in costs),
+                       "".join(" ".join(str(x) for x in (p0, p1, used, *off)) + ";" for p0, p1, used, off in pieces)))
+        return [(p0, p1) for p0, p1, _u, _o in pieces]
+
+    assert cut([9, 8, 7, 100], 5) == [(0, 1), (1, 2), (2, 3), (3, 4)]                        # every item beyond the budget: alone
+    assert cut([1, 2, 3, 4], 10) == [(0, 4)]                                                 # everything fits (exactly)
+    assert cut([1, 2, 3, 4], 9) == [(0, 3), (3, 4)]
+    assert cut([1] * 10, 100, 4) == [(0, 4), (4, 8), (8, 10)]                                # the item cap binds before the budget
+    assert cut([1] * 10, 3, 4) == [(0, 3), (3, 6), (6, 9), (9, 10)]                          # ... and the budget before the cap
+    assert cut([], 10) == [] and cut([], 10, 3) == []                                        # an empty range: no piece
+    assert cut([0, 0, 50, 0, 60, 0], 100, 3) == [(0, 3), (3, 6)]                             # items that cost nothing
+    assert cut([4, 100, 4, 4, 100, 100, 1], 8) == [(0, 1), (1, 2), (2, 4), (4, 5), (5, 6), (6, 7)]
+    assert cut([2 ** 40, 2 ** 40, 1], 2 ** 41) == [(0, 2), (2, 3)]                           # 64-bit sums
+    assert _cut_pieces_restated([5, 6, 7], 18, None) == [(0, 3, 18, [0, 5, 11])]             # offsets are the running sums
+    assert cut([5, 6, 7, 9, 2], 18, 4) == [(0, 3), (3, 5)] and script[-1][1] == "0 3 18 0 5 11;3 5 11 0 9;"   # ... the program's too
+
+    commands = tmp_path / "groups_check.in"      # (a file, so that the same run can be repeated by hand under a sanitizer build)
+    commands.write_text("\n".join(c for c, _ in script) + "\n")
+    out = subprocess.run([str(exe)], stdin=commands.open(), check=True, capture_output=True, text=True).stdout.split("\n")
+    assert len(out) == len(script) + 1
+    for k, ((cmd, want), got) in enumerate(zip(script, out)):
+        assert got.rstrip() == want.rstrip(), (k, cmd[:80], got, want)

@@ -19,6 +19,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from strkit_amd import _lib  # noqa: E402
+from strkit_amd._groups import pack_groups  # noqa: E402
 from strkit_amd.consensus import best_representatives_packed  # noqa: E402
 
 _A = np.frombuffer(b"ACGT", np.uint8)
@@ -38,22 +39,13 @@ def _read(rng, hap: np.ndarray, rate: float) -> np.ndarray:
 
 def make_groups(n_groups: int, n_reads: int, lo: int, hi: int, rate: float, seed: int = 1):
     rng = np.random.default_rng(seed)
-    parts, lens = [], []
+    groups = []
     for _ in range(n_groups):
         hap = _A[rng.integers(0, 4, int(rng.integers(lo, hi + 1)))]
-        for _ in range(n_reads):
-            r = _read(rng, hap, rate)
-            parts.append(r)
-            lens.append(r.shape[0])
-    lens = np.array(lens, np.int32)
-    starts = np.concatenate(([0], np.cumsum(lens[:-1], dtype=np.int64))).astype(np.int64)
-    off = (np.arange(n_groups + 1) * n_reads).astype(np.int32)
+        groups.append([_read(rng, hap, rate) for _ in range(n_reads)])
     # cells: all pairs, and the pairs of distinct strings
     all_cells = distinct_cells = 0
-    k = 0
-    for _ in range(n_groups):
-        g = parts[k:k + n_reads]
-        k += n_reads
+    for g in groups:
         ln = np.array([x.shape[0] for x in g], np.int64)
         all_cells += int((ln.sum() ** 2 - (ln ** 2).sum()) // 2)
         seen = {}
@@ -61,7 +53,7 @@ def make_groups(n_groups: int, n_reads: int, lo: int, hi: int, rate: float, seed
             seen.setdefault(x.tobytes(), x.shape[0])
         u = np.array(list(seen.values()), np.int64)
         distinct_cells += int((u.sum() ** 2 - (u ** 2).sum()) // 2)
-    return (off, starts, lens, np.concatenate(parts)), all_cells, distinct_cells
+    return pack_groups(groups), all_cells, distinct_cells
 
 
 def run(label: str, data, all_cells: int, distinct_cells: int, reps: int, ctx) -> None:

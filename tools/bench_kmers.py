@@ -25,6 +25,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import kmers_restatement as R  # noqa: E402
 from strkit_amd import _lib  # noqa: E402
+from strkit_amd._groups import pack_groups  # noqa: E402
 from strkit_amd.kmers import count_kmers_packed  # noqa: E402
 
 _A = np.frombuffer(b"ACGT", np.uint8)
@@ -45,20 +46,15 @@ def _read(rng, hap: np.ndarray, rate: float) -> np.ndarray:
 def make_groups(n_groups: int, n_reads: int, lo: int, hi: int, rate: float, k_lo: int, k_hi: int, motif_len=None, seed: int = 1):
     """Groups of n_reads reads of one tract (a random motif of k bases, or of motif_len, repeated to lo..hi bases) each."""
     rng = np.random.default_rng(seed)
-    parts, lens = [], []
+    groups = []
     ks = rng.integers(k_lo, k_hi + 1, n_groups).astype(np.int32)
     for g in range(n_groups):
         m = int(motif_len or ks[g])
         length = int(rng.integers(lo, hi + 1))
         hap = np.tile(_A[rng.integers(0, 4, m)], length // m + 1)[:length]
-        for _ in range(n_reads):
-            r = _read(rng, hap, rate)
-            parts.append(r)
-            lens.append(r.shape[0])
-    lens = np.array(lens, np.int32)
-    starts = np.concatenate(([0], np.cumsum(lens[:-1], dtype=np.int64))).astype(np.int64)
-    off = (np.arange(n_groups + 1) * n_reads).astype(np.int32)
-    return off, starts, lens, ks, np.concatenate(parts)
+        groups.append([_read(rng, hap, rate) for _ in range(n_reads)])
+    off, starts, lens, buf = pack_groups(groups)
+    return off, starts, lens, ks, buf
 
 
 def run(label: str, data, reps: int, cpu_windows: int, ctx) -> None:
