@@ -302,6 +302,66 @@ int strk_call_alleles(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off /*[
                       int32_t* out_ci99 /*[4n]*/, double* out_means, double* out_weights, double* out_stdevs /*[2n]*/,
                       int32_t* out_peak_n_reads /*[2n]*/, int32_t* out_read_peak /*[n_reads], -1 = none*/, strk_stats* stats);
 
+/* ---- phased allele calls: reads grouped by haplotags or by SNVs -------------------------------------------------------
+ * Stands where the reference separates the reads of a locus before it calls alleles (call_locus.py:1381-1495):
+ * call_alleles_with_haplotags (:222-288) for reads that carry HP / PS tags, else call_alleles_with_incorporated_snvs
+ * (:457-714) for reads that carry useful SNVs, clustered by calculate_read_distance (:91-174) and average linkage cut at
+ * two clusters, then call_and_filter_useful_snvs (snvs.py:63-171).  Every group is called as a single-allele locus by the
+ * rule of strk_call_alleles (min_reads = min_allele_reads, weights renormalised inside the group, seed
+ * mix64(seed[l] + 0x9E3779B97F4A7C15 * (g + 1)) for group g).  The whole rule: DESIGN.md §13.
+ * Defaults (the reference's): min_hp_read_coverage 8, snv_quality_threshold 20, many_snvs_quantity 3, cn_weight_few 0.2,
+ * cn_weight_many 0.1.  piece_loci and ws_budget (loci and workspace bytes of one piece of the call) are the library's
+ * when 0; the result does not depend on them. */
+typedef struct strk_phase_params {
+    int32_t min_hp_read_coverage, snv_quality_threshold, many_snvs_quantity, piece_loci;
+    double cn_weight_few, cn_weight_many;
+    int64_t ws_budget;
+} strk_phase_params;
+
+#define STRK_ALLELE_NOT_PHASED 3 /* out_status of a locus with enough reads and STRK_ASSIGN_NONE: call it with strk_call_alleles */
+
+#define STRK_ASSIGN_NONE 0       /* no phased call (the reference falls through to `dist` / `single`) */
+#define STRK_ASSIGN_HP 1         /* `hp` */
+#define STRK_ASSIGN_SNV 2        /* `snv`: SNVs alone */
+#define STRK_ASSIGN_SNV_DIST 3   /* `snv+dist`: SNVs and the copy-number difference */
+
+/* out_reason of a locus with STRK_ASSIGN_NONE (0 otherwise, and when the locus has fewer than min_reads reads) */
+#define STRK_PHASE_NO_TAGS 1            /* no tags given, and no SNV step possible (one allele, or no SNV) */
+#define STRK_PHASE_TAG_THRESHOLDS 2     /* tagged reads, distinct HP values or the top phase set miss their thresholds */
+#define STRK_PHASE_FEW_SNV_READS 3      /* too few reads carry a real SNV base */
+#define STRK_PHASE_GROUP_NOT_CALLED 4   /* a group has fewer than min_allele_reads reads */
+#define STRK_PHASE_NO_SNV_CALLED 5      /* no SNV survived the SNV calls */
+
+/* out_snv_status */
+#define STRK_SNV_NOT_EVALUATED (-1)     /* the locus was not grouped by SNVs */
+#define STRK_SNV_CALLED 0
+#define STRK_SNV_ZERO_TOTAL 1           /* a peak has no cell that counts */
+#define STRK_SNV_ONLY_OUT_OF_RANGE 2    /* '-' is a peak's only byte */
+#define STRK_SNV_CROSS_TALK 3           /* the other peak carries a peak's byte too often */
+#define STRK_SNV_SAME_BASE 4            /* both peaks call the same byte */
+
+/* Inputs as strk_call_alleles, with at most 1 024 reads per locus, and optionally
+ *   hp, ps [n_reads]       the reads' haplotag and (already remapped) phase set, -1 = untagged; both NULL or both given;
+ *   snv_off [n_loci+1]     locus l has S_l = snv_off[l+1] - snv_off[l] useful SNVs (at most 64); its cells, one base byte and
+ *   snv_base, snv_qual     one quality byte per read and SNV, read-major, start at the sum of reads x SNVs of the loci before
+ *                          it; n_snv_cells bytes each.  Bases are raw ASCII, '-' out of range, '_' a gap.  All NULL together.
+ * Outputs: those of strk_call_alleles in the same layout (a phased call has out_modal_n = the number of groups, weights
+ * 1 / groups, out_peak_n_reads the group sizes; peaks in ascending HP order for STRK_ASSIGN_HP, by (mean, low end of the 95 %
+ * interval) for the SNV methods; a read outside every group has peak -1), then per locus out_method, out_reason, out_ps (the
+ * top phase set for STRK_ASSIGN_HP, else -1), and per SNV out_snv_status, out_snv_call[2s + peak] (bytes),
+ * out_snv_rcs[2s + peak] (reads that carry the called byte).  The SNV outputs may be NULL when snv_off is.  A locus without a
+ * phased call has the outputs of a locus with too few reads and out_status STRK_ALLELE_NOT_PHASED.  All buffers are host
+ * buffers; every input is checked before the first launch.  stats (optional) receives kernel_ms. */
+int strk_call_alleles_phased(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off /*[n_loci+1]*/, const int32_t* cn, const double* w,
+                             const int32_t* n_alleles, const uint64_t* seed, const strk_allele_params* p, const strk_phase_params* pp,
+                             const int32_t* hp, const int32_t* ps, const int32_t* snv_off /*[n_loci+1]*/, const uint8_t* snv_base,
+                             const uint8_t* snv_qual, int64_t n_snv_cells,
+                             int32_t* out_status, int32_t* out_modal_n, int32_t* out_call /*[2n]*/, int32_t* out_ci95 /*[4n]*/,
+                             int32_t* out_ci99 /*[4n]*/, double* out_means, double* out_weights, double* out_stdevs /*[2n]*/,
+                             int32_t* out_peak_n_reads /*[2n]*/, int32_t* out_read_peak /*[n_reads]*/, int32_t* out_method,
+                             int32_t* out_reason, int32_t* out_ps, int32_t* out_snv_status, uint8_t* out_snv_call /*[2 n_snvs]*/,
+                             int32_t* out_snv_rcs /*[2 n_snvs]*/, strk_stats* stats);
+
 /* ---- best representative of a group of sequences ------------------------------------------------------------------
  * Stands where the reference calls strkit_rust_ext.consensus_seq (call_locus.py:1602-1613) for the methods `single` and
  * `best_rep`; partial-order alignment is strk_consensus, below.  A group is an ordered list of byte strings.  No string: index -1,

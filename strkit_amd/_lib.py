@@ -42,6 +42,12 @@ class StrkAlleleParams(C.Structure):
                 ("expansion_ratio", C.c_double)]
 
 
+class StrkPhaseParams(C.Structure):
+    _fields_ = [("min_hp_read_coverage", C.c_int32), ("snv_quality_threshold", C.c_int32), ("many_snvs_quantity", C.c_int32),
+                ("piece_loci", C.c_int32), ("cn_weight_few", C.c_double), ("cn_weight_many", C.c_double),
+                ("ws_budget", C.c_int64)]
+
+
 class StrkStats(C.Structure):
     _fields_ = [("dp_cells", C.c_int64), ("n_fallback", C.c_int32), ("n_miss_reads", C.c_int32),
                 ("n_miss_rounds", C.c_int32), ("kernel_ms", C.c_float), ("dp_kernel_ms", C.c_float),
@@ -65,6 +71,7 @@ EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk
            "strk_extract_reads", "strk_bgzf_inflate", "strk_bgzf_inflate_range", "strk_bam_names", "strk_bam_scan_piece",
            "strk_dbam_open", "strk_dbam_close", "strk_dbam_release_cache", "strk_dbam_inflate", "strk_dbam_inflate_file", "strk_dbam_inflate_file_range", "strk_dbam_file_ms", "strk_dbam_download", "strk_dbam_data", "strk_bgzf_inflate_sw",
            "strk_dbam_download_seqs", "strk_dbam_kernel_ms", "strk_dbam_voffsets", "strk_dbam_scan", "strk_dbam_extract", "strk_dbam_names", "strk_count_loci_dseqs", "strk_read_coords_both", "strk_call_alleles",
+           "strk_call_alleles_phased",
            "strk_best_representatives", "strk_best_representatives_dseqs",
            "strk_count_kmers", "strk_count_kmers_dseqs", "strk_count_kmers_ws",
            "strk_consensus", "strk_consensus_dseqs", "strk_consensus_ws")
@@ -193,6 +200,10 @@ def load(build: bool = True):
         L.strk_call_alleles.restype = C.c_int
         L.strk_call_alleles.argtypes = ([C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(StrkAlleleParams)]
                                         + [C.c_void_p] * 10 + [C.POINTER(StrkStats)])
+        L.strk_call_alleles_phased.restype = C.c_int
+        L.strk_call_alleles_phased.argtypes = ([C.c_void_p, C.c_int32] + [C.c_void_p] * 5
+                                               + [C.POINTER(StrkAlleleParams), C.POINTER(StrkPhaseParams)] + [C.c_void_p] * 5
+                                               + [C.c_int64] + [C.c_void_p] * 16 + [C.POINTER(StrkStats)])
         for f in (L.strk_best_representatives, L.strk_best_representatives_dseqs):
             f.restype = C.c_int
             f.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(StrkStats)]

@@ -7,7 +7,7 @@
 //   strk_host_miss.inc       window-miss rounds                       strk_host_pipe.inc       the pinned-slot host pipeline
 //   strk_host_ref.inc        reference side                           strk_host_realign.inc    realignment
 //   strk_host_alleles.inc    allele calling                           strk_host_consensus.inc  best representatives
-//   strk_host_kmers.inc      distinct windows (k-mer counts)
+//   strk_host_kmers.inc      distinct windows (k-mer counts)                 strk_host_phase.inc      phased allele calls
 //   strk_host_files.inc      the CPU-only file front end (its parser: strk_frontend.h)
 //   strk_dbam.inc            (at the end) the alignment file on the device: BGZF inflater, record scan, read extraction
 //
@@ -20,6 +20,7 @@
 #include "strk_host.h"
 #include "strk_policy.h"
 #include "strk_groups.h"
+#include "strk_phase_check.h"
 
 #include <algorithm>
 #include <array>
@@ -43,6 +44,7 @@
 #include "strk_frontend.h"
 #include "strk_inflate.h"
 #include "strk_alleles.h"
+#include "strk_phase.h"
 #include "strk_consensus.h"
 #include "strk_kmers.h"
 #include "strk_poa.h"
@@ -145,6 +147,8 @@ struct strk_ctx {
     Stream side;
     // allele calling (strk_call_alleles)
     DevBuf al_off, al_cn, al_w, al_meta, al_ws, al_out, al_rp;
+    // phased allele calls (strk_call_alleles_phased): what goes up, what the kernels hand each other, the workspaces, what comes down
+    DevBuf ph_in, ph_mid, ph_ws, ph_out;
     // best representatives (strk_best_representatives)
     GroupStage cs_in;
     DevBuf cs_bound, cs_out;
@@ -793,7 +797,7 @@ int score_table_impl(strk_ctx* ctx, const strk_batch* batch, const int32_t* lo, 
 
 #include "strk_host_realign.inc"
 
-// The stream of strk_call_alleles, strk_best_representatives, strk_count_kmers and strk_consensus (strk_ctx::side).
+// The stream of strk_call_alleles, strk_call_alleles_phased, strk_best_representatives, strk_count_kmers and strk_consensus (strk_ctx::side).
 int side_stream(strk_ctx* c, hipStream_t* st) {
     if (!c->side) HIP_TRY(hipStreamCreateWithFlags(&c->side.h, hipStreamNonBlocking));
     *st = c->side;
@@ -838,6 +842,7 @@ int check_dseqs(strk_ctx* c, const char* fn, const void* d_seqs) {
 }
 
 #include "strk_host_alleles.inc"
+#include "strk_host_phase.inc"
 #include "strk_host_consensus.inc"
 #include "strk_host_kmers.inc"
 #include "strk_host_poa.inc"
@@ -1066,6 +1071,31 @@ int strk_call_alleles(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off, co
     static_assert(STRK_ALLELE_CALLED == 0 && STRK_ALLELE_TOO_FEW == 1 && STRK_ALLELE_EMPTY_PEAK == 2, "include/strkit_amd.h <-> strk_alleles.h");
     return call_alleles_impl(ctx, n_loci, read_off, cn, w, n_alleles, seed, p, out_status, out_modal_n, out_call, out_ci95,
                              out_ci99, out_means, out_weights, out_stdevs, out_peak_n_reads, out_read_peak, stats);
+}
+
+int strk_call_alleles_phased(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off, const int32_t* cn, const double* w,
+                             const int32_t* n_alleles, const uint64_t* seed, const strk_allele_params* p, const strk_phase_params* pp,
+                             const int32_t* hp, const int32_t* ps, const int32_t* snv_off, const uint8_t* snv_base,
+                             const uint8_t* snv_qual, int64_t n_snv_cells, int32_t* out_status, int32_t* out_modal_n, int32_t* out_call,
+                             int32_t* out_ci95, int32_t* out_ci99, double* out_means, double* out_weights, double* out_stdevs,
+                             int32_t* out_peak_n_reads, int32_t* out_read_peak, int32_t* out_method, int32_t* out_reason,
+                             int32_t* out_ps, int32_t* out_snv_status, uint8_t* out_snv_call, int32_t* out_snv_rcs, strk_stats* stats) {
+    const char* fn = "strk_call_alleles_phased";
+    if (!ctx) return fail(STRK_E_INVALID, "%s: ctx is NULL", fn);
+    if (ctx->pending) return fail(STRK_E_INVALID, "%s: a submitted call is pending on this context", fn);
+    static_assert(STRK_ALLELE_NOT_PHASED == kStatusNotPhased && STRK_ALLELE_TOO_FEW == kStatusTooFew, "include/strkit_amd.h <-> strk_phase.h");
+    static_assert(STRK_ASSIGN_NONE == kAssignNone && STRK_ASSIGN_HP == kAssignHp && STRK_ASSIGN_SNV == kAssignSnv &&
+                  STRK_ASSIGN_SNV_DIST == kAssignSnvDist, "include/strkit_amd.h <-> strk_phase.h");
+    static_assert(STRK_PHASE_NO_TAGS == kReasonNoTags && STRK_PHASE_TAG_THRESHOLDS == kReasonTagThresholds &&
+                  STRK_PHASE_FEW_SNV_READS == kReasonFewSnvReads && STRK_PHASE_GROUP_NOT_CALLED == kReasonGroupNotCalled &&
+                  STRK_PHASE_NO_SNV_CALLED == kReasonNoSnvCalled, "include/strkit_amd.h <-> strk_phase.h");
+    static_assert(STRK_SNV_NOT_EVALUATED == kSnvNotEvaluated && STRK_SNV_CALLED == kSnvCalled && STRK_SNV_ZERO_TOTAL == kSnvZeroTotal &&
+                  STRK_SNV_ONLY_OUT_OF_RANGE == kSnvOnlyOutOfRange && STRK_SNV_CROSS_TALK == kSnvCrossTalk &&
+                  STRK_SNV_SAME_BASE == kSnvSameBase, "include/strkit_amd.h <-> strk_phase.h");
+    const strk_phase_check::Input in{n_loci, read_off, cn, w, n_alleles, seed, p, pp, hp, ps, snv_off, n_snv_cells, snv_base, snv_qual};
+    const PhaseOut out{out_status, out_modal_n, out_call, out_ci95, out_ci99, out_means, out_weights, out_stdevs, out_peak_n_reads,
+                       out_read_peak, out_method, out_reason, out_ps, out_snv_status, out_snv_call, out_snv_rcs};
+    return call_alleles_phased_impl(ctx, fn, in, out, stats);
 }
 
 int strk_best_representatives(strk_ctx* ctx, int32_t n_groups, const int32_t* group_off, const uint8_t* seqs, int64_t n_seq_bytes,

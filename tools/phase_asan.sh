@@ -1,0 +1,7 @@
+#!/bin/bash
+# The input checks and the piece cutting of strk_call_alleles_phased under AddressSanitizer + UBSan on the host (no GPU needed).
+set -e
+D=${TMPDIR:-/tmp}/strk_phase_asan
+mkdir -p $D
+g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $D/phase_asan tools/phase_asan.cpp
+$D/phase_asan
