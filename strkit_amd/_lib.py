@@ -258,6 +258,11 @@ def host_is_pinned(arr) -> bool:
     return bool(arr.nbytes) and bool(load().strk_host_is_pinned(C.c_void_p(arr.ctypes.data), arr.nbytes))
 
 
+def ptr(a) -> C.c_void_p | None:
+    """The address of a numpy array as a pointer argument of the C ABI; None (NULL) for None."""
+    return None if a is None else C.c_void_p(a.ctypes.data)
+
+
 def check(rc: int) -> None:
     if rc != 0:
         raise StrkError(rc, load().strk_last_error().decode("utf-8", "replace"))

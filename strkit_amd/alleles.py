@@ -12,6 +12,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 
 CALLED, TOO_FEW, EMPTY_PEAK = 0, 1, 2
 ASSIGN_SINGLE, ASSIGN_DIST = "single", "dist"
@@ -65,8 +66,30 @@ def locus_seeds(seed: int, t_idx) -> np.ndarray:
         return z ^ (z >> np.uint64(31))
 
 
-def _ptr(a: np.ndarray) -> C.c_void_p:
-    return C.c_void_p(a.ctypes.data)
+ALLELE_KEYS = ("status", "modal_n", "call", "ci95", "ci99", "means", "weights", "stdevs", "peak_n_reads")   # per locus, in C order
+
+
+def batch_inputs(read_off, cns, weights, n_alleles, seeds):
+    """The five inputs of a batched allele call as contiguous arrays of the C types, n_alleles and seeds broadcast to one
+    entry per locus: (read_off, cns, weights, n_alleles, seeds, n_loci).  read_off must span cns."""
+    read_off = np.ascontiguousarray(read_off, dtype=np.int32)
+    cns = np.ascontiguousarray(cns, dtype=np.int32)
+    weights = np.ascontiguousarray(weights, dtype=np.float64)
+    n_loci = read_off.shape[0] - 1
+    if n_loci < 0 or cns.shape != weights.shape or int(read_off[-1]) != cns.shape[0]:
+        raise ValueError("read_off must span cns, and cns and weights must have one entry per read")
+    n_alleles = np.ascontiguousarray(np.broadcast_to(np.asarray(n_alleles, dtype=np.int32), (n_loci,)))
+    seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (n_loci,)))
+    return read_off, cns, weights, n_alleles, seeds, n_loci
+
+
+def batch_outputs(n_loci: int, n_reads: int) -> dict:
+    """The arrays a batched allele call fills: ALLELE_KEYS per locus and read_peak per read."""
+    return dict(status=np.empty(n_loci, np.int32), modal_n=np.empty(n_loci, np.int32),
+                call=np.empty((n_loci, 2), np.int32), ci95=np.empty((n_loci, 2, 2), np.int32),
+                ci99=np.empty((n_loci, 2, 2), np.int32), means=np.empty((n_loci, 2)),
+                weights=np.empty((n_loci, 2)), stdevs=np.empty((n_loci, 2)),
+                peak_n_reads=np.empty((n_loci, 2), np.int32), read_peak=np.empty(n_reads, np.int32))
 
 
 def call_alleles_batch(read_off, cns, weights, n_alleles, seeds, params: AlleleParams | None = None, ctx=None,
@@ -76,25 +99,13 @@ def call_alleles_batch(read_off, cns, weights, n_alleles, seeds, params: AlleleP
     read_peak [n_reads] (-1: no call).  Slot 1 of a one-allele locus is -1 / NaN."""
     params = params or AlleleParams()
     ctx = ctx or _lib.default_context()
-    read_off = np.ascontiguousarray(read_off, dtype=np.int32)
-    cns = np.ascontiguousarray(cns, dtype=np.int32)
-    weights = np.ascontiguousarray(weights, dtype=np.float64)
-    n_loci = read_off.shape[0] - 1
-    n_alleles = np.ascontiguousarray(np.broadcast_to(np.asarray(n_alleles, dtype=np.int32), (n_loci,)))
-    seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (n_loci,)))
-    if n_loci < 0 or cns.shape != weights.shape or (n_loci >= 0 and int(read_off[-1]) != cns.shape[0]):
-        raise ValueError("read_off must span cns, and cns and weights must have one entry per read")
-    out = dict(status=np.empty(n_loci, np.int32), modal_n=np.empty(n_loci, np.int32),
-               call=np.empty((n_loci, 2), np.int32), ci95=np.empty((n_loci, 2, 2), np.int32),
-               ci99=np.empty((n_loci, 2, 2), np.int32), means=np.empty((n_loci, 2)),
-               weights=np.empty((n_loci, 2)), stdevs=np.empty((n_loci, 2)),
-               peak_n_reads=np.empty((n_loci, 2), np.int32), read_peak=np.empty(cns.shape[0], np.int32))
+    read_off, cns, weights, n_alleles, seeds, n_loci = batch_inputs(read_off, cns, weights, n_alleles, seeds)
+    out = batch_outputs(n_loci, cns.shape[0])
     cp = params._c()
     st = _lib.StrkStats()
     _lib.check(_lib.load().strk_call_alleles(
-        ctx.handle, n_loci, _ptr(read_off), _ptr(cns), _ptr(weights), _ptr(n_alleles), _ptr(seeds), C.byref(cp),
-        *[_ptr(out[k]) for k in ("status", "modal_n", "call", "ci95", "ci99", "means", "weights", "stdevs",
-                                  "peak_n_reads", "read_peak")], C.byref(st)))
+        ctx.handle, n_loci, *map(ptr, (read_off, cns, weights, n_alleles, seeds)), C.byref(cp),
+        *[ptr(out[k]) for k in (*ALLELE_KEYS, "read_peak")], C.byref(st)))
     if with_stats:
         return out, st.as_dict()
     return out

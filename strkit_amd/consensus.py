@@ -15,6 +15,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from ._groups import group_args, pack_groups
 
 NONE, SINGLE, BEST_REP = 0, 1, 2
@@ -24,10 +25,6 @@ MAX_POA_LEN = 4096       # a group with a longer string is not taken by POA
 MAX_POA_NODES = 16384    # nor one whose graph grows beyond this
 MAX_GROUP = 250
 MAX_LEN = 65535
-
-
-def _ptr(a: np.ndarray) -> C.c_void_p:
-    return C.c_void_p(a.ctypes.data)
 
 
 def best_representatives_packed(group_off, seq_start, seq_len, seqs=None, d_seqs=None, n_seq_bytes: int | None = None,
@@ -43,11 +40,11 @@ def best_representatives_packed(group_off, seq_start, seq_len, seqs=None, d_seqs
                dist_sum=np.empty(n_groups, np.int64))
     st = _lib.StrkStats()
     L = _lib.load()
-    tail = (n, _ptr(seq_start), _ptr(seq_len), _ptr(out["index"]), _ptr(out["method"]), _ptr(out["dist_sum"]), C.byref(st))
+    tail = (n, ptr(seq_start), ptr(seq_len), ptr(out["index"]), ptr(out["method"]), ptr(out["dist_sum"]), C.byref(st))
     if d_seqs is None:
-        _lib.check(L.strk_best_representatives(ctx.handle, n_groups, _ptr(group_off), h_ptr, *tail))
+        _lib.check(L.strk_best_representatives(ctx.handle, n_groups, ptr(group_off), h_ptr, *tail))
     else:
-        _lib.check(L.strk_best_representatives_dseqs(ctx.handle, n_groups, _ptr(group_off), d_ptr, *tail))
+        _lib.check(L.strk_best_representatives_dseqs(ctx.handle, n_groups, ptr(group_off), d_ptr, *tail))
     if with_stats:
         return out, st.as_dict()
     return out
@@ -84,9 +81,9 @@ def consensus_packed(group_off, seq_start, seq_len, seqs=None, d_seqs=None, n_se
     L = _lib.load()
 
     def call(cap_, arr):
-        rc = L.strk_consensus_ws(ctx.handle, n_groups, _ptr(group_off), h_ptr, d_ptr, n, _ptr(seq_start), _ptr(seq_len),
-                                 int(max_mdn_poa_length), int(cap_), _ptr(out["index"]), _ptr(out["method"]), _ptr(out["seq_off"]),
-                                 _ptr(arr) if arr is not None else None, int(node_limit), int(workspace_bytes), C.byref(st))
+        rc = L.strk_consensus_ws(ctx.handle, n_groups, ptr(group_off), h_ptr, d_ptr, n, ptr(seq_start), ptr(seq_len),
+                                 int(max_mdn_poa_length), int(cap_), ptr(out["index"]), ptr(out["method"]), ptr(out["seq_off"]),
+                                 ptr(arr), int(node_limit), int(workspace_bytes), C.byref(st))
         if rc < 0:
             _lib.check(int(rc))
         return int(rc)

@@ -3,6 +3,7 @@
 //   strk_host.h     the calling thread's error message (fail, HIP_TRY) and the owning types: DevBuf, PinnedBuf, Stream, Event
 //   strk_policy.h   the adaptive policies as plain state machines: default window, band gate, grid history (no HIP in it)
 //   strk_groups.h   groups of byte strings as three calls take them: the view, its one check, the piece cutter (no HIP in it)
+//   strk_alleles_check.h, strk_phase_check.h   the input of the two allele calls and its checks (no HIP in them)
 // and the other parts live in include fragments spliced into this file:
 //   strk_host_miss.inc       window-miss rounds                       strk_host_pipe.inc       the pinned-slot host pipeline
 //   strk_host_ref.inc        reference side                           strk_host_realign.inc    realignment
@@ -145,8 +146,8 @@ struct strk_ctx {
     // The stream of the four calls below (side_stream creates it on first use).  One serves them all: each of these calls
     // synchronises before it returns and leaves no work in flight, and a context serves one host thread at a time.
     Stream side;
-    // allele calling (strk_call_alleles)
-    DevBuf al_off, al_cn, al_w, al_meta, al_ws, al_out, al_rp;
+    // allele calling (strk_call_alleles): what goes up, the workspaces, what comes down
+    DevBuf al_in, al_ws, al_out;
     // phased allele calls (strk_call_alleles_phased): what goes up, what the kernels hand each other, the workspaces, what comes down
     DevBuf ph_in, ph_mid, ph_ws, ph_out;
     // best representatives (strk_best_representatives)
@@ -804,14 +805,17 @@ int side_stream(strk_ctx* c, hipStream_t* st) {
     return 0;
 }
 
-// one timed launch sequence on `st`: the events of the context bracket it, the call waits for it
-template <class F>
-int timed_launch(strk_ctx* c, hipStream_t st, strk_stats* stats, const char* fn, const char* what, int n_launches, F&& launch) {
+// one timed launch sequence on `st`: the events of the context bracket it, `copies_down` (returns 0 or an error code) enqueues
+// behind the closing event what the one synchronise is to wait for as well, the call waits for it
+template <class F, class G>
+int timed_launch(strk_ctx* c, hipStream_t st, strk_stats* stats, const char* fn, const char* what, int n_launches, F&& launch,
+                 G&& copies_down) {
     hipEvent_t ev0 = c->ev[0], ev1 = c->ev[kNumEvents - 1];
     HIP_TRY(hipEventRecord(ev0, st));
     launch();
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(ev1, st));
+    if (const int rc = copies_down()) return rc;
     const hipError_t q = hipStreamSynchronize(st);
     if (q != hipSuccess) return fail(STRK_E_DEVICE, "%s: %s: %s", fn, what, hipGetErrorString(q));
     float ms = 0.f;
@@ -821,6 +825,10 @@ int timed_launch(strk_ctx* c, hipStream_t st, strk_stats* stats, const char* fn,
         stats->n_dp_launches += n_launches;
     }
     return 0;
+}
+template <class F>
+int timed_launch(strk_ctx* c, hipStream_t st, strk_stats* stats, const char* fn, const char* what, int n_launches, F&& launch) {
+    return timed_launch(c, st, stats, fn, what, n_launches, launch, [] { return 0; });
 }
 
 // strk_groups::check with the refusal as this library reports one: "<function>: <what is wrong>"
@@ -1066,11 +1074,13 @@ int strk_call_alleles(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off, co
                       int32_t* out_modal_n, int32_t* out_call, int32_t* out_ci95, int32_t* out_ci99, double* out_means,
                       double* out_weights, double* out_stdevs, int32_t* out_peak_n_reads, int32_t* out_read_peak,
                       strk_stats* stats) {
-    if (!ctx) return fail(STRK_E_INVALID, "ctx is NULL");
-    if (ctx->pending) return fail(STRK_E_INVALID, "a submitted call is pending on this context");
+    const char* fn = "strk_call_alleles";
+    if (!ctx) return fail(STRK_E_INVALID, "%s: ctx is NULL", fn);
+    if (ctx->pending) return fail(STRK_E_INVALID, "%s: a submitted call is pending on this context", fn);
     static_assert(STRK_ALLELE_CALLED == 0 && STRK_ALLELE_TOO_FEW == 1 && STRK_ALLELE_EMPTY_PEAK == 2, "include/strkit_amd.h <-> strk_alleles.h");
-    return call_alleles_impl(ctx, n_loci, read_off, cn, w, n_alleles, seed, p, out_status, out_modal_n, out_call, out_ci95,
-                             out_ci99, out_means, out_weights, out_stdevs, out_peak_n_reads, out_read_peak, stats);
+    const AlleleOut out{out_status, out_modal_n, out_call, out_ci95, out_ci99, out_means, out_weights, out_stdevs, out_peak_n_reads,
+                        out_read_peak};
+    return call_alleles_impl(ctx, fn, {n_loci, read_off, cn, w, n_alleles, seed, p}, out, stats);
 }
 
 int strk_call_alleles_phased(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off, const int32_t* cn, const double* w,
@@ -1092,9 +1102,9 @@ int strk_call_alleles_phased(strk_ctx* ctx, int32_t n_loci, const int32_t* read_
     static_assert(STRK_SNV_NOT_EVALUATED == kSnvNotEvaluated && STRK_SNV_CALLED == kSnvCalled && STRK_SNV_ZERO_TOTAL == kSnvZeroTotal &&
                   STRK_SNV_ONLY_OUT_OF_RANGE == kSnvOnlyOutOfRange && STRK_SNV_CROSS_TALK == kSnvCrossTalk &&
                   STRK_SNV_SAME_BASE == kSnvSameBase, "include/strkit_amd.h <-> strk_phase.h");
-    const strk_phase_check::Input in{n_loci, read_off, cn, w, n_alleles, seed, p, pp, hp, ps, snv_off, n_snv_cells, snv_base, snv_qual};
-    const PhaseOut out{out_status, out_modal_n, out_call, out_ci95, out_ci99, out_means, out_weights, out_stdevs, out_peak_n_reads,
-                       out_read_peak, out_method, out_reason, out_ps, out_snv_status, out_snv_call, out_snv_rcs};
+    const strk_phase_check::Input in{{n_loci, read_off, cn, w, n_alleles, seed, p}, pp, hp, ps, snv_off, n_snv_cells, snv_base, snv_qual};
+    const PhaseOut out{{out_status, out_modal_n, out_call, out_ci95, out_ci99, out_means, out_weights, out_stdevs, out_peak_n_reads,
+                        out_read_peak}, out_method, out_reason, out_ps, out_snv_status, out_snv_call, out_snv_rcs};
     return call_alleles_phased_impl(ctx, fn, in, out, stats);
 }
 

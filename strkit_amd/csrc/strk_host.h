@@ -56,6 +56,7 @@ struct OwnedMem {
     }
     ~OwnedMem() { release(); }
     template <class T> T* as() const { return static_cast<T*>(p); }
+    template <class T> T* at(size_t byte_off) const { return reinterpret_cast<T*>(static_cast<char*>(p) + byte_off); }
     void release() {
         if (p) (void)Free(p);
         p = nullptr;
@@ -79,6 +80,16 @@ struct DevBuf : OwnedMem<hipFree> {
         }
         cap = want;
         return 0;
+    }
+};
+
+// Sub-buffers of one device buffer, each 256-aligned: take() every part, ensure(bytes) the DevBuf, add the offsets to its p.
+struct Carve {
+    size_t bytes = 0;
+    size_t take(size_t n) {
+        const size_t at = bytes;
+        bytes += (n + 255) & ~(size_t)255;
+        return at;
     }
 };
 

@@ -1,27 +1,13 @@
 // Host side of strk_call_alleles_phased (call_locus.py:1381-1495 without the file front end; DESIGN.md §13): input checks
-// (strk_phase_check.h), pieces, launches.
-// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, strk_ctx and side_stream
-// defined there); not a stand-alone header.
+// (strk_phase_check.h), pieces, launches.  What it shares with strk_call_alleles is in strk_host_alleles.inc.
+// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf and Carve of strk_host.h, and
+// strk_ctx, side_stream and timed_launch defined there); not a stand-alone header.
 // ---------------------------------------------------------------------------------------------
 // Phased allele calls: strk_call_alleles_phased
 // ---------------------------------------------------------------------------------------------
-constexpr size_t kPhaseWsBudget = (size_t)512 << 20;   // workspace bytes of one piece (a larger single locus runs alone)
-constexpr int kPhasePieceLoci = 32768;
-
-// sub-buffers of one device buffer, each 256-aligned
-struct PhaseCarve {
-    size_t bytes = 0;
-    size_t take(size_t n) {
-        const size_t at = bytes;
-        bytes += (n + 255) & ~(size_t)255;
-        return at;
-    }
-};
-
 struct PhaseOut {
-    int32_t *status, *modal_n, *call, *ci95, *ci99;
-    double *means, *weights, *stdevs;
-    int32_t *peak_n_reads, *read_peak, *method, *reason, *ps, *snv_status;
+    AlleleOut al;
+    int32_t *method, *reason, *ps, *snv_status;
     uint8_t* snv_call;
     int32_t* snv_rcs;
 };
@@ -37,9 +23,7 @@ int call_alleles_phased_impl(strk_ctx* c, const char* fn, const strk_phase_check
     const int32_t n_loci = in.n_loci;
     if (n_loci == 0) return 0;
     const bool snvs = in.snv_off != nullptr, tags = in.hp != nullptr;
-    if (!out.status || !out.modal_n || !out.call || !out.ci95 || !out.ci99 || !out.means || !out.weights || !out.stdevs ||
-        !out.peak_n_reads || !out.read_peak || !out.method || !out.reason || !out.ps)
-        return fail(STRK_E_INVALID, "%s: NULL argument", fn);
+    if (!out.al.complete() || !out.method || !out.reason || !out.ps) return fail(STRK_E_INVALID, "%s: NULL argument", fn);
     if (snvs && in.snv_off[n_loci] > 0 && (!out.snv_status || !out.snv_call || !out.snv_rcs))
         return fail(STRK_E_INVALID, "%s: NULL argument (SNV outputs)", fn);
     const strk_allele_params* p = in.p;
@@ -49,13 +33,11 @@ int call_alleles_phased_impl(strk_ctx* c, const char* fn, const strk_phase_check
     hipStream_t st;
     if (const int rc = side_stream(c, &st)) return rc;
     const int B = p->num_bootstrap;
-    const int allele_threads = std::min(256, (B + 63) / 64 * 64);
-    const int64_t budget = pp->ws_budget > 0 ? pp->ws_budget : (int64_t)kPhaseWsBudget;
-    const size_t piece_loci = pp->piece_loci > 0 ? (size_t)pp->piece_loci : (size_t)kPhasePieceLoci;
+    const int64_t budget = pp->ws_budget > 0 ? pp->ws_budget : (int64_t)kAlleleWsBudget;
+    const size_t piece_loci = pp->piece_loci > 0 ? (size_t)pp->piece_loci : (size_t)kAllelePieceLoci;
     std::vector<int64_t> ws_off, aws_base, cell_rel;
     std::vector<int32_t> off_rel, snv_rel, oi;
     std::vector<double> od;
-    hipEvent_t ev0 = c->ev[0], ev1 = c->ev[kNumEvents - 1];
     auto n_snvs_of = [&](size_t l) { return snvs ? in.snv_off[l + 1] - in.snv_off[l] : 0; };
     auto group_ws = [&](size_t l) {   // k_phase_group's workspace
         return (int64_t)phase_ws_bytes(read_off[l + 1] - read_off[l], n_snvs_of(l), in.n_alleles[l], p->min_reads);
@@ -70,23 +52,21 @@ int call_alleles_phased_impl(strk_ctx* c, const char* fn, const strk_phase_check
         const int32_t nl = l1 - l0, r0 = read_off[l0], nr = read_off[l1] - r0;
         const int32_t s0 = snvs ? in.snv_off[l0] : 0, ns = snvs ? in.snv_off[l1] - s0 : 0;
         const int64_t c0 = snvs ? cell_off[l0] : 0, nc = snvs ? cell_off[l1] - c0 : 0;
-        off_rel.resize((size_t)nl + 1);
+        piece_offsets(read_off, l0, nl, off_rel);
         aws_base.resize(nl);
         int max_n = 0;
-        for (int32_t l = 0; l <= nl; ++l) off_rel[l] = read_off[l0 + l] - r0;
         for (int32_t l = 0; l < nl; ++l) {
             const int64_t g = group_ws((size_t)l0 + l);
             aws_base[l] = ws_off[l] + g;
             if (g > 0) max_n = std::max(max_n, off_rel[l + 1] - off_rel[l]);
         }
         if (snvs) {
-            snv_rel.resize((size_t)nl + 1);
+            piece_offsets(in.snv_off, l0, nl, snv_rel);
             cell_rel.resize(nl);
-            for (int32_t l = 0; l <= nl; ++l) snv_rel[l] = in.snv_off[l0 + l] - s0;
             for (int32_t l = 0; l < nl; ++l) cell_rel[l] = cell_off[l0 + l] - c0;
         }
         const size_t snl = (size_t)nl, snr = std::max<size_t>(nr, 1), sns = std::max<size_t>(ns, 1);
-        PhaseCarve ci, cm, co;
+        Carve ci, cm, co;
         const size_t i_off = ci.take((snl + 1) * 4), i_cn = ci.take(snr * 4), i_w = ci.take(snr * 8), i_nal = ci.take(snl * 4),
                      i_seed = ci.take(snl * 8), i_hp = ci.take(snr * 4), i_ps = ci.take(snr * 4), i_soff = ci.take((snl + 1) * 4),
                      i_coff = ci.take(snl * 8), i_base = ci.take(std::max<size_t>((size_t)nc, 1)), i_qual = ci.take(std::max<size_t>((size_t)nc, 1)),
@@ -102,7 +82,7 @@ int call_alleles_phased_impl(strk_ctx* c, const char* fn, const strk_phase_check
         if ((rc = c->ph_mid.ensure(cm.bytes))) return rc;
         if ((rc = c->ph_out.ensure(co.bytes))) return rc;
         if ((rc = c->ph_ws.ensure(std::max<size_t>((size_t)wsum, 256)))) return rc;
-        char *di = c->ph_in.as<char>(), *dm = c->ph_mid.as<char>(), *dout = c->ph_out.as<char>();
+        char* di = c->ph_in.as<char>();
         HIP_TRY(hipMemcpyAsync(di + i_off, off_rel.data(), (snl + 1) * 4, hipMemcpyHostToDevice, st));
         if (nr > 0) {
             HIP_TRY(hipMemcpyAsync(di + i_cn, in.cn + r0, (size_t)nr * 4, hipMemcpyHostToDevice, st));
@@ -125,37 +105,37 @@ int call_alleles_phased_impl(strk_ctx* c, const char* fn, const strk_phase_check
         HIP_TRY(hipMemcpyAsync(di + i_wsoff, ws_off.data(), snl * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(di + i_aws, aws_base.data(), snl * 8, hipMemcpyHostToDevice, st));
         PhaseArgs a{};
-        a.read_off = reinterpret_cast<int32_t*>(di + i_off);
-        a.cn = reinterpret_cast<int32_t*>(di + i_cn);
-        a.w = reinterpret_cast<double*>(di + i_w);
-        a.n_alleles = reinterpret_cast<int32_t*>(di + i_nal);
-        a.seed = reinterpret_cast<uint64_t*>(di + i_seed);
-        a.hp = tags ? reinterpret_cast<int32_t*>(di + i_hp) : nullptr;
-        a.ps = tags ? reinterpret_cast<int32_t*>(di + i_ps) : nullptr;
-        a.snv_off = snvs ? reinterpret_cast<int32_t*>(di + i_soff) : nullptr;
-        a.cell_off = reinterpret_cast<int64_t*>(di + i_coff);
-        a.snv_base = reinterpret_cast<uint8_t*>(di + i_base);
-        a.snv_qual = reinterpret_cast<uint8_t*>(di + i_qual);
-        a.ws_off = reinterpret_cast<int64_t*>(di + i_wsoff);
+        a.read_off = c->ph_in.at<int32_t>(i_off);
+        a.cn = c->ph_in.at<int32_t>(i_cn);
+        a.w = c->ph_in.at<double>(i_w);
+        a.n_alleles = c->ph_in.at<int32_t>(i_nal);
+        a.seed = c->ph_in.at<uint64_t>(i_seed);
+        a.hp = tags ? c->ph_in.at<int32_t>(i_hp) : nullptr;
+        a.ps = tags ? c->ph_in.at<int32_t>(i_ps) : nullptr;
+        a.snv_off = snvs ? c->ph_in.at<int32_t>(i_soff) : nullptr;
+        a.cell_off = c->ph_in.at<int64_t>(i_coff);
+        a.snv_base = c->ph_in.at<uint8_t>(i_base);
+        a.snv_qual = c->ph_in.at<uint8_t>(i_qual);
+        a.ws_off = c->ph_in.at<int64_t>(i_wsoff);
         a.ws = c->ph_ws.as<char>();
-        a.aws_base = reinterpret_cast<int64_t*>(di + i_aws);
-        a.perm = reinterpret_cast<int32_t*>(dm + m_perm);
-        a.gsz = reinterpret_cast<int32_t*>(dm + m_gsz);
-        a.meta = reinterpret_cast<int32_t*>(dm + m_meta);
-        a.gseed = reinterpret_cast<uint64_t*>(dm + m_gseed);
-        a.gone = reinterpret_cast<int32_t*>(dm + m_gone);
-        a.goff = reinterpret_cast<int32_t*>(dm + m_goff);
-        a.gws_off = reinterpret_cast<int64_t*>(dm + m_gws);
-        a.gcn = reinterpret_cast<int32_t*>(dm + m_gcn);
-        a.gw = reinterpret_cast<double*>(dm + m_gw);
-        a.g_oi = reinterpret_cast<int32_t*>(dm + m_goi);
-        a.g_od = reinterpret_cast<double*>(dm + m_god);
-        a.out_i = reinterpret_cast<int32_t*>(dout + o_i);
-        a.out_d = reinterpret_cast<double*>(dout + o_d);
-        a.read_peak = reinterpret_cast<int32_t*>(dout + o_rp);
-        a.snv_status = reinterpret_cast<int32_t*>(dout + o_sst);
-        a.snv_call = reinterpret_cast<uint8_t*>(dout + o_scall);
-        a.snv_rcs = reinterpret_cast<int32_t*>(dout + o_srcs);
+        a.aws_base = c->ph_in.at<int64_t>(i_aws);
+        a.perm = c->ph_mid.at<int32_t>(m_perm);
+        a.gsz = c->ph_mid.at<int32_t>(m_gsz);
+        a.meta = c->ph_mid.at<int32_t>(m_meta);
+        a.gseed = c->ph_mid.at<uint64_t>(m_gseed);
+        a.gone = c->ph_mid.at<int32_t>(m_gone);
+        a.goff = c->ph_mid.at<int32_t>(m_goff);
+        a.gws_off = c->ph_mid.at<int64_t>(m_gws);
+        a.gcn = c->ph_mid.at<int32_t>(m_gcn);
+        a.gw = c->ph_mid.at<double>(m_gw);
+        a.g_oi = c->ph_mid.at<int32_t>(m_goi);
+        a.g_od = c->ph_mid.at<double>(m_god);
+        a.out_i = c->ph_out.at<int32_t>(o_i);
+        a.out_d = c->ph_out.at<double>(o_d);
+        a.read_peak = c->ph_out.at<int32_t>(o_rp);
+        a.snv_status = c->ph_out.at<int32_t>(o_sst);
+        a.snv_call = c->ph_out.at<uint8_t>(o_scall);
+        a.snv_rcs = c->ph_out.at<int32_t>(o_srcs);
         a.n_loci = nl;
         a.min_reads = p->min_reads;
         a.min_allele_reads = p->min_allele_reads;
@@ -166,7 +146,7 @@ int call_alleles_phased_impl(strk_ctx* c, const char* fn, const strk_phase_check
         a.w_few = pp->cn_weight_few;
         a.w_many = pp->cn_weight_many;
         // the groups as 2 nl single-allele loci of k_alleles
-        AlleleArgs g{};
+        AlleleArgs g = allele_rule_args(p);
         g.read_off = a.goff;
         g.cn = a.gcn;
         g.w = a.gw;
@@ -174,70 +154,41 @@ int call_alleles_phased_impl(strk_ctx* c, const char* fn, const strk_phase_check
         g.seed = a.gseed;
         g.ws_off = a.gws_off;
         g.ws = a.ws;
-        g.out_i = reinterpret_cast<int32_t*>(dm + m_goi);
-        g.out_d = reinterpret_cast<double*>(dm + m_god);
-        g.read_peak = reinterpret_cast<int32_t*>(dm + m_grp);
+        g.out_i = c->ph_mid.at<int32_t>(m_goi);
+        g.out_d = c->ph_mid.at<double>(m_god);
+        g.read_peak = c->ph_mid.at<int32_t>(m_grp);
         g.n_loci = 2 * nl;
         g.min_reads = p->min_allele_reads;
         g.min_allele_reads = p->min_allele_reads;
-        g.B = B;
-        g.n_init = p->n_init;
-        g.max_iter = p->max_iter;
-        g.filter_factor = p->filter_factor;
-        g.force_gm_filter = p->force_gm_filter;
-        g.tol = p->tol;
-        g.reg_covar = p->reg_covar;
-        g.expansion_ratio = p->expansion_ratio;
         const int lds_matrix = (int)phase_lds_matrix_bytes(max_n);
-        HIP_TRY(hipEventRecord(ev0, st));
-        hipLaunchKernelGGL(k_phase_group, dim3(nl), dim3(kPhaseThreads), lds_matrix + kPhaseLdsFixed, st, a, lds_matrix);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_phase_pack, dim3((nl + kPhasePackLoci - 1) / kPhasePackLoci), dim3(256), 0, st, a);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_alleles, dim3(2 * nl), dim3(allele_threads), 0, st, g);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_phase_finish, dim3(nl), dim3(kPhaseFinishThreads), 0, st, a);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(ev1, st));
         oi.resize(snl * kPhaseOutI);
         od.resize(snl * kAlleleOutD);
-        HIP_TRY(hipMemcpyAsync(oi.data(), a.out_i, oi.size() * 4, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipMemcpyAsync(od.data(), a.out_d, od.size() * 8, hipMemcpyDeviceToHost, st));
-        if (nr > 0) HIP_TRY(hipMemcpyAsync(out.read_peak + r0, a.read_peak, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
-        if (ns > 0) {
-            HIP_TRY(hipMemcpyAsync(out.snv_status + s0, a.snv_status, (size_t)ns * 4, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out.snv_call + 2 * (size_t)s0, a.snv_call, (size_t)ns * 2, hipMemcpyDeviceToHost, st));
-            HIP_TRY(hipMemcpyAsync(out.snv_rcs + 2 * (size_t)s0, a.snv_rcs, (size_t)ns * 8, hipMemcpyDeviceToHost, st));
-        }
-        const hipError_t q = hipStreamSynchronize(st);
-        if (q != hipSuccess) return fail(STRK_E_DEVICE, "%s: phase kernels: %s", fn, hipGetErrorString(q));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-        if (stats) {
-            stats->kernel_ms += ms;
-            stats->n_dp_launches += 4;
-            stats->n_sub_batches += 1;
-        }
+        if ((rc = timed_launch(c, st, stats, fn, "phase kernels", 4, [&] {   // a launch that failed is the last one (timed_launch reports it)
+                hipLaunchKernelGGL(k_phase_group, dim3(nl), dim3(kPhaseThreads), lds_matrix + kPhaseLdsFixed, st, a, lds_matrix);
+                if (hipPeekAtLastError() != hipSuccess) return;
+                hipLaunchKernelGGL(k_phase_pack, dim3((nl + kPhasePackLoci - 1) / kPhasePackLoci), dim3(256), 0, st, a);
+                if (hipPeekAtLastError() != hipSuccess) return;
+                hipLaunchKernelGGL(k_alleles, dim3(2 * nl), dim3(allele_threads(B)), 0, st, g);
+                if (hipPeekAtLastError() != hipSuccess) return;
+                hipLaunchKernelGGL(k_phase_finish, dim3(nl), dim3(kPhaseFinishThreads), 0, st, a);
+            }, [&] {
+                HIP_TRY(hipMemcpyAsync(oi.data(), a.out_i, oi.size() * 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(od.data(), a.out_d, od.size() * 8, hipMemcpyDeviceToHost, st));
+                if (nr > 0) HIP_TRY(hipMemcpyAsync(out.al.read_peak + r0, a.read_peak, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
+                if (ns > 0) {
+                    HIP_TRY(hipMemcpyAsync(out.snv_status + s0, a.snv_status, (size_t)ns * 4, hipMemcpyDeviceToHost, st));
+                    HIP_TRY(hipMemcpyAsync(out.snv_call + 2 * (size_t)s0, a.snv_call, (size_t)ns * 2, hipMemcpyDeviceToHost, st));
+                    HIP_TRY(hipMemcpyAsync(out.snv_rcs + 2 * (size_t)s0, a.snv_rcs, (size_t)ns * 8, hipMemcpyDeviceToHost, st));
+                }
+                return 0;
+            }))) return rc;
+        if (stats) stats->n_sub_batches += 1;
+        scatter_alleles(out.al, l0, nl, oi.data(), kPhaseOutI, od.data());
         for (int32_t l = 0; l < nl; ++l) {
-            const int32_t* s = oi.data() + (size_t)l * kPhaseOutI;
-            const double* t = od.data() + (size_t)l * kAlleleOutD;
-            const size_t gl = (size_t)(l0 + l);
-            out.status[gl] = s[0];
-            out.modal_n[gl] = s[1];
-            for (int e = 0; e < 2; ++e) {
-                out.call[2 * gl + e] = s[2 + e];
-                out.peak_n_reads[2 * gl + e] = s[12 + e];
-                out.means[2 * gl + e] = t[e];
-                out.weights[2 * gl + e] = t[2 + e];
-                out.stdevs[2 * gl + e] = t[4 + e];
-            }
-            for (int e = 0; e < 4; ++e) {
-                out.ci95[4 * gl + e] = s[4 + e];
-                out.ci99[4 * gl + e] = s[8 + e];
-            }
-            out.method[gl] = s[kAlleleOutI];
-            out.reason[gl] = s[kAlleleOutI + 1];
-            out.ps[gl] = s[kAlleleOutI + 2];
+            const int32_t* s = oi.data() + (size_t)l * kPhaseOutI + kAlleleOutI;
+            out.method[l0 + l] = s[0];
+            out.reason[l0 + l] = s[1];
+            out.ps[l0 + l] = s[2];
         }
     }
     return 0;

@@ -14,15 +14,12 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._lib import ptr
 from ._groups import group_args, pack_groups
 
 MAX_GROUP = 250
 MAX_LEN = 65535
 EAGER_ENTRIES = 1 << 22     # a-priori bound (all windows) up to which the arrays are allocated at once; beyond: size query first
-
-
-def _ptr(a: np.ndarray | None) -> C.c_void_p:
-    return C.c_void_p(a.ctypes.data if a is not None and a.size else None)
 
 
 def count_kmers_packed(group_off, seq_start, seq_len, k, seqs=None, d_seqs=None, n_seq_bytes: int | None = None, ctx=None,
@@ -45,8 +42,8 @@ def count_kmers_packed(group_off, seq_start, seq_len, k, seqs=None, d_seqs=None,
     L = _lib.load()
 
     def call(cap: int, pos, count) -> int:
-        rc = L.strk_count_kmers_ws(ctx.handle, n_groups, _ptr(group_off), h_seqs, dev, n, _ptr(seq_start), _ptr(seq_len), _ptr(k),
-                                   cap, _ptr(entry_off), _ptr(pos), _ptr(count), int(workspace_bytes or 0), C.byref(st))
+        rc = L.strk_count_kmers_ws(ctx.handle, n_groups, ptr(group_off), h_seqs, dev, n, ptr(seq_start), ptr(seq_len), ptr(k),
+                                   cap, ptr(entry_off), ptr(pos), ptr(count), int(workspace_bytes or 0), C.byref(st))
         if rc < 0:
             _lib.check(int(rc))
         return int(rc)

@@ -14,7 +14,9 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib
-from .alleles import ASSIGN_DIST, ASSIGN_SINGLE, CALLED, TOO_FEW, AlleleParams, CallData, call_alleles_batch, call_data_from_batch
+from ._lib import ptr
+from .alleles import (ALLELE_KEYS, ASSIGN_DIST, ASSIGN_SINGLE, CALLED, TOO_FEW, AlleleParams, CallData, batch_inputs, batch_outputs,
+                      call_alleles_batch, call_data_from_batch)
 
 NOT_PHASED = 3
 ASSIGN_NONE, ASSIGN_HP, ASSIGN_SNV, ASSIGN_SNV_DIST = 0, 1, 2, 3
@@ -23,7 +25,6 @@ ASSIGN_NAMES = {ASSIGN_HP: "hp", ASSIGN_SNV: "snv", ASSIGN_SNV_DIST: "snv+dist"}
  REASON_NO_SNV_CALLED) = range(6)
 SNV_NOT_EVALUATED, SNV_CALLED, SNV_ZERO_TOTAL, SNV_ONLY_OUT_OF_RANGE, SNV_CROSS_TALK, SNV_SAME_BASE = -1, 0, 1, 2, 3, 4
 MAX_READS, MAX_SNVS = 1024, 64
-_ALLELE_KEYS = ("status", "modal_n", "call", "ci95", "ci99", "means", "weights", "stdevs", "peak_n_reads")
 
 
 @dataclass(frozen=True)
@@ -44,10 +45,6 @@ class PhaseParams:
                                     float(self.cn_weight_many), int(self.ws_budget))
 
 
-def _ptr(a):
-    return None if a is None else C.c_void_p(a.ctypes.data)
-
-
 def call_alleles_phased_batch(read_off, cns, weights, n_alleles, seeds, hp=None, ps=None, snv_off=None, snv_base=None,
                               snv_qual=None, params: AlleleParams | None = None, phase_params: PhaseParams | None = None,
                               fallback: bool = True, ctx=None, with_stats: bool = False):
@@ -62,14 +59,7 @@ def call_alleles_phased_batch(read_off, cns, weights, n_alleles, seeds, hp=None,
     params = params or AlleleParams()
     phase_params = phase_params or PhaseParams()
     ctx = ctx or _lib.default_context()
-    read_off = np.ascontiguousarray(read_off, dtype=np.int32)
-    cns = np.ascontiguousarray(cns, dtype=np.int32)
-    weights = np.ascontiguousarray(weights, dtype=np.float64)
-    n_loci = read_off.shape[0] - 1
-    n_alleles = np.ascontiguousarray(np.broadcast_to(np.asarray(n_alleles, dtype=np.int32), (n_loci,)))
-    seeds = np.ascontiguousarray(np.broadcast_to(np.asarray(seeds, dtype=np.uint64), (n_loci,)))
-    if n_loci < 0 or cns.shape != weights.shape or int(read_off[-1]) != cns.shape[0]:
-        raise ValueError("read_off must span cns, and cns and weights must have one entry per read")
+    read_off, cns, weights, n_alleles, seeds, n_loci = batch_inputs(read_off, cns, weights, n_alleles, seeds)
     n_reads = cns.shape[0]
     if hp is not None:
         hp = np.ascontiguousarray(hp, dtype=np.int32)
@@ -83,7 +73,7 @@ def call_alleles_phased_batch(read_off, cns, weights, n_alleles, seeds, hp=None,
         snv_off = np.ascontiguousarray(snv_off, dtype=np.int32)
         if snv_off.shape != (n_loci + 1,):
             raise ValueError("snv_off must have one entry per locus and one more")
-        n_snvs = max(int(snv_off[-1]), 0) if n_loci >= 0 else 0
+        n_snvs = max(int(snv_off[-1]), 0)
     if snv_base is not None:
         snv_base = np.ascontiguousarray(snv_base, dtype=np.uint8).ravel()
         n_cells = snv_base.shape[0]
@@ -91,20 +81,16 @@ def call_alleles_phased_batch(read_off, cns, weights, n_alleles, seeds, hp=None,
         snv_qual = np.ascontiguousarray(snv_qual, dtype=np.uint8).ravel()
         if snv_base is not None and snv_qual.shape != snv_base.shape:
             raise ValueError("snv_base and snv_qual must have one byte per cell each")
-    out = dict(status=np.empty(n_loci, np.int32), modal_n=np.empty(n_loci, np.int32),
-               call=np.empty((n_loci, 2), np.int32), ci95=np.empty((n_loci, 2, 2), np.int32),
-               ci99=np.empty((n_loci, 2, 2), np.int32), means=np.empty((n_loci, 2)),
-               weights=np.empty((n_loci, 2)), stdevs=np.empty((n_loci, 2)),
-               peak_n_reads=np.empty((n_loci, 2), np.int32), read_peak=np.empty(n_reads, np.int32),
+    out = dict(batch_outputs(n_loci, n_reads),
                method=np.empty(n_loci, np.int32), reason=np.empty(n_loci, np.int32), ps=np.empty(n_loci, np.int32),
                snv_status=np.empty(n_snvs, np.int32), snv_call=np.zeros((n_snvs, 2), np.uint8),
                snv_rcs=np.zeros((n_snvs, 2), np.int32))
     cp, pp = params._c(), phase_params._c()
     st = _lib.StrkStats()
     _lib.check(_lib.load().strk_call_alleles_phased(
-        ctx.handle, n_loci, _ptr(read_off), _ptr(cns), _ptr(weights), _ptr(n_alleles), _ptr(seeds), C.byref(cp), C.byref(pp),
-        _ptr(hp), _ptr(ps), _ptr(snv_off), _ptr(snv_base), _ptr(snv_qual), n_cells,
-        *[_ptr(out[k]) for k in (*_ALLELE_KEYS, "read_peak", "method", "reason", "ps", "snv_status", "snv_call", "snv_rcs")],
+        ctx.handle, n_loci, *map(ptr, (read_off, cns, weights, n_alleles, seeds)), C.byref(cp), C.byref(pp),
+        *map(ptr, (hp, ps, snv_off, snv_base, snv_qual)), n_cells,
+        *[ptr(out[k]) for k in (*ALLELE_KEYS, "read_peak", "method", "reason", "ps", "snv_status", "snv_call", "snv_rcs")],
         C.byref(st)))
     stats = st.as_dict()
     if fallback:
@@ -115,7 +101,7 @@ def call_alleles_phased_batch(read_off, cns, weights, n_alleles, seeds, hp=None,
             reads = np.concatenate([np.arange(read_off[l], read_off[l + 1]) for l in rest]) if sub_off[-1] else np.zeros(0, np.int64)
             sub, sub_st = call_alleles_batch(sub_off, cns[reads], weights[reads], n_alleles[rest], seeds[rest], params, ctx,
                                              with_stats=True)
-            for k in _ALLELE_KEYS:
+            for k in ALLELE_KEYS:
                 out[k][rest] = sub[k]
             out["read_peak"][reads] = sub["read_peak"]
             stats["kernel_ms"] += sub_st["kernel_ms"]

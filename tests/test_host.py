@@ -752,3 +752,18 @@ int main() {
     assert len(out) == len(script) + 1
     for k, ((cmd, want), got) in enumerate(zip(script, out)):
         assert got.rstrip() == want.rstrip(), (k, cmd[:80], got, want)
+
+
+def test_allele_call_checkers_accept_and_refuse_what_they_should(tmp_path):
+    """Host build of tools/phase_asan.cpp (no HIP in strk_alleles_check.h and strk_phase_check.h): the input checks of
+    strk_call_alleles and strk_call_alleles_phased over random valid calls and every refusal, arrays of exactly their length;
+    the program counts its own failures and exits 0 without one."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no host C++ compiler")
+    exe = tmp_path / "phase_check"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tools", "phase_asan.cpp")], check=True)
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert " 0 failed" in run.stdout, run.stdout

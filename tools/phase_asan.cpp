@@ -1,6 +1,7 @@
-// The host side of strk_call_alleles_phased that runs before any launch (strk_phase_check.h: every input check; strk_groups.h:
-// the piece cutter over per-locus costs shaped like the call's) under AddressSanitizer / UBSan.  Every array is a heap block of
-// exactly its length, so a read one element past any of them is reported.  Build and run: tools/phase_asan.sh
+// The host side of strk_call_alleles and strk_call_alleles_phased that runs before any launch (strk_alleles_check.h and
+// strk_phase_check.h: every input check; strk_groups.h: the piece cutter over per-locus costs shaped like the phased call's).
+// Every array is a heap block of exactly its length, so a read one element past any of them is reported under
+// AddressSanitizer / UBSan (tools/phase_asan.sh); tests/test_host.py builds it plain and requires exit 0.
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -8,6 +9,7 @@
 #include <limits>
 #include <random>
 #include <string>
+#include <tuple>
 #include <vector>
 #include "../strkit_amd/csrc/strk_phase_check.h"
 
@@ -22,7 +24,7 @@ struct Call {
     strk_phase_params pp{8, 20, 3, 0, 0.2, 0.1, 0};
     bool tags = true, snvs = true;
     strk_phase_check::Input input() const {
-        return {(int32_t)n_alleles.size(), read_off.data(), cn.data(), w.data(), n_alleles.data(), seed.data(), &p, &pp,
+        return {{(int32_t)n_alleles.size(), read_off.data(), cn.data(), w.data(), n_alleles.data(), seed.data(), &p}, &pp,
                 tags ? hp.data() : nullptr, tags ? ps.data() : nullptr, snvs ? snv_off.data() : nullptr, (int64_t)base.size(),
                 snvs ? base.data() : nullptr, snvs ? qual.data() : nullptr};
     }
@@ -50,7 +52,35 @@ Call make(std::mt19937& rng, int n_loci, int max_n, int max_s) {
     return c;
 }
 
-int g_failed = 0;
+int g_failed = 0, g_refusals = 0;
+
+// strk_call_alleles' own check (the limits of strk_alleles.h)
+void expect_plain(const Call& c, bool ok, const char* what, const char* needle = "") {
+    strk_groups::Message m;
+    m.text[0] = 0;
+    const int rc = strk_alleles_check::check(c.input(), {65535, 1024, 15}, &m);
+    if (!(ok ? rc == 0 : (rc == strk_groups::kInvalid && strstr(m.text, needle)))) {
+        fprintf(stderr, "FAILED plain %s: rc %d, message '%s'\n", what, rc, m.text);
+        ++g_failed;
+    }
+    g_refusals += !ok;
+}
+
+// two loci of five reads, or one of n_reads
+Call plain_call(int n_reads = 0) {
+    Call c;
+    c.tags = c.snvs = false;
+    if (n_reads) c.read_off = {0, n_reads};
+    else c.read_off = {0, 5, 10};
+    for (int r = 0; r < c.read_off.back(); ++r) {
+        c.cn.push_back(r);
+        c.w.push_back(1.0);
+    }
+    c.n_alleles.assign(c.read_off.size() - 1, 2);
+    c.seed.assign(c.read_off.size() - 1, 1);
+    return c;
+}
+
 void expect(const Call& c, bool ok, const char* what, const char* needle = "") {
     const strk_phase_check::Limits lim{1024, 64, 1024, 15};
     std::vector<int64_t> cell_off;
@@ -58,6 +88,7 @@ void expect(const Call& c, bool ok, const char* what, const char* needle = "") {
     m.text[0] = 0;
     const int rc = strk_phase_check::check(c.input(), lim, cell_off, &m);
     const bool good = ok ? rc == 0 : (rc == strk_groups::kInvalid && strstr(m.text, needle));
+    g_refusals += !ok;
     if (!good) {
         fprintf(stderr, "FAILED %s: rc %d, message '%s'\n", what, rc, m.text);
         ++g_failed;
@@ -140,6 +171,7 @@ int main() {
             fprintf(stderr, "FAILED hp without ps\n");
             ++g_failed;
         }
+        ++g_refusals;
     }
     t = c;
     t.base.pop_back();
@@ -161,8 +193,9 @@ int main() {
     t.read_off[3] = t.read_off[2] - 1;
     expect(t, false, "decreasing read_off", "decreasing");
     t = c;
-    t.p.min_allele_reads = 0;
+    t.p.min_allele_reads = 0;   // only a group's call needs it: the plain checker takes it
     expect(t, false, "min_allele_reads 0", "min_allele_reads");
+    expect_plain(t, true, "min_allele_reads 0");
     t = c;
     t.p.num_bootstrap = 1025;
     expect(t, false, "1 025 bootstraps", "num_bootstrap");
@@ -172,6 +205,34 @@ int main() {
     t = c;
     t.pp.piece_loci = -1;
     expect(t, false, "negative piece", "piece_loci");
-    printf("phase_asan: %ld valid calls, %ld pieces, 13 refusals, %d failed\n", calls, pieces, g_failed);
+    // strk_call_alleles: the refusals of tests/test_gpu_alleles.py::test_invalid_input_is_rejected_before_any_launch
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    expect_plain(plain_call(), true, "valid call");
+    expect_plain(plain_call(65535), true, "65 535 reads");
+    expect_plain(plain_call(65536), false, "65 536 reads", "locus 0: 65536 reads (at most 65535)");
+    for (auto [l, n_alleles, needle] : {std::tuple{1, 3, "locus 1: n_alleles 3"}, std::tuple{0, 0, "locus 0: n_alleles 0"}}) {
+        t = plain_call();
+        t.n_alleles[l] = n_alleles;
+        expect_plain(t, false, "n_alleles", needle);
+    }
+    for (auto [r, weight, needle] : {std::tuple{7, 0.0, "locus 1: read 7"}, std::tuple{2, nan, "locus 0: read 2"}, std::tuple{6, -1.0, "locus 1: read 6"}}) {
+        t = plain_call();
+        t.w[r] = weight;
+        expect_plain(t, false, "weight", needle);
+    }
+    for (int b : {1, 1025}) {
+        t = plain_call();
+        t.p.num_bootstrap = b;
+        expect_plain(t, false, "num_bootstrap", "num_bootstrap");
+    }
+    for (int n : {0, 16}) {
+        t = plain_call();
+        t.p.n_init = n;
+        expect_plain(t, false, "n_init", "n_init");
+    }
+    t = plain_call();
+    t.p.reg_covar = 0.0;
+    expect_plain(t, false, "reg_covar 0", "reg_covar");
+    printf("phase_asan: %ld valid calls, %ld pieces, %d refusals, %d failed\n", calls, pieces, g_refusals, g_failed);
     return g_failed ? 1 : 0;
 }

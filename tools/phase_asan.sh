@@ -1,5 +1,5 @@
 #!/bin/bash
-# The input checks and the piece cutting of strk_call_alleles_phased under AddressSanitizer + UBSan on the host (no GPU needed).
+# The input checks of strk_call_alleles and strk_call_alleles_phased and the latter's piece cutting under AddressSanitizer + UBSan on the host (no GPU needed).
 set -e
 D=${TMPDIR:-/tmp}/strk_phase_asan
 mkdir -p $D
