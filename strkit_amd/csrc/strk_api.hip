@@ -4,6 +4,7 @@
 //   strk_policy.h   the adaptive policies as plain state machines: default window, band gate, grid history (no HIP in it)
 //   strk_groups.h   groups of byte strings as three calls take them: the view, its one check, the piece cutter (no HIP in it)
 //   strk_alleles_check.h, strk_phase_check.h   the input of the two allele calls and its checks (no HIP in them)
+//   strk_realign_plan.h   strk_realign's input check, chunks and workspace layout (no HIP in it)
 // and the other parts live in include fragments spliced into this file:
 //   strk_host_miss.inc       window-miss rounds                       strk_host_pipe.inc       the pinned-slot host pipeline
 //   strk_host_ref.inc        reference side                           strk_host_realign.inc    realignment
@@ -62,6 +63,7 @@ std::atomic<int> g_calls_in_flight{0};
 strk_policy::WindowPolicy g_window;
 static_assert(strk_policy::kWinBuckets == strk::kWinBuckets, "strk_policy.h <-> strk_kernels.h");
 static_assert(strk_groups::kInvalid == STRK_E_INVALID, "strk_groups.h <-> include/strkit_amd.h");
+static_assert(strk_realign_plan::kNoMem == STRK_E_NOMEM, "strk_realign_plan.h <-> include/strkit_amd.h");
 
 // The band pass most recently enqueued by any context of this process (its kEvBand event): in whole-grid mode the next call's
 // band pass waits for it (enqueue_scoring), so that two calls in flight run half a period apart whatever their submit times.
@@ -136,15 +138,17 @@ struct strk_ctx {
     // workspace
     DevBuf read_locus, win_lo, win_n, tab_off, table, cls_list, band_recs, band_recs_w, long_list, counters, scratch, state_i32, state_f64, spec, rhash, rep, exact;
     DevBuf win_lo2, win_n2, tab_off2, table2, items;
-    DevBuf sc_dev;                  // strk_repeat_count's fast path: one read's arrays in one device buffer ...
-    PinnedBuf sc_host, sc_out;      // ... their pinned host image (one copy up) and the pinned result (one copy down)
-    // staging for the host-buffer entry points
-    DevBuf in_seqs, in_seq_off, in_nfl, in_ntr, in_nfr, in_est, in_read_off, in_motifs, in_motif_off;
-    DevBuf out_cn, out_score, out_n, out_start;
-    // realignment (strk_realign)
-    DevBuf rl_s1, rl_s2, rl_pairs, rl_trace, rl_edge, rl_out, rl_cigar, rl_queue;
-    // The stream of the four calls below (side_stream creates it on first use).  One serves them all: each of these calls
-    // synchronises before it returns and leaves no work in flight, and a context serves one host thread at a time.
+    // staging for the host-buffer entry points: the arrays of a host batch (upload_batch; strk_repeat_count's fast path keeps
+    // its one read's arrays there), the four result arrays of strk_count_loci
+    DevBuf stage_in, stage_out;
+    PinnedBuf sc_host, sc_out;      // the fast path's pinned host image (one copy up) and its pinned result (one copy down)
+    // realignment (strk_realign): what a call sizes once (the bases, the queue counters), what it sizes per chunk
+    DevBuf rl_call, rl_chunk;
+    // The stream of every call for which the library chooses one (side_stream creates it on first use): the scalar, table,
+    // reference-side and realign calls, strk_count_loci below the pipeline's threshold or with d_seqs, and the allele, group
+    // and consensus calls below.  One serves them all: each of these calls synchronises before it returns and leaves no work
+    // in flight, and a context serves one host thread at a time.  It is non-blocking, so nothing on it is ordered against the
+    // NULL stream: whatever such a call copies, sets or launches goes on this stream and is waited for on it.
     Stream side;
     // allele calling (strk_call_alleles): what goes up, the workspaces, what comes down
     DevBuf al_in, al_ws, al_out;
@@ -634,9 +638,17 @@ int check_batch_range(const strk_batch* b, size_t l0, size_t l1) {
     return 0;
 }
 
-// uploads a host batch into the context's staging buffers; returns a batch of device pointers
+// The stream of every call that is given none (strk_ctx::side).
+int side_stream(strk_ctx* c, hipStream_t* st) {
+    if (!c->side) HIP_TRY(hipStreamCreateWithFlags(&c->side.h, hipStreamNonBlocking));
+    *st = c->side;
+    return 0;
+}
+
+// uploads a host batch into the context's staging buffer on the context's side stream; returns a batch of device pointers and
+// (unless the batch is empty) that stream
 // `d_seqs` (optional): the bases are in device memory already (strk_dbam_extract); b->seqs is not read then
-int upload_batch(strk_ctx* c, const strk_batch* b, strk_batch* d, hipStream_t st, const uint8_t* d_seqs = nullptr) {
+int upload_batch(strk_ctx* c, const strk_batch* b, strk_batch* d, hipStream_t* side, const uint8_t* d_seqs = nullptr) {
     if (!b || b->n_reads < 0 || b->n_loci < 0) return fail(STRK_E_INVALID, "bad batch");
     *d = *b;
     if (b->n_reads == 0 || b->n_loci == 0) return 0;
@@ -649,30 +661,93 @@ int upload_batch(strk_ctx* c, const strk_batch* b, strk_batch* d, hipStream_t st
     const size_t nbases = (size_t)b->seq_off[nr], nmot = (size_t)b->motif_off[nl];
     if (nbases && !b->seqs && !d_seqs) return fail(STRK_E_INVALID, "seqs is NULL");
     HIP_TRY(hipSetDevice(c->device));
-#define UP(buf, src, bytes, field)                                                              \
-    if ((rc = c->buf.ensure(std::max<size_t>((bytes), 16)))) return rc;                         \
-    if ((bytes) > 0) HIP_TRY(hipMemcpyAsync(c->buf.p, (src), (bytes), hipMemcpyHostToDevice, st)); \
-    d->field = static_cast<decltype(d->field)>(c->buf.p);
-    if (d_seqs) d->seqs = d_seqs;
-    else { UP(in_seqs, b->seqs, nbases, seqs) }
-    UP(in_seq_off, b->seq_off, (nr + 1) * 8, seq_off)
-    UP(in_nfl, b->nfl, nr * 4, nfl)
-    UP(in_ntr, b->ntr, nr * 4, ntr)
-    UP(in_nfr, b->nfr, nr * 4, nfr)
-    UP(in_read_off, b->read_off, (nl + 1) * 4, read_off)
-    UP(in_motifs, b->motifs, nmot, motifs)
-    UP(in_motif_off, b->motif_off, (nl + 1) * 4, motif_off)
-    if (b->est_cn) {
-        UP(in_est, b->est_cn, nr * 4, est_cn)
-    } else {
-        if ((rc = c->in_est.ensure(nr * 4))) return rc;
-        HIP_TRY(hipMemsetAsync(c->in_est.p, 0, nr * 4, st));
-        d->est_cn = c->in_est.as<int32_t>();
-    }
-#undef UP
+    if ((rc = side_stream(c, side))) return rc;
+    const hipStream_t st = *side;
+    const struct { const void* src; size_t bytes; } part[9] = {
+        {b->seqs, d_seqs ? 0 : nbases}, {b->seq_off, (nr + 1) * 8}, {b->nfl, nr * 4}, {b->ntr, nr * 4}, {b->nfr, nr * 4},
+        {b->est_cn, nr * 4}, {b->read_off, (nl + 1) * 4}, {b->motifs, nmot}, {b->motif_off, (nl + 1) * 4}};
+    Carve cv;
+    size_t at[9];
+    for (int k = 0; k < 9; ++k) at[k] = cv.take(part[k].bytes);
+    if ((rc = c->stage_in.ensure(cv.bytes))) return rc;
+    const DevBuf& s = c->stage_in;
+    for (int k = 0; k < 9; ++k)
+        if (part[k].src && part[k].bytes) HIP_TRY(hipMemcpyAsync(s.at<char>(at[k]), part[k].src, part[k].bytes, hipMemcpyHostToDevice, st));
+    if (!b->est_cn) HIP_TRY(hipMemsetAsync(s.at<char>(at[5]), 0, nr * 4, st));
+    d->seqs = d_seqs ? d_seqs : s.at<uint8_t>(at[0]);
+    d->seq_off = s.at<int64_t>(at[1]); d->nfl = s.at<int32_t>(at[2]); d->ntr = s.at<int32_t>(at[3]); d->nfr = s.at<int32_t>(at[4]);
+    d->est_cn = s.at<int32_t>(at[5]); d->read_off = s.at<int32_t>(at[6]); d->motifs = s.at<uint8_t>(at[7]);
+    d->motif_off = s.at<int32_t>(at[8]);
     return 0;
 }
 
+// One timed launch sequence on `st`: the events of the context bracket it, `copies_down` (returns 0 or an error code) enqueues
+// behind the closing event what the wait is to cover as well, the call waits for it: with one synchronise, or, given limit_s,
+// by polling the stream for at most that many seconds.  A failed wait is reported as "<fn>: <what>: <error>" (fn may be NULL).
+template <class F, class G = int (*)()>
+int timed_launch(strk_ctx* c, hipStream_t st, strk_stats* stats, const char* fn, const char* what, int n_launches, F&& launch,
+                 G&& copies_down = +[] { return 0; }, double limit_s = 0.0) {
+    hipEvent_t ev0 = c->ev[0], ev1 = c->ev[kNumEvents - 1];
+    HIP_TRY(hipEventRecord(ev0, st));
+    launch();
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev1, st));
+    if (const int rc = copies_down()) return rc;
+    const char* sep = fn ? ": " : "";
+    hipError_t q;
+    if (limit_s > 0.0) {
+        const auto t0 = std::chrono::steady_clock::now();
+        while ((q = hipStreamQuery(st)) == hipErrorNotReady) {
+            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > limit_s)
+                return fail(STRK_E_DEVICE, "%s%s%s did not finish within %.0f s", fn ? fn : "", sep, what, limit_s);
+            usleep(50);
+        }
+        (void)hipGetLastError();   // (a "not ready" of the polling is no error of the next call)
+    } else {
+        q = hipStreamSynchronize(st);
+    }
+    if (q != hipSuccess) return fail(STRK_E_DEVICE, "%s%s%s: %s", fn ? fn : "", sep, what, hipGetErrorString(q));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    if (stats) {
+        stats->kernel_ms += ms;
+        stats->n_dp_launches += n_launches;
+    }
+    return 0;
+}
+
+// bases that are on the device already must be on THIS context's device (no peer access is set up)
+int check_dseqs(strk_ctx* c, const char* fn, const void* d_seqs) {
+    (void)hipSetDevice(c->device);
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, d_seqs) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != c->device) {
+        (void)hipGetLastError();
+        return fail(STRK_E_INVALID, "%s: d_seqs is not device memory of device %d (the context's)", fn, c->device);
+    }
+    return 0;
+}
+
+// strk_params with the semantics of the scalar calls (strk_repeat_count, and the final counts of the reference side): the first
+// maximum, every end free, no feedback, and the window those calls take for their search schedule
+strk_params default_params(int32_t max_iters, int32_t lsr, int32_t step) {
+    strk_params p;
+    memset(&p, 0, sizeof p);
+    p.max_iters = max_iters; p.local_search_range = lsr; p.step_size = step;
+    p.tie_rule = STRK_TIE_FIRST; p.end_flags = STRK_SG_ALL; p.feedback = 0;
+    p.window = std::min(15, std::max(kDefaultWindow, lsr + step + 1));
+    return p;
+}
+
+// The offset arrays of a batch of one read of one locus, in one block (the head of the fast path's device image) ...
+struct OneRead {
+    int64_t seq_off[2];
+    int32_t lens[4];   // nfl, ntr, nfr, est_cn
+    int32_t read_off[2], motif_off[2];
+};
+// ... and the batch over such a block where it lies (`at`: host or device; only addresses are taken), its bases and its motif
+strk_batch one_read_batch(const OneRead* at, const uint8_t* seqs, const uint8_t* motif) {
+    return {1, 1, seqs, at->seq_off, at->lens, at->lens + 1, at->lens + 2, at->lens + 3, at->read_off, motif, at->motif_off};
+}
 
 #include "strk_host_pipe.inc"
 
@@ -681,47 +756,36 @@ int upload_batch(strk_ctx* c, const strk_batch* b, strk_batch* d, hipStream_t st
 // single read (about 0.1 ms).  Returns 0 with the result, 1 when the read has to go the general way (no fast class, more than
 // eight symbol classes, a search that leaves the window, nothing scored), < 0 on an error.
 constexpr size_t kScalarSeqMax = 1792, kScalarMotifMax = 256;
-constexpr size_t kScOffSeqOff = 0, kScOffLens = 16, kScOffReadOff = 32, kScOffMotifOff = 40, kScOffMotif = 48,
-                 kScOffSeq = kScOffMotif + kScalarMotifMax, kScBytes = kScOffSeq + kScalarSeqMax + 64;
+constexpr size_t kScOffMotif = sizeof(OneRead), kScOffSeq = kScOffMotif + kScalarMotifMax, kScBytes = kScOffSeq + kScalarSeqMax + 64;
+static_assert(kScOffMotif == 48, "the fast path's image: 48 bytes of offsets, the motif, the bases");
 int scalar_fast(strk_ctx* c, int32_t start, const uint8_t* tr, int32_t ntr, const uint8_t* fl, int32_t nfl, const uint8_t* fr, int32_t nfr,
-                const uint8_t* motif, int32_t m, int32_t max_iters, int32_t lsr, int32_t step, int32_t window, int32_t* cn, int32_t* score,
-                int32_t* n_explored) {
+                const uint8_t* motif, int32_t m, strk_params p, int32_t* cn, int32_t* score, int32_t* n_explored) {
     const size_t ndb = (size_t)nfl + ntr + nfr;
-    if (c->pending || nfl < 1 || nfr < 1 || ndb + 1 > kScalarSeqMax || (size_t)m > kScalarMotifMax || lsr < 0 || step < 1) return 1;
+    if (c->pending || nfl < 1 || nfr < 1 || ndb + 1 > kScalarSeqMax || (size_t)m > kScalarMotifMax || p.local_search_range < 0 || p.step_size < 1)
+        return 1;
     HIP_TRY(hipSetDevice(c->device));
     int rc;
+    hipStream_t st;
+    if ((rc = side_stream(c, &st))) return rc;
     if (!c->sc_host.p) HIP_TRY(c->sc_host.alloc(kScBytes));
     if (!c->sc_out.p) HIP_TRY(c->sc_out.alloc(64));
-    if ((rc = c->sc_dev.ensure(kScBytes))) return rc;
-    const int ts = std::min(kTableMax - 1, 2 * (window + 7) + 1);
+    if ((rc = c->stage_in.ensure(kScBytes))) return rc;
+    const int ts = std::min(kTableMax - 1, 2 * (p.window + 7) + 1);
     if ((rc = ensure_workspace(c, 1, 1, (size_t)ts, 1))) return rc;
     uint8_t* h = c->sc_host.as<uint8_t>();
-    const int64_t seq_off[2] = {0, (int64_t)ndb};
-    const int32_t lens[4] = {nfl, ntr, nfr, start}, read_off[2] = {0, 1}, motif_off[2] = {0, m};
-    memcpy(h + kScOffSeqOff, seq_off, 16);
-    memcpy(h + kScOffLens, lens, 16);
-    memcpy(h + kScOffReadOff, read_off, 8);
-    memcpy(h + kScOffMotifOff, motif_off, 8);
+    const OneRead head{{0, (int64_t)ndb}, {nfl, ntr, nfr, start}, {0, 1}, {0, m}};
+    memcpy(h, &head, sizeof head);
     memcpy(h + kScOffMotif, motif, (size_t)m);
     memcpy(h + kScOffSeq, fl, (size_t)nfl);
     if (ntr) memcpy(h + kScOffSeq + nfl, tr, (size_t)ntr);
     memcpy(h + kScOffSeq + nfl + ntr, fr, (size_t)nfr);
-    hipStream_t st = nullptr;
     const size_t up = kScOffSeq + ndb;
-    HIP_TRY(hipMemcpyAsync(c->sc_dev.p, h, up, hipMemcpyHostToDevice, st));
-    const uint8_t* d = c->sc_dev.as<uint8_t>();
-    strk_batch b;
-    b.n_reads = 1; b.n_loci = 1;
-    b.seqs = d + kScOffSeq; b.seq_off = reinterpret_cast<const int64_t*>(d + kScOffSeqOff);
-    b.nfl = reinterpret_cast<const int32_t*>(d + kScOffLens); b.ntr = b.nfl + 1; b.nfr = b.nfl + 2; b.est_cn = b.nfl + 3;
-    b.read_off = reinterpret_cast<const int32_t*>(d + kScOffReadOff);
-    b.motifs = d + kScOffMotif; b.motif_off = reinterpret_cast<const int32_t*>(d + kScOffMotifOff);
-    strk_params p;
-    memset(&p, 0, sizeof p);
-    p.max_iters = max_iters; p.local_search_range = lsr; p.step_size = step; p.tie_rule = STRK_TIE_FIRST; p.end_flags = STRK_SG_ALL;
+    HIP_TRY(hipMemcpyAsync(c->stage_in.p, h, up, hipMemcpyHostToDevice, st));
+    const uint8_t* d = c->stage_in.as<uint8_t>();
+    const strk_batch b = one_read_batch(c->stage_in.as<OneRead>(), d + kScOffSeq, d + kScOffMotif);
     p.no_dedupe = 1; p.no_band = 1;
     for (int k = 0; k < kWinBuckets; ++k) c->p_window_b[k] = 0;
-    KArgs a = make_args(c, &b, p.end_flags, window, ts, 1, &p);
+    KArgs a = make_args(c, &b, p.end_flags, p.window, ts, 1, &p);
     hipLaunchKernelGGL(k_scalar_plan, dim3(1), dim3(64), 0, st, a, (int)(kCountersBytes / 4));
     hipLaunchKernelGGL(k_dp_all, dim3(1), dim3(256), 0, st, a);
     HIP_TRY(hipMemcpyAsync(c->sc_out.p, a.spec, sizeof(int4), hipMemcpyDeviceToHost, st));
@@ -745,7 +809,8 @@ int score_table_impl(strk_ctx* ctx, const strk_batch* batch, const int32_t* lo, 
     if (end_flags < 0 || end_flags > 15) return fail(STRK_E_INVALID, "bad end_flags");
     strk_batch d;
     int rc;
-    if ((rc = upload_batch(ctx, batch, &d, nullptr))) return rc;
+    hipStream_t st;
+    if ((rc = upload_batch(ctx, batch, &d, &st))) return rc;
     if (batch->n_reads == 0 || batch->n_loci == 0) return 0;
     if (!lo || !n || !table_off || !scores) return fail(STRK_E_INVALID, "lo / n / table_off / scores is NULL");
     const size_t nr = (size_t)batch->n_reads;
@@ -760,7 +825,6 @@ int score_table_impl(strk_ctx* ctx, const strk_batch* batch, const int32_t* lo, 
     if ((rc = ensure_workspace(ctx, batch->n_reads, batch->n_loci, tab * mul, std::max<size_t>(n_chunks, 1)))) return rc;
     KArgs a = make_args(ctx, &d, end_flags, 0, 0, (int)std::max<size_t>(n_chunks, 1), nullptr);
     a.ref_mode = ref_mode;
-    hipStream_t st = nullptr;
     std::vector<int64_t> off_dev(table_off, table_off + nr);
     for (auto& o : off_dev) o *= mul;
     HIP_TRY(hipMemcpyAsync(a.win_lo, lo, nr * 4, hipMemcpyHostToDevice, st));
@@ -769,15 +833,12 @@ int score_table_impl(strk_ctx* ctx, const strk_batch* batch, const int32_t* lo, 
     if ((rc = score_until_scratch_fits(ctx, a, nullptr, batch->n_reads, force_generic, st, true))) return rc;
     if ((rc = check_error_bits(ctx->h_counters.cnt(kCntError)))) return rc;
     if (tab) {
-        if (!ref_mode) {
-            HIP_TRY(hipMemcpy(scores, a.table, tab * 4, hipMemcpyDeviceToHost));
-        } else {
-            std::vector<int32_t> pairs(tab * 2);
-            HIP_TRY(hipMemcpy(pairs.data(), a.table, tab * 8, hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < tab; ++k) {
-                scores[k] = pairs[2 * k];
-                end_query[k] = pairs[2 * k + 1];
-            }
+        std::vector<int32_t> pairs(ref_mode ? tab * 2 : 0);   // (score, end_query) per candidate
+        HIP_TRY(hipMemcpyAsync(ref_mode ? pairs.data() : scores, a.table, tab * 4 * mul, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (size_t k = 0; k < pairs.size() / 2; ++k) {
+            scores[k] = pairs[2 * k];
+            end_query[k] = pairs[2 * k + 1];
         }
     }
     if (stats) {
@@ -798,55 +859,11 @@ int score_table_impl(strk_ctx* ctx, const strk_batch* batch, const int32_t* lo, 
 
 #include "strk_host_realign.inc"
 
-// The stream of strk_call_alleles, strk_call_alleles_phased, strk_best_representatives, strk_count_kmers and strk_consensus (strk_ctx::side).
-int side_stream(strk_ctx* c, hipStream_t* st) {
-    if (!c->side) HIP_TRY(hipStreamCreateWithFlags(&c->side.h, hipStreamNonBlocking));
-    *st = c->side;
-    return 0;
-}
-
-// one timed launch sequence on `st`: the events of the context bracket it, `copies_down` (returns 0 or an error code) enqueues
-// behind the closing event what the one synchronise is to wait for as well, the call waits for it
-template <class F, class G>
-int timed_launch(strk_ctx* c, hipStream_t st, strk_stats* stats, const char* fn, const char* what, int n_launches, F&& launch,
-                 G&& copies_down) {
-    hipEvent_t ev0 = c->ev[0], ev1 = c->ev[kNumEvents - 1];
-    HIP_TRY(hipEventRecord(ev0, st));
-    launch();
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(ev1, st));
-    if (const int rc = copies_down()) return rc;
-    const hipError_t q = hipStreamSynchronize(st);
-    if (q != hipSuccess) return fail(STRK_E_DEVICE, "%s: %s: %s", fn, what, hipGetErrorString(q));
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-    if (stats) {
-        stats->kernel_ms += ms;
-        stats->n_dp_launches += n_launches;
-    }
-    return 0;
-}
-template <class F>
-int timed_launch(strk_ctx* c, hipStream_t st, strk_stats* stats, const char* fn, const char* what, int n_launches, F&& launch) {
-    return timed_launch(c, st, stats, fn, what, n_launches, launch, [] { return 0; });
-}
-
 // strk_groups::check with the refusal as this library reports one: "<function>: <what is wrong>"
 int check_groups(const char* fn, const strk_groups::View& v, int max_group, int max_len, strk_groups::Totals* t) {
     strk_groups::Message m;
     const int rc = strk_groups::check(v, max_group, max_len, t, &m);
     return rc ? fail(rc, "%s: %s", fn, m.text) : 0;
-}
-
-// bases that are on the device already must be on THIS context's device (no peer access is set up)
-int check_dseqs(strk_ctx* c, const char* fn, const void* d_seqs) {
-    (void)hipSetDevice(c->device);
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, d_seqs) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != c->device) {
-        (void)hipGetLastError();
-        return fail(STRK_E_INVALID, "%s: d_seqs is not device memory of device %d (the context's)", fn, c->device);
-    }
-    return 0;
 }
 
 #include "strk_host_alleles.inc"
@@ -966,34 +983,28 @@ int strk_count_loci_dseqs(strk_ctx* ctx, const strk_batch* batch, const void* d_
     if (stats) memset(stats, 0, sizeof *stats);
     strk_batch d;
     int rc;
-    if (d_seqs) {   // bases that are on the device already must be on THIS context's device (no peer access is set up)
-        hipPointerAttribute_t attr;
-        if (hipPointerGetAttributes(&attr, d_seqs) != hipSuccess || attr.type != hipMemoryTypeDevice || attr.device != ctx->device) {
-            (void)hipGetLastError();
-            return fail(STRK_E_INVALID, "d_seqs is not device memory of device %d (the context's)", ctx->device);
-        }
-    }
-    if (!d_seqs) {   // host bases: large batches go through the pinned four-slot pipeline (strk_host_pipe.inc)
+    if (d_seqs) {
+        if ((rc = check_dseqs(ctx, "strk_count_loci_dseqs", d_seqs))) return rc;
+    } else {   // host bases: large batches go through the pinned four-slot pipeline (strk_host_pipe.inc)
         bool taken = false;
         rc = count_loci_pipelined(ctx, batch, params, out_cn, out_score, out_n_iters, out_start, stats, &taken);
         if (taken) return rc;
     }
-    if ((rc = upload_batch(ctx, batch, &d, nullptr, static_cast<const uint8_t*>(d_seqs)))) return rc;
+    hipStream_t st;
+    if ((rc = upload_batch(ctx, batch, &d, &st, static_cast<const uint8_t*>(d_seqs)))) return rc;
     if (batch->n_reads == 0 || batch->n_loci == 0) return 0;
     if (!batch->est_cn) return fail(STRK_E_INVALID, "est_cn is NULL");
-    const size_t nb = (size_t)batch->n_reads * 4;
-    if ((rc = ctx->out_cn.ensure(nb)) || (rc = ctx->out_score.ensure(nb)) || (rc = ctx->out_n.ensure(nb)) ||
-        (rc = ctx->out_start.ensure(nb)))
-        return rc;
-    rc = count_device(ctx, &d, params, ctx->out_cn.as<int32_t>(), ctx->out_score.as<int32_t>(), ctx->out_n.as<int32_t>(),
-                      ctx->out_start.as<int32_t>(), nullptr, stats);
+    const size_t nb = (size_t)batch->n_reads * 4, stride = (nb + 255) & ~(size_t)255;   // the four result arrays, 256-aligned
+    if ((rc = ctx->stage_out.ensure(4 * stride))) return rc;
+    int32_t* dev[4];
+    for (int k = 0; k < 4; ++k) dev[k] = ctx->stage_out.at<int32_t>(k * stride);
+    rc = count_device(ctx, &d, params, dev[0], dev[1], dev[2], dev[3], st, stats);
     if (rc && rc != STRK_E_EMPTY) return rc;
-    const int rc_keep = rc;
-    if (out_cn) HIP_TRY(hipMemcpy(out_cn, ctx->out_cn.p, nb, hipMemcpyDeviceToHost));
-    if (out_score) HIP_TRY(hipMemcpy(out_score, ctx->out_score.p, nb, hipMemcpyDeviceToHost));
-    if (out_n_iters) HIP_TRY(hipMemcpy(out_n_iters, ctx->out_n.p, nb, hipMemcpyDeviceToHost));
-    if (out_start) HIP_TRY(hipMemcpy(out_start, ctx->out_start.p, nb, hipMemcpyDeviceToHost));
-    return rc_keep;
+    int32_t* const host[4] = {out_cn, out_score, out_n_iters, out_start};
+    for (int k = 0; k < 4; ++k)
+        if (host[k]) HIP_TRY(hipMemcpyAsync(host[k], dev[k], nb, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return rc;
 }
 
 int strk_repeat_count(strk_ctx* ctx, int32_t start_count, const uint8_t* tr, int32_t tr_len, const uint8_t* fl,
@@ -1003,7 +1014,7 @@ int strk_repeat_count(strk_ctx* ctx, int32_t start_count, const uint8_t* tr, int
     if (!ctx) return fail(STRK_E_INVALID, "ctx is NULL");
     if (tr_len < 0 || fl_len < 0 || fr_len < 0 || motif_len < 1) return fail(STRK_E_INVALID, "bad sequence length");
     if ((tr_len && !tr) || (fl_len && !fl) || (fr_len && !fr) || !motif) return fail(STRK_E_INVALID, "sequence pointer is NULL");
-    const int32_t window = std::min(15, std::max(kDefaultWindow, local_search_range + step_size + 1));
+    const strk_params p = default_params(max_iters, local_search_range, step_size);
     int32_t cn = 0, sc = 0, n = 0, st = 0;
     auto done = [&] {
         if (out_cn) *out_cn = cn;
@@ -1011,25 +1022,15 @@ int strk_repeat_count(strk_ctx* ctx, int32_t start_count, const uint8_t* tr, int
         if (out_n_explored) *out_n_explored = n;
         return 0;
     };
-    const int rf = scalar_fast(ctx, start_count, tr, tr_len, fl, fl_len, fr, fr_len, motif, motif_len, max_iters, local_search_range,
-                               step_size, window, &cn, &sc, &n);
+    const int rf = scalar_fast(ctx, start_count, tr, tr_len, fl, fl_len, fr, fr_len, motif, motif_len, p, &cn, &sc, &n);
     if (rf < 0) return rf;
     if (rf == 0) return done();
     std::vector<uint8_t> seq((size_t)fl_len + tr_len + fr_len);
     if (fl_len) memcpy(seq.data(), fl, (size_t)fl_len);
     if (tr_len) memcpy(seq.data() + fl_len, tr, (size_t)tr_len);
     if (fr_len) memcpy(seq.data() + fl_len + tr_len, fr, (size_t)fr_len);
-    const int64_t seq_off[2] = {0, (int64_t)seq.size()};
-    const int32_t read_off[2] = {0, 1}, motif_off[2] = {0, motif_len};
-    strk_batch b;
-    b.n_reads = 1; b.n_loci = 1;
-    b.seqs = seq.data(); b.seq_off = seq_off; b.nfl = &fl_len; b.ntr = &tr_len; b.nfr = &fr_len;
-    b.est_cn = &start_count; b.read_off = read_off; b.motifs = motif; b.motif_off = motif_off;
-    strk_params p;
-    memset(&p, 0, sizeof p);
-    p.max_iters = max_iters; p.local_search_range = local_search_range; p.step_size = step_size;
-    p.tie_rule = STRK_TIE_FIRST; p.end_flags = STRK_SG_ALL; p.feedback = 0;
-    p.window = window;
+    const OneRead head{{0, (int64_t)seq.size()}, {fl_len, tr_len, fr_len, start_count}, {0, 1}, {0, motif_len}};
+    const strk_batch b = one_read_batch(&head, seq.data(), motif);
     const int rc = strk_count_loci(ctx, &b, &p, &cn, &sc, &n, &st, nullptr);
     return rc ? rc : done();
 }

@@ -123,10 +123,8 @@ int ref_score_requests(strk_ctx* ctx, std::vector<RefJob*>& req) {
         }
     }
     std::vector<int32_t> sc((size_t)toff.back()), eq((size_t)toff.back());
-    strk_batch b;
-    b.n_reads = (int32_t)(2 * nj); b.n_loci = (int32_t)(2 * nj);
-    b.seqs = seqs.data(); b.seq_off = seq_off.data(); b.nfl = nfl.data(); b.ntr = ntr.data(); b.nfr = nfr.data();
-    b.est_cn = nullptr; b.read_off = read_off.data(); b.motifs = motifs.data(); b.motif_off = motif_off.data();
+    const strk_batch b{(int32_t)(2 * nj), (int32_t)(2 * nj), seqs.data(), seq_off.data(), nfl.data(), ntr.data(), nfr.data(), nullptr,
+                       read_off.data(), motifs.data(), motif_off.data()};
     const int rc = score_table_impl(ctx, &b, los.data(), ns.data(), toff.data(), STRK_DB_END_FREE, 0, 1, sc.data(), eq.data(), nullptr);
     if (rc) return rc;
     for (size_t q = 0; q < nj; ++q) {
@@ -195,15 +193,9 @@ int ref_repeat_count_batch_impl(strk_ctx* ctx, std::vector<RefJob>& jobs, int32_
             read_off.push_back(read_off.back() + 1);
             motif_off.push_back(motif_off.back() + jobs[i].m);
         }
-        strk_batch b;
-        b.n_reads = (int32_t)grp.size(); b.n_loci = (int32_t)grp.size();
-        b.seqs = seqs.data(); b.seq_off = seq_off.data(); b.nfl = a_nfl.data(); b.ntr = a_ntr.data(); b.nfr = a_nfr.data();
-        b.est_cn = a_est.data(); b.read_off = read_off.data(); b.motifs = motifs.data(); b.motif_off = motif_off.data();
-        strk_params p;
-        memset(&p, 0, sizeof p);
-        p.max_iters = jobs[g].max_iters; p.local_search_range = jobs[g].lsr; p.step_size = jobs[g].step;
-        p.tie_rule = STRK_TIE_FIRST; p.end_flags = STRK_SG_ALL; p.feedback = 0;
-        p.window = std::min(15, std::max(kDefaultWindow, jobs[g].lsr + jobs[g].step + 1));   // as strk_repeat_count
+        const strk_batch b{(int32_t)grp.size(), (int32_t)grp.size(), seqs.data(), seq_off.data(), a_nfl.data(), a_ntr.data(), a_nfr.data(),
+                           a_est.data(), read_off.data(), motifs.data(), motif_off.data()};
+        const strk_params p = default_params(jobs[g].max_iters, jobs[g].lsr, jobs[g].step);   // as strk_repeat_count
         std::vector<int32_t> cn(grp.size()), sc(grp.size()), ni(grp.size());
         const int rc = strk_count_loci(ctx, &b, &p, cn.data(), sc.data(), ni.data(), nullptr, nullptr);
         if (rc) return rc;

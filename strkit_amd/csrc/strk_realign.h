@@ -27,6 +27,7 @@
 #include <type_traits>
 
 #include "strk_kernels.h"
+#include "strk_realign_plan.h"
 
 namespace strk {
 
@@ -39,20 +40,7 @@ constexpr int kTagDiag = 8;            // bits 3:2 = 2
 constexpr int kTagMask = 12;
 constexpr int kFlagGiExt = 1, kFlagGdExt = 2;
 
-struct RealignPair {
-    int64_t s1_off, s2_off;      // into the raw base arrays
-    int64_t trace_off;           // bytes into the trace workspace
-    int64_t edge_off;            // ints into the edge scratch (2 * 2 * n2 ints, tiles ping-pong), -1: single tile
-    int64_t cig_off;             // uint32 units into the CIGAR buffer
-    int32_t n1, n2;
-    int32_t cl;                  // columns per lane: 4, 8, 16, 32
-    int32_t ntiles;
-    int32_t pad;                 // pad columns on the left of tile 0
-    int32_t cig_cap;
-    int32_t orig;                // caller's pair index
-    int32_t reserved;
-};
-
+// (RealignPair, what the host lays out for one pair: strk_realign_plan.h)
 struct RealignArgs {
     const RealignPair* pairs;    // sorted by decreasing work
     int32_t n_pairs;

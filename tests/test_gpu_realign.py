@@ -12,8 +12,8 @@ from strkit_amd.realign import (get_aligned_pair_matches, perform_realign, reali
 pytestmark = pytest.mark.gpu
 
 
-def check_pairs(refs, reads, open_=7, ext=0, gap_pref=0):
-    got = realign_pairs(refs, reads, open_, ext, gap_pref)
+def check_pairs(refs, reads, open_=7, ext=0, gap_pref=0, context=None):
+    got = realign_pairs(refs, reads, open_, ext, gap_pref, context=context)
     for p, (r, q) in enumerate(zip(refs, reads)):
         sc, e2, cg = oracle.realign(r, q, open_, ext, gap_pref)
         assert got[p][0] == sc, (p, len(r), len(q), got[p][0], sc)

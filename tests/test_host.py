@@ -767,3 +767,18 @@ def test_allele_call_checkers_accept_and_refuse_what_they_should(tmp_path):
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr
     assert " 0 failed" in run.stdout, run.stdout
+
+
+def test_realign_planner_accepts_refuses_and_lays_out_what_it_should(tmp_path):
+    """Host build of tools/realign_asan.cpp (no HIP in strk_realign_plan.h): strk_realign's input check over every refusal, by
+    its message, and the invariants of the plan (chunks, order, trace / edge / CIGAR ranges) over random valid calls and trace
+    budgets from 1 MiB up, arrays of exactly their length; the program counts its own failures and exits 0 without one."""
+    import shutil
+    import subprocess
+    if shutil.which("g++") is None:
+        pytest.skip("no host C++ compiler")
+    exe = tmp_path / "realign_plan"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-o", str(exe), os.path.join(ROOT, "tools", "realign_asan.cpp")], check=True)
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert " 0 failed" in run.stdout, run.stdout
