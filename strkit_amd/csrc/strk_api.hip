@@ -194,8 +194,11 @@ using namespace strk;
 constexpr int kDefaultWindow = 8;
 enum { kEvStart = 0, kEvHead, kEvBand, kEvWide, kEvPre, kEvExact, kEvLong, kEvGeneric, kEvEnd, kNumEvents };
 constexpr int kBandProbationReads = 2048;
-// defaults of BandTune (strk_search.h): the band is laid around the table's middle +- kBandSpanW candidate sizes
-constexpr int kBandSpanW = 64, kBandSlackM8 = 0;
+// defaults of BandTune (strk_search.h): the band is laid around the table's middle +- kBandSpanW candidate sizes for motifs of up
+// to kBandSpanMaxMotif bases (the window buckets whose table is +-6 or +-8 sizes), around the whole table for longer ones.
+// Off (64 covers every table): +-4 for motifs of up to 6 bases was measured again in round 15 with two calls in flight and lost
+// 12-19 % of the headline to the reads it stops certifying (profiles/r15_band_order.txt); the knobs stay as tuning aids.
+constexpr int kBandSpanW = 64, kBandSlackM8 = 0, kBandSpanMaxMotif = 6;
 // Scratch pool (int32 units): kLongWaves slots of kLongSlotInts for k_dp_long (one per resident wave; a slot
 // holds the backward row of all column tiles + two boundary columns: windows up to ~16 kb), then 16 Mi
 // ints of H rows for the generic kernel.  448 MiB of the 288 GB, allocated once per context.
@@ -273,7 +276,7 @@ KArgs make_args(strk_ctx* c, const strk_batch* b, int end_flags, int window, int
     a.long_slot = (long long)c->long_slot_ints;
     a.long_waves = kLongWaves;
     a.list_stride = list_stride;
-    a.band_tune = {kBandSpanW, kBandSlackM8};
+    a.band_tune = {kBandSpanW, kBandSlackM8, kBandSpanMaxMotif};
     a.end_flags = end_flags;
     a.window = window;
     for (int k = 0; k < kWinBuckets; ++k) a.window_b[k] = c->p_window_b[k] > 0 ? c->p_window_b[k] : window;

@@ -175,9 +175,9 @@ __device__ __forceinline__ void band_pass(const BandCtx& x, const uint8_t* rowsy
     wordO = row_word(psym[1]);
     // class byte entering the lane's window after step t: column jb0 + t + D
     lds_cu8 pnb = (lds_cu8)(x.selb + col_addr(jb0 + D)) - (BWD ? 1 : 0);
-#define STRK_BAND_STEP(SRC, DST, TT, ODD, EDGE)                                                    \
+#define STRK_BAND_STEP(SRC, DST, TT, ODD, EDGE, FORK)                                              \
     {                                                                                              \
-        STRK_BAND_FORK(SRC, (TT) - 1)                                                              \
+        if (FORK) { STRK_BAND_FORK(SRC, (TT) - 1) }                                                \
         const uint2 word = (ODD) ? wordO : wordE;                                                  \
         unsigned sym2 = (unsigned)psym[2 + (ODD)];                      /* row of step TT + 2 */   \
         unsigned nb = pnb[BWD ? 1 - (ODD) : (ODD)];                                                \
@@ -246,7 +246,14 @@ __device__ __forceinline__ void band_pass(const BandCtx& x, const uint8_t* rowsy
     const int tL0 = wave_min_over_groups(hasL ? -dlo_ : 0x3fffffff) & ~1;
     const int tL1 = wave_max_over_groups(hasL ? -dlo_ : -1);
     // runs of plain pairs and runs of boundary pairs alternate, each run a loop of its own (one loop with both forms in
-    // its body makes the compiler copy the two row arrays once per pair)
+    // its body makes the compiler copy the two row arrays once per pair).
+    // The plain pairs in front of the wave's first event run without the fork-row test (compare, saveexec, a mostly-taken
+    // branch per step): such a pair is ONE basic block.  A step tests for the event of the step before it, and no lane's
+    // first event falls before fork0 - 1 (forward: fork rows exist in the last (n - 1) m + G steps only) or nrows - 1
+    // (backward: the one event, in the last G steps), so the pairs below tF, the wave's earliest such step rounded down to
+    // a pair, skip no event.  The few boundary pairs keep the test wherever they fall (a third form of them would be code
+    // for a handful of steps).
+    const int tF = min(T, wave_min_over_groups(BWD ? (nrows > 0 ? nrows - 1 : 0x3fffffff) : (nEff > 0 ? fork0 - 1 : 0x3fffffff)) & ~1);
     auto advance = [&]() {
         psym += 2;
         if (FLY) {   // psym -= flyP when it has passed flyEnd — without a select (sub, ashr, and, sub: four fast-class instructions)
@@ -263,14 +270,19 @@ __device__ __forceinline__ void band_pass(const BandCtx& x, const uint8_t* rowsy
         int ts = T;                                    // the next boundary pair at or after t
         if (tTop >= t) ts = min(ts, tTop);
         if (tL1 >= t) ts = min(ts, max(tL0, t));
+        for (const int tn = min(ts, tF); t < tn; t += 2) {
+            STRK_BAND_STEP(Ha, Hb, t, 0, false, false)
+            STRK_BAND_STEP(Hb, Ha, t + 1, 1, false, false)
+            advance();
+        }
         for (; t < ts; t += 2) {
-            STRK_BAND_STEP(Ha, Hb, t, 0, false)
-            STRK_BAND_STEP(Hb, Ha, t + 1, 1, false)
+            STRK_BAND_STEP(Ha, Hb, t, 0, false, true)
+            STRK_BAND_STEP(Hb, Ha, t + 1, 1, false, true)
             advance();
         }
         for (; t < T && (t == tTop || (t >= tL0 && t <= tL1)); t += 2) {
-            STRK_BAND_STEP(Ha, Hb, t, 0, true)
-            STRK_BAND_STEP(Hb, Ha, t + 1, 1, true)
+            STRK_BAND_STEP(Ha, Hb, t, 0, true, true)
+            STRK_BAND_STEP(Hb, Ha, t + 1, 1, true, true)
             advance();
         }
     }

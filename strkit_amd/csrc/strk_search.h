@@ -194,15 +194,22 @@ constexpr int kBandNarrowSlack = 22; // diagonals a 12-diagonal class keeps free
 // Slack per side: |db| / 32 (a HiFi read's score deficit grows with its length), at least 12 (22 in the 12-diagonal classes),
 // and slack_m8 / 8 diagonals per motif base: a search window that does not hold the best size has its maximum about 7 |motif| under
 // the perfect score (one copy too many or too few), and the 2 * len(diagonal) bound of its inexact entries must stay below that.
+// Round 15 tried span_w = 4 for motifs of up to six bases (max_m) as the default, with two calls in flight: half of BASELINE config
+// 2's band reads move from the 128- to the 96-diagonal class, but a search that starts a size off the best one (the caller's
+// feedback) no longer certifies there (the best size's neighbours have 22 diagonals of slack, not 27-33), and those reads cost
+// more in the exact kernels, or as host rounds, than the band saves (profiles/r15_band_order.txt).  Still off.
 struct BandTune {
     int32_t span_w;     // half-width (in candidate sizes) of the table's middle that the band is laid around
     int32_t slack_m8;   // slack per side >= slack_m8 * |motif| / 8 diagonals
+    int32_t max_m;      // span_w applies to motifs of at most max_m bases, longer ones get the whole table (0: to every motif)
 };
-constexpr BandTune kBandTuneNone = {64, 0};   // the whole table, no motif term (the geometry of rounds 2-3)
+constexpr int32_t kBandSpanWhole = 64;        // a span_w that covers every table (kTableMax entries)
+constexpr BandTune kBandTuneNone = {kBandSpanWhole, 0, 0};   // the whole table, no motif term (the geometry of rounds 2-3)
+STRK_HD int32_t band_span_w(BandTune tune, int32_t m) { return (tune.max_m > 0 && m > tune.max_m) ? kBandSpanWhole : tune.span_w; }
 
-// the inner candidates [c_lo, c_hi] of a table [lo, lo + n)
-STRK_HD void band_inner(int32_t lo, int32_t n, int32_t span_w, int32_t* c_lo, int32_t* c_hi) {
-    int32_t t = (n - 1) / 2 - span_w;
+// the inner candidates [c_lo, c_hi] of a table [lo, lo + n) of a motif of m bases
+STRK_HD void band_inner(int32_t lo, int32_t n, BandTune tune, int32_t m, int32_t* c_lo, int32_t* c_hi) {
+    int32_t t = (n - 1) / 2 - band_span_w(tune, m);
     if (t < 0) t = 0;
     *c_lo = lo + t;
     *c_hi = lo + n - 1 - t;
@@ -213,7 +220,7 @@ STRK_HD BandGeo band_geometry(int32_t nfl, int32_t ntr, int32_t nfr, int32_t m, 
     const int64_t ndb = (int64_t)nfl + ntr + nfr;
     if (nfl < 1 || nfr < 1 || nfr > kBandMaxFlank || m < 1 || m > 256 || n < 1 || n > 32) return b;
     int32_t c_lo, c_hi;
-    band_inner(lo, n, tune.span_w, &c_lo, &c_hi);
+    band_inner(lo, n, tune, m, &c_lo, &c_hi);
     const int64_t e_lo = (int64_t)ntr - (int64_t)c_hi * m, e_hi = (int64_t)ntr - (int64_t)c_lo * m;
     const int64_t span_lo = e_lo < 0 ? e_lo : 0, span_hi = e_hi > 0 ? e_hi : 0;
     // slack on each side: the certificate needs about half the score deficit of the read, and a HiFi read's deficit grows
@@ -256,7 +263,7 @@ STRK_HD BandGeo band_geometry(int32_t nfl, int32_t ntr, int32_t nfr, int32_t m, 
 STRK_HD BandGeo band_geometry_of_class(int32_t cls, int32_t nfl, int32_t ntr, int32_t m, int32_t lo, int32_t n, BandTune tune = kBandTuneNone) {
     BandGeo b;
     int32_t c_lo, c_hi;
-    band_inner(lo, n, tune.span_w, &c_lo, &c_hi);
+    band_inner(lo, n, tune, m, &c_lo, &c_hi);
     const int32_t e_lo = ntr - c_hi * m, e_hi = ntr - c_lo * m;
     const int32_t span_lo = e_lo < 0 ? e_lo : 0, span_hi = e_hi > 0 ? e_hi : 0;
     const int32_t wd = band_class_wd(cls);
