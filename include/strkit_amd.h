@@ -563,6 +563,49 @@ int strk_read_coords_both(const uint32_t* cigar, int32_t n_cigar, int64_t start,
 /* strk_bgzf_inflate's contract, served by the DEVICE inflater's code compiled for the host, one thread (test aid) */
 int64_t strk_bgzf_inflate_sw(const uint8_t* comp, int64_t n_comp, uint8_t* out, int64_t out_cap);
 
+/* ---- inputs of strk_call_alleles_phased read from an alignment file (the rule: DESIGN.md §13, frontend/phase_inputs.py) --
+ * Stands where the reference reads STRkitAlignedSegment.hp / .ps and calls process_read_snvs_for_locus_and_calculate_useful_snvs
+ * (strkit_rust_ext, not in its tree; call sites strkit/call/call_locus.py:1147-1260).
+ *
+ * strk_phase_cells: item i = (record at rec_off[i], locus item_locus[i]); locus l has the candidate SNV positions
+ * cand_pos[cand_off[l] .. cand_off[l+1]) (0-based, ascending, distinct, at most 1 024).  alt_* as in strk_extract_reads: an item
+ * with a substitute CIGAR is walked along that one.  Per item: out_hp / out_ps = its HP and PS tags (types c C s S i I, values
+ * that fit an int32; -1 / -1 unless both are present), and one cell per candidate of its locus, items back to back in item
+ * order (cell_cap >= their number): out_base = the read's base under the alignment as ASCII, '_' inside a deletion, '-'
+ * outside [lo, hi) and inside a reference skip, out_qual = its quality (0 without qualities and for '-' / '_').
+ * lo = first aligned reference base + (take_in if the left soft clip >= clip_threshold), hi likewise from the right.
+ * A malformed record, or an auxiliary chain that runs past its record, is STRK_E_INVALID naming the item. */
+int strk_phase_cells(const uint8_t* buf, int64_t n_bytes, int32_t n_items, const int64_t* rec_off, const int32_t* item_locus,
+                     int32_t n_loci, const int32_t* cand_off /*[n_loci+1]*/, const int64_t* cand_pos, const uint32_t* alt_cigar,
+                     const int64_t* alt_cigar_off, const int64_t* alt_start, int32_t clip_threshold, int32_t take_in, int32_t* out_hp,
+                     int32_t* out_ps, uint8_t* out_base, uint8_t* out_qual, int64_t cell_cap);
+/* strk_useful_snvs: over the cells of a strk_phase_cells call with the same n_items, item_locus, n_loci and cand_off.  Locus l
+ * keeps the reads kept_item[kept_off[l] .. kept_off[l+1]) (items of that locus, in read order), n of them.  A candidate is
+ * useful iff at least two distinct bytes other than '-' and '_' each occur >= max(rint(n / 5.0), min_allele_reads) times among
+ * its cells of the kept reads and those bytes number >= max(rint(n * 0.55), 5) in all (float64, round half to even); the first
+ * 64 in ascending position are taken.  out_snv_off [n_loci+1]; out_snv_cand (room for 64 * n_loci) = per useful SNV its index
+ * among the locus's candidates; out_base / out_qual = the kept reads' cells of the useful SNVs, read-major per locus, loci
+ * back to back: what strk_call_alleles_phased takes as snv_base / snv_qual.  Returns the number of packed cells; when it
+ * exceeds cap no cell is written (a size query), everything else is. */
+int64_t strk_useful_snvs(int32_t n_items, const int32_t* item_locus, int32_t n_loci, const int32_t* cand_off, const uint8_t* cells_base,
+                         const uint8_t* cells_qual, const int32_t* kept_off /*[n_loci+1]*/, const int32_t* kept_item,
+                         int32_t min_allele_reads, int32_t* out_snv_off, int32_t* out_snv_cand, uint8_t* out_base, uint8_t* out_qual,
+                         int64_t cap);
+/* The same two over the file resident on the device.  strk_dbam_phase_cells (kernel k_dbam_phase_cells: one wave per item) leaves
+ * the cells in HBM, owned by the object until its next call (at most 512 MB of them: STRK_E_NOMEM beyond, call it for fewer loci);
+ * the tags come back.  piece_items > 0 cuts the LAUNCHES into that many items each (every item's cells have their place in the one
+ * workspace, so the result does not depend on it and the workspace is not made smaller by it): a caller whose cells would exceed
+ * the workspace splits its loci over several pairs of calls, as frontend/phase_block.py does.
+ * strk_dbam_useful_snvs (k_snv_useful: one workgroup per locus, then k_snv_gather) works on those cells.
+ * strk_dbam_download_cells copies them to the host (tests; n_cells must be their number). */
+int strk_dbam_phase_cells(strk_dbam* d, int32_t n_items, const int64_t* rec_off, const int32_t* item_locus, int32_t n_loci,
+                          const int32_t* cand_off, const int64_t* cand_pos, const uint32_t* alt_cigar, const int64_t* alt_cigar_off,
+                          const int64_t* alt_start, int32_t clip_threshold, int32_t take_in, int32_t piece_items, int32_t* out_hp,
+                          int32_t* out_ps);
+int strk_dbam_download_cells(strk_dbam* d, int64_t n_cells, uint8_t* out_base, uint8_t* out_qual);
+int64_t strk_dbam_useful_snvs(strk_dbam* d, int32_t n_loci, const int32_t* kept_off, const int32_t* kept_item, int32_t min_allele_reads,
+                              int32_t* out_snv_off, int32_t* out_snv_cand, uint8_t* out_base, uint8_t* out_qual, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

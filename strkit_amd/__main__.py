@@ -43,6 +43,11 @@ def build_parser() -> argparse.ArgumentParser:
                         "default when the flag stands alone; needs --call-alleles), or both")
     # same names as `strkit call` (strkit/entry.py:20-342); --seed seeds the allele caller (the per-read path has no random
     # component), --processes sizes the locus blocks as the reference does (loci.py:193)
+    c.add_argument("--use-hp", action="store_true", help="group reads by their HP / PS tags where a locus has enough tagged reads (needs --call-alleles)")
+    c.add_argument("--incorporate-snvs", "--snv", "-v", dest="incorporate_snvs", default=None, metavar="PATH",
+                   help="VCF (plain or gzip) of candidate SNVs: reads are grouped by the bases they carry at them (needs --call-alleles)")
+    c.add_argument("--snv-min-base-qual", type=int, default=20)
+    c.add_argument("--significant-clip-threshold", type=int, default=100)
     c.add_argument("--sample-id", default=None)
     c.add_argument("--processes", type=int, default=1)
     c.add_argument("--seed", type=int, default=None)
@@ -61,6 +66,8 @@ def main(argv=None) -> int:
         ap.error("--max-mdn-poa-length must be >= 0")
     if a.count_kmers in ("peak", "both") and not a.call_alleles:
         ap.error(f"--count-kmers {a.count_kmers} needs --call-alleles")
+    if (a.use_hp or a.incorporate_snvs) and not a.call_alleles:
+        ap.error("--use-hp / --incorporate-snvs need --call-alleles")
     import os
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:   # python -m torch.distributed.run --nproc-per-node N -m strkit_amd call ...: one rank per GPU
@@ -78,6 +85,8 @@ def main(argv=None) -> int:
                       sample_id=a.sample_id, processes=a.processes, rc_params=rc,
                       min_read_align_score=a.min_read_align_score, front_end=a.front_end, span_bytes=a.span_mb << 20,
                       count_kmers=a.count_kmers, consensus_method=a.consensus_method, max_mdn_poa_length=a.max_mdn_poa_length,
+                      **(dict(use_hp=a.use_hp, snv_vcf=a.incorporate_snvs, snv_min_base_qual=a.snv_min_base_qual,
+                              significant_clip_threshold=a.significant_clip_threshold) if a.use_hp or a.incorporate_snvs else {}),
                       **(dict(call_alleles=True, consensus=a.consensus or bool(a.vcf), seed=a.seed, n_alleles=a.n_alleles)
                          if a.call_alleles else {}))
     if world > 1:

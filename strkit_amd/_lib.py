@@ -74,7 +74,8 @@ EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk
            "strk_call_alleles_phased",
            "strk_best_representatives", "strk_best_representatives_dseqs",
            "strk_count_kmers", "strk_count_kmers_dseqs", "strk_count_kmers_ws",
-           "strk_consensus", "strk_consensus_dseqs", "strk_consensus_ws")
+           "strk_consensus", "strk_consensus_dseqs", "strk_consensus_ws",
+           "strk_phase_cells", "strk_useful_snvs", "strk_dbam_phase_cells", "strk_dbam_download_cells", "strk_dbam_useful_snvs")
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -221,6 +222,20 @@ def load(build: bool = True):
         L.strk_consensus_ws.restype = C.c_int64
         L.strk_consensus_ws.argtypes = ([C.c_void_p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 2
                                         + [C.c_int32, C.c_int64] + [C.c_void_p] * 4 + [C.c_int32, C.c_int64, C.POINTER(StrkStats)])
+        L.strk_phase_cells.restype = C.c_int
+        L.strk_phase_cells.argtypes = ([C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
+                                       + [C.c_int32] * 2 + [C.c_void_p] * 4 + [C.c_int64])
+        L.strk_useful_snvs.restype = C.c_int64
+        L.strk_useful_snvs.argtypes = ([C.c_int32, C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 4
+                                       + [C.c_int64])
+        L.strk_dbam_phase_cells.restype = C.c_int
+        L.strk_dbam_phase_cells.argtypes = ([C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 5
+                                            + [C.c_int32] * 3 + [C.c_void_p] * 2)
+        L.strk_dbam_download_cells.restype = C.c_int
+        L.strk_dbam_download_cells.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.strk_dbam_useful_snvs.restype = C.c_int64
+        L.strk_dbam_useful_snvs.argtypes = ([C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
+                                            + [C.c_int64])
         L.strk_device_mem.restype = C.c_int
         L.strk_device_mem.argtypes = [C.c_int, _i64p, _i64p]
         L.strk_realign_i16_flags.restype = C.c_int

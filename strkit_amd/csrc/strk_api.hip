@@ -12,6 +12,7 @@
 //   strk_host_kmers.inc      distinct windows (k-mer counts)                 strk_host_phase.inc      phased allele calls
 //   strk_host_files.inc      the CPU-only file front end (its parser: strk_frontend.h)
 //   strk_dbam.inc            (at the end) the alignment file on the device: BGZF inflater, record scan, read extraction
+//   strk_phase_inputs.inc    (after it) tags, SNV cells and useful SNVs for the phased call: host twins and device entry points (walks and kernels: strk_phase_inputs.h)
 //
 // One context = one HIP device.  A batched call enqueues, on the caller's stream:
 //   memset(counters) -> k_hash -> k_plan -> k_dp_band -> k_dp_band_wide -> k_dp_all -> k_dp_long -> k_dp_generic -> k_replay
@@ -23,6 +24,7 @@
 #include "strk_policy.h"
 #include "strk_groups.h"
 #include "strk_phase_check.h"
+#include "strk_phase_inputs.h"
 
 #include <algorithm>
 #include <array>
@@ -1241,3 +1243,4 @@ int strk_realign_i16_flags(int32_t n_pairs, const int64_t* s1_off, const int64_t
 }  // extern "C"
 
 #include "strk_dbam.inc"
+#include "strk_phase_inputs.inc"

@@ -232,6 +232,12 @@ struct strk_dbam {
     int device = 0;
     DevBuf comp, blocks, data, lens, status;
     DevBuf w_a, w_b, w_c, w_d, w_e, w_f, seqs;   // scan / extraction work buffers, the extracted bases
+    // strk_dbam_phase_cells (strk_phase_inputs.inc): the cells of its last call (base | quality), their offsets per item and the
+    // candidate offsets on the device, and what strk_dbam_useful_snvs checks its input against
+    DevBuf pc_cells, pc_cell_off, pc_cand_off, pc_in, pc_work;
+    std::vector<int32_t> pc_item_locus, pc_cand_off_h;
+    std::vector<int64_t> pc_cell_off_h;
+    bool pc_valid = false;
     int64_t n_data = 0;    // bytes of `data` that are filled
     int64_t coff0 = 0;     // compressed offset of the inflated stretch
     PinnedBuf ring_mem;                     // strk_dbam_inflate_file: pinned pieces, their stream and events

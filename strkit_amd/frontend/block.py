@@ -14,11 +14,12 @@ from ..segment import calculate_seq_with_wildcards
 from ..synth import LocusBatch
 from .bam import BamFile
 from .extract import LowMeanBaseQual, get_read_coords_from_cigar, get_read_coords_from_matched_pairs, get_sequence_data_for_locus
-from .genotype import block_consensus, block_kmers, call_block_alleles, genotype_row, kmers_row
+from .genotype import block_consensus, block_kmers, call_block_alleles, call_block_alleles_phased, genotype_row, kmers_row
 from .loci import Locus
 from .native import extract_raw_slices, extract_reads, realign_cigar_to_read_alignment
 from .options import VCF_ANCHOR_SIZE, CallOptions
 from .output import block_read_weights, read_weights
+from .phase_block import native_block_phase, phase_row, python_block_phase
 
 
 def _locus_dict(locus: Locus) -> dict:
@@ -52,15 +53,18 @@ def _count(batch: LocusBatch, opts: CallOptions, ctx, tm=None):
     return res, filter_reads(batch, res, opts.min_read_align_score)
 
 
-def _genotype_tail(loci, n_kept, cn, ws, slices, opts: CallOptions, ctx, tm):
+def _genotype_tail(loci, n_kept, cn, ws, slices, opts: CallOptions, ctx, tm, phase=None):
     """The genotype tail of both block paths -> (al, cons, kmers), None for what is off: allele calls of the live `loci` over
     their kept reads (locus l owns the next n_kept[l] entries of `cn` / `ws`) and, with `consensus` or `count_kmers`, allele
     sequences and k-mer counts.  `slices()` is asked only then, and once: (tract_start, tract_len, anchor_start, anchor_len) of
-    every kept read inside one buffer, and that buffer as the keywords of genotype.block_consensus (`seqs`, or `d_seqs` ...)."""
+    every kept read inside one buffer, and that buffer as the keywords of genotype.block_consensus (`seqs`, or `d_seqs` ...).
+    `phase()` (with a switch of PhasedCallOptions on: call_blocks then hands its PhaseRun to the block paths): the block's phase_block.BlockPhase; the calls are then the phased ones,
+    and the consensus and k-mer stages take their read peaks unchanged."""
     want_kmers = opts.count_kmers != "none"
     al = cons = kmers = None
     if opts.call_alleles:
-        al = call_block_alleles(loci, n_kept, cn, ws, opts, ctx, tm)
+        al = (call_block_alleles_phased(loci, n_kept, cn, ws, opts, ctx, tm, phase()) if phase is not None
+              else call_block_alleles(loci, n_kept, cn, ws, opts, ctx, tm))
     if (opts.consensus or want_kmers) and len(cn):      # (no kept read: nothing to cut, and both stages would return nothing)
         t_start, t_len, a_start, a_len, where = slices()
         if opts.consensus:
@@ -71,7 +75,7 @@ def _genotype_tail(loci, n_kept, cn, ws, slices, opts: CallOptions, ctx, tm):
     return al, cons, kmers
 
 
-def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data):
+def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data, phase_run=None):
     """One block through bam.py / extract.py (the readable statement of the front end): (rows, reads kept).  `ref_data`: the
     reference side of every locus of the block (refside.get_loci_with_ref_data)."""
     flank_size = opts.flank_size
@@ -130,7 +134,8 @@ def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data
     t_a = time.perf_counter()
     res, flt = _count(batch, opts, ctx)
     tm["count_s"] += time.perf_counter() - t_a
-    recs_of, pairs = [], []
+    recs_of, pairs, kept_of = [], [], []
+    seg_of = [{e[0].name: e for e in entries} for _, _, entries in prepared] if phase_run is not None else None
     for li, (locus, rd, _) in enumerate(prepared):
         r0, r1 = int(batch.read_off[li]), int(batch.read_off[li + 1])
         kept = [r for r in range(r0, r1) if flt["keep"][r]]
@@ -150,6 +155,8 @@ def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data
             reads, raws = {}, {}
         results.append(_locus_row(locus, rd, reads, opts))
         recs_of.append(list(reads.values()))     # calls and k-mer counts are made from the records of the row
+        if seg_of is not None:
+            kept_of.append([(seg_of[li][name][0], bool(r.get("realn")), r["cn"]) for name, r in reads.items()])
         pairs.extend(raws.values())
 
     def slices():      # (raw anchor | raw tract) of every record, in row order, in one host buffer, as the native path has them
@@ -161,11 +168,16 @@ def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data
 
     al, cons, km = _genotype_tail([p[0] for p in prepared], np.array([len(x) for x in recs_of], np.int64),
                                   np.array([r["cn"] for x in recs_of for r in x], np.int32),
-                                  np.array([r["w"] for x in recs_of for r in x], np.float64), slices, opts, ctx, tm)
+                                  np.array([r["w"] for x in recs_of for r in x], np.float64), slices, opts, ctx, tm,
+                                  phase=(lambda: python_block_phase(phase_run, opts, [p[0] for p in prepared],
+                                                                    [[(e[0], e[1] is not None) for e in p[2]] for p in prepared], kept_of, tm))
+                                  if phase_run is not None else None)
     first = 0
     for li, row in enumerate(results[-len(prepared):]):
         if al is not None:
             genotype_row(row, al, li, recs_of[li], cons)
+            if "phase" in al:
+                phase_row(row, al, li, recs_of[li], prepared[li][0])
         if km is not None:
             kmers_row(row, km, li, recs_of[li], first)
         first += len(recs_of[li])
@@ -194,7 +206,7 @@ class BlockState:
     kmers: dict | None = None
 
 
-def _call_block_native(block, bam, opts: CallOptions, ctx, tm, ref_data):
+def _call_block_native(block, bam, opts: CallOptions, ctx, tm, ref_data, phase_run=None):
     """One block over the records of a NativeBam / an IndexedBam region / a DeviceBam, with no Python per read before the report:
     one vectorised interval query (`fetch_many`), ONE extraction call, one device call that counts, numpy filters
     (_block_device_stage); only the rows of the report are built read by read (_block_report_stage): (rows, reads kept)."""
@@ -202,11 +214,11 @@ def _call_block_native(block, bam, opts: CallOptions, ctx, tm, ref_data):
     live = [(locus, rd) for locus, rd in zip(block, ref_data) if rd is not None]
     if not live:
         return results, 0
-    rows, n_kept = _block_report_stage(_block_device_stage(live, bam, opts, ctx, tm), opts, tm)
+    rows, n_kept = _block_report_stage(_block_device_stage(live, bam, opts, ctx, tm, phase_run), opts, tm)
     return results + rows, n_kept
 
 
-def _block_device_stage(live, bam, opts: CallOptions, ctx, tm) -> BlockState:
+def _block_device_stage(live, bam, opts: CallOptions, ctx, tm, phase_run=None) -> BlockState:
     """Everything of a block's live loci that touches the reader and the device: interval query, extraction, counting, filters,
     the names of the reads that are kept, and the genotype tail."""
     flank_size = opts.flank_size
@@ -278,7 +290,9 @@ def _block_device_stage(live, bam, opts: CallOptions, ctx, tm) -> BlockState:
         # the raw tract and start anchor of every kept read: a second extraction, made only when the tail asks for it
         st.al, st.cons, st.kmers = _genotype_tail(
             [l for l, _ in live], np.bincount(read_locus[kept], minlength=len(live)), st.cn[kept], st.ws,
-            lambda: extract_raw_slices(st, bam, coords, VCF_ANCHOR_SIZE, opts.min_avg_phred, tm), opts, ctx, tm)
+            lambda: extract_raw_slices(st, bam, coords, VCF_ANCHOR_SIZE, opts.min_avg_phred, tm), opts, ctx, tm,
+            phase=(lambda: native_block_phase(phase_run, opts, [l for l, _ in live], bam, rec, item_locus.astype(np.int32), alt,
+                                              ok_items[kept], read_locus[kept], st.cn[kept], tm)) if phase_run is not None else None)
     return st
 
 
@@ -304,6 +318,8 @@ def _block_report_stage(st: BlockState, opts: CallOptions, tm):
         row = _locus_row(locus, rd, dict(zip(names[a:b], recs[a:b])), opts)
         if al is not None:
             genotype_row(row, al, li, recs[a:b], cons)
+            if "phase" in al:
+                phase_row(row, al, li, recs[a:b], locus)
         if km is not None:
             kmers_row(row, km, li, recs[a:b], a)
         results.append(row)

@@ -21,12 +21,14 @@ from .fasta import Fasta
 from .gather import _distributed, call_blocks_sharded, deal_locus_blocks
 from .loci import Locus, load_loci, resolve_contig
 from .native import DeviceBam, IndexedBam, NativeBam
-from .options import DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, PoaCallOptions, report_parameters, with_keywords
+from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, PhasedCallOptions, PoaCallOptions, phased, report_parameters,
+                      with_keywords)
+from .phase_block import PhaseRun
 from .reader import open_path
 from .refside import get_loci_with_ref_data, get_locus_with_ref_data, ref_side_of_blocks
 
 # (what moved to the other modules is still offered here under the names it had)
-__all__ = ["CallOptions", "PoaCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
+__all__ = ["CallOptions", "PoaCallOptions", "PhasedCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
 
 
 def call_locus(locus: Locus, bam: BamFile, ref: Fasta, *, ctx: _lib.Context | None = None, opts: CallOptions | None = None,
@@ -193,6 +195,7 @@ def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = Non
     re-run locus by locus so that only the locus that fails is lost; `stage times["errors"]` lists them."""
     opts = opts or CallOptions()
     opts.validate()
+    phase_run = PhaseRun(opts) if phased(opts) else None     # the candidate SNVs and the renumbering of the phase sets: one per run
     ctx = ctx or _lib.default_context()
     run_block = _call_block_native if isinstance(bam, (NativeBam, IndexedBam, DeviceBam)) else _call_block_python
     results: list[dict] = []
@@ -201,13 +204,18 @@ def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = Non
 
     def safe(block, records):
         nonlocal n_depth
+        ids = None
         try:
             t_a = time.perf_counter()      # (a chunk of the reference side that failed is computed again here, block by block)
             ref_data = ([ref_cache[id(l)] for l in block] if all(id(l) in ref_cache for l in block)
                         else get_loci_with_ref_data(block, ref, opts.respect_ref, ctx))
             tm["ref_side_s"] += time.perf_counter() - t_a
-            rows, n = run_block(block, records, opts, ctx, tm, ref_data)
+            ids = phase_run.remap.snapshot() if phase_run is not None else None
+            # (without a switch of PhasedCallOptions the block paths are called as they always were)
+            rows, n = run_block(block, records, opts, ctx, tm, ref_data, **({"phase_run": phase_run} if phase_run is not None else {}))
         except _lib.StrkError as e:
+            if ids is not None:     # the phase sets a failed block has numbered are numbered again by its re-run, from where it began
+                phase_run.remap.restore(ids)
             if len(block) > 1:
                 for locus in block:
                     safe([locus], records)

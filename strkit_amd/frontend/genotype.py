@@ -13,7 +13,7 @@ from ..alleles import CALLED, TOO_FEW, AlleleParams, call_alleles_batch, call_da
 from ..consensus import METHOD_NAMES, best_representatives_packed, consensus_packed
 from ..kmers import count_kmers_packed, dicts_of
 
-__all__ = ["n_alleles_of", "call_block_alleles", "peak_groups", "block_consensus", "genotype_row", "block_kmers", "kmers_row"]
+__all__ = ["n_alleles_of", "call_block_alleles", "call_block_alleles_phased", "peak_groups", "block_consensus", "genotype_row", "block_kmers", "kmers_row"]
 
 
 def n_alleles_of(n_alleles, contig: str) -> int:
@@ -47,6 +47,48 @@ def call_block_alleles(loci, n_kept: np.ndarray, cns: np.ndarray, ws: np.ndarray
     out["read_peak"] = rp
     out["n_alleles"] = nal
     out["read_off"] = np.concatenate(([0], np.cumsum(n_kept))).astype(np.int64)
+    tm["alleles_s"] = tm.get("alleles_s", 0.0) + time.perf_counter() - t_a
+    tm["alleles_device_s"] = tm.get("alleles_device_s", 0.0) + st["kernel_ms"] / 1e3
+    return out
+
+
+def call_block_alleles_phased(loci, n_kept: np.ndarray, cns: np.ndarray, ws: np.ndarray, opts, ctx, tm, phase) -> dict:
+    """call_block_alleles with the reads grouped by haplotags or SNVs where that applies: the same
+    normalisation of the weights, the same seeds, ONE call_alleles_phased_batch(..., fallback=True).  `phase`: the block's
+    phase_block.BlockPhase (hp / ps per kept read when use_hp, the useful SNVs' cells when snv_vcf).  Returns what
+    call_block_alleles returns plus method, reason, ps, the SNV outputs, `phase`, and `snv_base` / `cell_off` (the cells as the
+    call took them and the cells in front of every locus)."""
+    from ..phasing import PhaseParams, call_alleles_phased_batch
+    t_a = time.perf_counter()
+    n_loci = len(loci)
+    n_kept = np.asarray(n_kept, np.int64)
+    owner = np.repeat(np.arange(n_loci), n_kept)
+    w = np.asarray(ws, np.float64)
+    good = np.isfinite(w) & (w > 0)
+    bad_locus = np.bincount(owner[~good], minlength=n_loci) > 0
+    sel = ~bad_locus[owner]
+    sums = np.bincount(owner[sel], weights=w[sel], minlength=n_loci)
+    n_sel = np.where(bad_locus, 0, n_kept)
+    nal = np.array([n_alleles_of(opts.n_alleles, l.contig) for l in loci], np.int32)
+    seeds = locus_seeds(opts.seed, np.array([l.t_idx for l in loci], np.int64))
+    used = phase.without(bad_locus, n_kept)
+    pp = opts.phase_params or PhaseParams()
+    if pp.snv_quality_threshold != opts.snv_min_base_qual:
+        import dataclasses
+        pp = dataclasses.replace(pp, snv_quality_threshold=int(opts.snv_min_base_qual))
+    out, st = call_alleles_phased_batch(np.concatenate(([0], np.cumsum(n_sel))).astype(np.int32), np.asarray(cns, np.int32)[sel],
+                                        w[sel] / sums[owner[sel]], nal, seeds, hp=used.hp, ps=used.ps, snv_off=used.snv_off,
+                                        snv_base=used.snv_base, snv_qual=used.snv_qual, params=opts.allele_params or AlleleParams(),
+                                        phase_params=pp, fallback=True, ctx=ctx, with_stats=True)
+    rp = np.full(owner.shape[0], -1, np.int32)
+    rp[sel] = out["read_peak"]
+    out["read_peak"] = rp
+    out["n_alleles"] = nal
+    out["read_off"] = np.concatenate(([0], np.cumsum(n_kept))).astype(np.int64)
+    out["phase"] = phase
+    if used.snv_off is not None:
+        out["snv_base"] = used.snv_base
+        out["cell_off"] = np.concatenate(([0], np.cumsum(n_sel * np.diff(used.snv_off)))).astype(np.int64)
     tm["alleles_s"] = tm.get("alleles_s", 0.0) + time.perf_counter() - t_a
     tm["alleles_device_s"] = tm.get("alleles_device_s", 0.0) + st["kernel_ms"] / 1e3
     return out

@@ -8,6 +8,7 @@ from dataclasses import dataclass
 from .. import _lib
 from ..alleles import AlleleParams
 from ..batch import MIN_READ_ALIGN_SCORE
+from ..phasing import PhaseParams
 from ..repeat_count_params import RepeatCountParams
 from .extract import MIN_AVG_PHRED
 
@@ -85,10 +86,44 @@ class PoaCallOptions(CallOptions):
 POA_OPTION_NAMES = ("consensus_method", "max_mdn_poa_length")
 
 
+@dataclass
+class PhasedCallOptions(PoaCallOptions):
+    """PoaCallOptions plus the options of phasing from files.  `use_hp`: reads are grouped by their `HP` / `PS`
+    tags where a locus has enough tagged reads (`strkit call --use-hp`).  `snv_vcf`: a VCF of candidate SNVs; reads are
+    grouped by the bases they carry at the useful ones (`--incorporate-snvs`).  `snv_min_base_qual`: the quality a base needs
+    to count in an SNV call and distance.  `significant_clip_threshold`: the soft clip from which a read's ends are not
+    trusted for SNVs (strkit/call/params.py:61).  `phase_params`: the phased call's other parameters.  Both switches need
+    call_alleles.  A type of its own for the reason PoaCallOptions gives."""
+    use_hp: bool = False
+    snv_vcf: str | None = None
+    snv_min_base_qual: int = 20
+    significant_clip_threshold: int = 100
+    phase_params: PhaseParams | None = None
+
+    def validate(self) -> None:
+        super().validate()
+        if (self.use_hp or self.snv_vcf) and not self.call_alleles:
+            raise ValueError("use_hp / snv_vcf require call_alleles=True: they decide how the reads of a call are grouped")
+        for name in ("snv_min_base_qual", "significant_clip_threshold"):
+            v = getattr(self, name)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0 or (name == "snv_min_base_qual" and v > 255):
+                raise ValueError(f"{name} must be an integer >= 0 (a base quality: at most 255): got {v!r}")
+
+
+PHASE_OPTION_NAMES = ("use_hp", "snv_vcf", "snv_min_base_qual", "significant_clip_threshold", "phase_params")
+
+
+def phased(opts) -> bool:
+    """Whether a switch of PhasedCallOptions is on (any options type may be asked)."""
+    return bool(getattr(opts, "use_hp", False) or getattr(opts, "snv_vcf", None))
+
+
 def with_keywords(opts: CallOptions | None, **option_keywords) -> CallOptions:
     """`opts` (or the defaults) with the options given by name replaced: dataclasses.replace, after widening a plain
-    CallOptions to PoaCallOptions when one of POA_OPTION_NAMES is among them.  An unknown name is a TypeError."""
+    CallOptions to PoaCallOptions when one of POA_OPTION_NAMES is among them, and to PhasedCallOptions for PHASE_OPTION_NAMES.  An unknown name is a TypeError."""
     opts = opts or CallOptions()
+    if not isinstance(opts, PhasedCallOptions) and any(k in option_keywords for k in PHASE_OPTION_NAMES):
+        opts = PhasedCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, PoaCallOptions) and any(k in option_keywords for k in POA_OPTION_NAMES):
         opts = PoaCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     return dataclasses.replace(opts, **option_keywords)
@@ -109,4 +144,7 @@ def report_parameters(opts: CallOptions, processes: int) -> dict:
                 "max_n_large_consensus_reads": opts.max_n_large_consensus_reads} if opts.consensus else {}),
             **({"consensus_method": opts.consensus_method} if opts.consensus_method != "best_rep" else {}),
             **({"max_mdn_poa_length": opts.max_mdn_poa_length} if opts.max_mdn_poa_length != 5000 else {}),
-            **({"count_kmers": opts.count_kmers} if opts.count_kmers != "none" else {})}
+            **({"count_kmers": opts.count_kmers} if opts.count_kmers != "none" else {}),
+            **({"use_hp": True} if getattr(opts, "use_hp", False) else {}),
+            **({"snv_vcf": opts.snv_vcf, "snv_min_base_qual": opts.snv_min_base_qual} if getattr(opts, "snv_vcf", None) else {}),
+            **({"significant_clip_threshold": opts.significant_clip_threshold} if phased(opts) else {})}

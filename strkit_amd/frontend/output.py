@@ -165,6 +165,12 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
     formats = _FORMATS
     if any(_has_seqs(r) for r in report["results"]):
         formats = _FORMATS[:1] + _SEQ_FORMATS + _FORMATS[1:]
+    # phased rows: the two fields are declared only when a row carries them, so that a report without them
+    # gives the bytes it always gave
+    extra = ([("NSNV", "1", "Integer", "Number of supporting SNVs for the STR peak-call")] if any(r.get("snvs") for r in report["results"]) else []) + \
+            ([("PS", "1", "Integer", "Phase set")] if any(r.get("ps") is not None for r in report["results"]) else [])
+    if extra:
+        formats = tuple(sorted(formats + tuple(extra), key=lambda f: f[0]))
     sample = sample_id or report.get("sample_id") or "sample"
     now = datetime.now()  # noqa: DTZ005
     lines = ["##fileformat=VCFv4.2", "##fileDate=" + (date or f"{now.year}{now.month:02d}{now.day:02d}"), "##source=strkit_amd",
@@ -197,13 +203,17 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
             offset, raw, strings, gt_idx, methods = alleles
             anchor = anchor[offset:]
             start0 += offset
-            ref_allele, alt, gt = strings[0], ",".join(strings[1:]), "/".join(map(str, gt_idx))
+            ref_allele, alt, gt = strings[0], ",".join(strings[1:]), ("|" if row.get("ps") is not None else "/").join(map(str, gt_idx))
         if peaks:
             n_peaks = int(peaks["modal_n"])
         info = f"VT=str;MOTIF={row['motif']};REFMC={row['ref_cn']};BED_START={row['start']};BED_END={row['end']};ANCH={len(anchor)}"
         keys, vals = ["GT", "DP"], [gt, str(len(reads))]
         if row.get("assign_method"):
             keys.append("PM"); vals.append(str(row["assign_method"]))
+        if call and row.get("snvs"):
+            keys.append("NSNV"); vals.append(str(len(row["snvs"])))
+        if call and row.get("ps") is not None:
+            keys.append("PS"); vals.append(str(row["ps"]))
         if peaks:
             mmas = row.get("mean_model_align_score")
             keys += ["MMAS", "DPS", "AD"]
