@@ -606,6 +606,38 @@ int strk_dbam_download_cells(strk_dbam* d, int64_t n_cells, uint8_t* out_base, u
 int64_t strk_dbam_useful_snvs(strk_dbam* d, int32_t n_loci, const int32_t* kept_off, const int32_t* kept_item, int32_t min_allele_reads,
                               int32_t* out_snv_off, int32_t* out_snv_cand, uint8_t* out_base, uint8_t* out_qual, int64_t cap);
 
+/* ---- 5-methyl CpG calls of a read inside a locus's tract, from its MM / ML tags (the rule: DESIGN.md §14, frontend/methyl.py) --
+ * Stands where the reference calls STRkitAlignedSegment.get_methylation_prop(locus, 127, 0.0) (strkit_rust_ext, not in its tree;
+ * call site strkit/call/call_locus.py:1301-1305): the rule is this project's own, built from the SAM tags specification.
+ *
+ * strk_methyl: item i = (record at rec_off[i], locus boundaries coords[4i..4i+3]) and alt_* exactly as strk_extract_reads takes
+ * them.  The tract [q_l, q_r) is the bases that function returns as `tr`.  A site is a stored C inside the tract with a stored G
+ * behind it; the first C+m entry of MM (first occurrence of MM:Z / ML:B,C; Mm / Ml where a record has neither) says which of
+ * the read's Cs (as sequenced: the stored Gs from the end, for a reverse read) carry a call and ML its probability.
+ * out_status[i]: STRK_METHYL_OK; _NOT_SPANNING (extraction would refuse the item for a reason other than base quality);
+ * _NO_TAGS (no MM, or no C+m entry in it); _CLIPPED (an H in the record's CIGAR, or an MN that differs from l_seq); _MALFORMED
+ * (MM not of the grammar, ML not B,C or not of the length MM asks for, a skip past the last target); _NO_SITES (no known site).
+ * out_sites = the sites, out_known = those the tags speak about (a site without a call is known with probability 0 unless the
+ * entry's mode is '?'), out_mc = the known ones with probability > threshold (0 .. 255).  All zero unless OK or NO_SITES.
+ * m = out_mc / out_known is the caller's.  A malformed record, or an auxiliary chain that runs past its record, is STRK_E_INVALID
+ * naming the item (the last such item). */
+#define STRK_METHYL_OK 0
+#define STRK_METHYL_NOT_SPANNING 1
+#define STRK_METHYL_NO_TAGS 2
+#define STRK_METHYL_CLIPPED 3
+#define STRK_METHYL_MALFORMED 4
+#define STRK_METHYL_NO_SITES 5
+int strk_methyl(const uint8_t* buf, int64_t n_bytes, int32_t n_items, const int64_t* rec_off, const int64_t* coords,
+                const uint32_t* alt_cigar, const int64_t* alt_cigar_off, const int64_t* alt_start, int32_t threshold,
+                int32_t* out_status, int32_t* out_sites, int32_t* out_known, int32_t* out_mc);
+/* The same over the file resident on the device (kernel k_dbam_methyl: one wave per item); piece_items > 0 cuts the launches into
+ * that many items each, which changes no output. */
+int strk_dbam_methyl(strk_dbam* d, int32_t n_items, const int64_t* rec_off, const int64_t* coords, const uint32_t* alt_cigar,
+                     const int64_t* alt_cigar_off, const int64_t* alt_start, int32_t threshold, int32_t piece_items,
+                     int32_t* out_status, int32_t* out_sites, int32_t* out_known, int32_t* out_mc);
+/* the size constants of k_dbam_methyl as built: bases per lane and pass, bases per pass, MM bytes per pass, ordinals per window */
+void strk_methyl_constants(int32_t* out4);
+
 #ifdef __cplusplus
 }
 #endif

@@ -48,6 +48,9 @@ def build_parser() -> argparse.ArgumentParser:
                    help="VCF (plain or gzip) of candidate SNVs: reads are grouped by the bases they carry at them (needs --call-alleles)")
     c.add_argument("--snv-min-base-qual", type=int, default=20)
     c.add_argument("--significant-clip-threshold", type=int, default=100)
+    c.add_argument("--use-methyl", "-m", action="store_true",
+                   help="5-methyl CpG calls from the reads' MM / ML tags (GPU): m / mc per read, am / amc per called allele")
+    c.add_argument("--methyl-threshold", type=int, default=127, help="--use-methyl: a site counts as methylated above this ML value (0 .. 255)")
     c.add_argument("--sample-id", default=None)
     c.add_argument("--processes", type=int, default=1)
     c.add_argument("--seed", type=int, default=None)
@@ -68,6 +71,8 @@ def main(argv=None) -> int:
         ap.error(f"--count-kmers {a.count_kmers} needs --call-alleles")
     if (a.use_hp or a.incorporate_snvs) and not a.call_alleles:
         ap.error("--use-hp / --incorporate-snvs need --call-alleles")
+    if not 0 <= a.methyl_threshold <= 255:
+        ap.error("--methyl-threshold must be in 0 .. 255")
     import os
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:   # python -m torch.distributed.run --nproc-per-node N -m strkit_amd call ...: one rank per GPU
@@ -87,6 +92,7 @@ def main(argv=None) -> int:
                       count_kmers=a.count_kmers, consensus_method=a.consensus_method, max_mdn_poa_length=a.max_mdn_poa_length,
                       **(dict(use_hp=a.use_hp, snv_vcf=a.incorporate_snvs, snv_min_base_qual=a.snv_min_base_qual,
                               significant_clip_threshold=a.significant_clip_threshold) if a.use_hp or a.incorporate_snvs else {}),
+                      **(dict(use_methyl=True, methyl_threshold=a.methyl_threshold) if a.use_methyl else {}),
                       **(dict(call_alleles=True, consensus=a.consensus or bool(a.vcf), seed=a.seed, n_alleles=a.n_alleles)
                          if a.call_alleles else {}))
     if world > 1:

@@ -17,6 +17,8 @@ STRK_NARROW_NONE, STRK_NARROW_DECREMENT, STRK_NARROW_HALVE, STRK_NARROW_AFTER_SE
 STRK_I16_CELL_MAY_SATURATE, STRK_I16_SCORE_SATURATES = 1, 2
 STRK_E_EMPTY = -61
 STRK_E_INVALID, STRK_E_NOMEM, STRK_E_DEVICE, STRK_E_NODEV = -22, -12, -5, -19
+(STRK_METHYL_OK, STRK_METHYL_NOT_SPANNING, STRK_METHYL_NO_TAGS, STRK_METHYL_CLIPPED, STRK_METHYL_MALFORMED,
+ STRK_METHYL_NO_SITES) = range(6)
 
 _u8p = C.POINTER(C.c_uint8)
 _i32p = C.POINTER(C.c_int32)
@@ -75,7 +77,8 @@ EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk
            "strk_best_representatives", "strk_best_representatives_dseqs",
            "strk_count_kmers", "strk_count_kmers_dseqs", "strk_count_kmers_ws",
            "strk_consensus", "strk_consensus_dseqs", "strk_consensus_ws",
-           "strk_phase_cells", "strk_useful_snvs", "strk_dbam_phase_cells", "strk_dbam_download_cells", "strk_dbam_useful_snvs")
+           "strk_phase_cells", "strk_useful_snvs", "strk_dbam_phase_cells", "strk_dbam_download_cells", "strk_dbam_useful_snvs",
+           "strk_methyl", "strk_dbam_methyl", "strk_methyl_constants")
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -236,6 +239,12 @@ def load(build: bool = True):
         L.strk_dbam_useful_snvs.restype = C.c_int64
         L.strk_dbam_useful_snvs.argtypes = ([C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
                                             + [C.c_int64])
+        L.strk_methyl.restype = C.c_int
+        L.strk_methyl.argtypes = [C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 4
+        L.strk_dbam_methyl.restype = C.c_int
+        L.strk_dbam_methyl.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] * 2 + [C.c_void_p] * 4
+        L.strk_methyl_constants.restype = None
+        L.strk_methyl_constants.argtypes = [_i32p]
         L.strk_device_mem.restype = C.c_int
         L.strk_device_mem.argtypes = [C.c_int, _i64p, _i64p]
         L.strk_realign_i16_flags.restype = C.c_int

@@ -25,6 +25,7 @@
 #include "strk_groups.h"
 #include "strk_phase_check.h"
 #include "strk_phase_inputs.h"
+#include "strk_methyl.h"
 
 #include <algorithm>
 #include <array>
@@ -1244,3 +1245,4 @@ int strk_realign_i16_flags(int32_t n_pairs, const int64_t* s1_off, const int64_t
 
 #include "strk_dbam.inc"
 #include "strk_phase_inputs.inc"
+#include "strk_methyl.inc"

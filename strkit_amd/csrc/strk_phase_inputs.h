@@ -16,6 +16,7 @@
 
 #include "strk_bamrec.h"
 #include "strk_groups.h"
+#include "strk_aux.h"
 
 namespace strk_pi {
 
@@ -27,54 +28,13 @@ constexpr int64_t kCellBudget = (int64_t)512 << 20;   // bytes of the device's c
 // Walks the auxiliary fields aux[0 .. n_aux) of one record.  HP and PS count when their type is one of c C s S i I and the
 // value fits an int32 (the first occurrence that counts); a read is tagged only with both, otherwise both come out -1.
 // false: the chain runs past the end of the record (or holds a type the format does not know) — nothing outside
-// aux[0 .. n_aux) is read in either case.
+// aux[0 .. n_aux) is read in either case.  (The walk itself is strk_aux.h's aux_find.)
 STRK_FE_HD bool aux_tags(const uint8_t* aux, int64_t n_aux, int32_t* hp, int32_t* ps) {
     *hp = -1; *ps = -1;
-    bool have_hp = false, have_ps = false;
-    int32_t v_hp = -1, v_ps = -1;
-    int64_t t = 0;
-    while (t < n_aux) {
-        if (t + 3 > n_aux) return false;
-        const char ty = (char)aux[t + 2];
-        const int64_t v = t + 3, left = n_aux - v;
-        int64_t sz = -1, val = 0;
-        bool is_int = true;
-        if (ty == 'c' || ty == 'C' || ty == 'A') {
-            sz = 1;
-            if (left >= 1) val = ty == 'c' ? (int64_t)(int8_t)aux[v] : (int64_t)aux[v];
-            is_int = ty != 'A';
-        } else if (ty == 's' || ty == 'S') {
-            sz = 2;
-            if (left >= 2) val = ty == 's' ? (int64_t)(int16_t)strk_fe::rd_u16(aux + v) : (int64_t)strk_fe::rd_u16(aux + v);
-        } else if (ty == 'i' || ty == 'I' || ty == 'f') {
-            sz = 4;
-            if (left >= 4) val = ty == 'i' ? (int64_t)strk_fe::rd_i32(aux + v) : (int64_t)strk_fe::rd_u32(aux + v);
-            is_int = ty != 'f';
-        } else if (ty == 'Z' || ty == 'H') {
-            int64_t z = v;
-            while (z < n_aux && aux[z]) ++z;
-            if (z >= n_aux) return false;
-            sz = z - v + 1;
-            is_int = false;
-        } else if (ty == 'B') {
-            if (left < 5) return false;
-            const char sub = (char)aux[v];
-            int64_t es;
-            if (sub == 'c' || sub == 'C') es = 1;
-            else if (sub == 's' || sub == 'S') es = 2;
-            else if (sub == 'i' || sub == 'I' || sub == 'f') es = 4;
-            else return false;
-            sz = 5 + (int64_t)strk_fe::rd_u32(aux + v + 1) * es;   // at most 5 + 4 * (2^32 - 1): no overflow in 64 bits
-            is_int = false;
-        }
-        if (sz < 0 || sz > left) return false;
-        if (is_int && val <= (int64_t)INT32_MAX) {
-            if (aux[t] == 'H' && aux[t + 1] == 'P' && !have_hp) { have_hp = true; v_hp = (int32_t)val; }
-            if (aux[t] == 'P' && aux[t + 1] == 'S' && !have_ps) { have_ps = true; v_ps = (int32_t)val; }
-        }
-        t = v + sz;
-    }
-    if (have_hp && have_ps) { *hp = v_hp; *ps = v_ps; }
+    const strk_fe::AuxWant want[2] = {{'H', 'P', strk_fe::kAuxInt32}, {'P', 'S', strk_fe::kAuxInt32}};
+    int64_t off[2], size[2], val[2];
+    if (!strk_fe::aux_find(aux, n_aux, want, 2, off, size, val)) return false;
+    if (off[0] >= 0 && off[1] >= 0) { *hp = (int32_t)val[0]; *ps = (int32_t)val[1]; }
     return true;
 }
 

@@ -16,6 +16,7 @@ from .bam import BamFile
 from .extract import LowMeanBaseQual, get_read_coords_from_cigar, get_read_coords_from_matched_pairs, get_sequence_data_for_locus
 from .genotype import block_consensus, block_kmers, call_block_alleles, call_block_alleles_phased, genotype_row, kmers_row
 from .loci import Locus
+from .methyl import methyl, methyl_row, read_methylation, record_values
 from .native import extract_raw_slices, extract_reads, realign_cigar_to_read_alignment
 from .options import VCF_ANCHOR_SIZE, CallOptions
 from .output import block_read_weights, read_weights
@@ -80,6 +81,7 @@ def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data
     reference side of every locus of the block (refside.get_loci_with_ref_data)."""
     flank_size = opts.flank_size
     want_raw = opts.consensus or opts.count_kmers != "none"
+    use_methyl = getattr(opts, "use_methyl", False)
     results: list[dict] = []
     prepared = []                     # (locus, ref data, [[segment, the pairs of its new alignment or None] ...])
     realign_jobs = []                 # (locus, ref data, entry) of the soft-clipped reads
@@ -121,7 +123,7 @@ def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data
             except LowMeanBaseQual:
                 continue
             triples.append((sd.flank_left_seq_wc[-flank_size:], sd.tr_seq_wc, sd.flank_right_seq_wc[:flank_size]))
-            names.append((seg.name, seg.strand, pairs is not None, len(sd.tr_seq)))
+            names.append((seg.name, seg.strand, pairs is not None, len(sd.tr_seq), seg, coords))
             if want_raw:   # the raw tract and the raw read bases in front of it (no wildcards), call_locus.py:1296-1299
                 raw.append((sd.tr_seq, seg.query_sequence[max(coords.left_flank_start, coords.left_flank_end - VCF_ANCHOR_SIZE):
                                                           coords.left_flank_end]))
@@ -145,10 +147,15 @@ def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data
         tlwf = (batch.nfl[r0:r1] + batch.ntr[r0:r1] + batch.nfr[r0:r1]).astype(np.int64)
         ws = read_weights(lens_sorted, tlwf)
         for r in kept:
-            name, strand, realigned, sl = meta[li][r - r0]
+            name, strand, realigned, sl, seg, rc = meta[li][r - r0]
             sc = float(flt["sc"][r])
             reads[name] = {"s": strand, "cn": int(res["cn"][r]), "w": float(ws[r - r0]),
                            "sc": None if np.isnan(sc) else sc, "sl": sl, **({"realn": True} if realigned else {})}
+            if use_methyl:     # the rule itself (methyl.py) on the tract extraction cut
+                a, b, c, d = rc.left_flank_start, rc.left_flank_end, rc.right_flank_start, rc.right_flank_end
+                q = (b, c) if 0 <= a <= b <= c <= d and c <= seg.length else (None, None)
+                st_m, _, known, mc = read_methylation(seg.query_sequence, seg.flag, seg.cigar, seg.tags, *q, opts.methyl_threshold)
+                reads[name]["m"], reads[name]["mc"] = record_values(st_m, known, mc)
             if want_raw:
                 raws[name] = raw[r]
         if not flt["locus_ok"][li]:
@@ -178,6 +185,8 @@ def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data
             genotype_row(row, al, li, recs_of[li], cons)
             if "phase" in al:
                 phase_row(row, al, li, recs_of[li], prepared[li][0])
+            if use_methyl:
+                methyl_row(row, recs_of[li])
         if km is not None:
             kmers_row(row, km, li, recs_of[li], first)
         first += len(recs_of[li])
@@ -204,6 +213,7 @@ class BlockState:
     al: dict | None = None
     cons: dict | None = None
     kmers: dict | None = None
+    methyl: dict | None = None    # status / known / mc per kept read (use_methyl)
 
 
 def _call_block_native(block, bam, opts: CallOptions, ctx, tm, ref_data, phase_run=None):
@@ -284,6 +294,12 @@ def _block_device_stage(live, bam, opts: CallOptions, ctx, tm, phase_run=None) -
                     weigh=lambda: block_read_weights(counts, item_locus, lens_all, read_locus[kept],
                                                      batch.nfl[kept].astype(np.int64) + batch.ntr[kept] + batch.nfr[kept]))
     tm["names_s"] = tm.get("names_s", 0.0) + time.perf_counter() - t_a
+    if getattr(opts, "use_methyl", False):     # one library call over the kept items: the records are read where they lie
+        t_a = time.perf_counter()
+        items = ok_items[kept]
+        st.methyl = methyl(bam, rec[items], coords[items], {k: alt[it] for k, it in enumerate(items.tolist()) if it in alt} if alt else None,
+                           opts.methyl_threshold)
+        tm["methyl_s"] = tm.get("methyl_s", 0.0) + time.perf_counter() - t_a
     if opts.call_alleles or opts.count_kmers != "none":
         if opts.call_alleles:
             st.ws = st.weigh()
@@ -313,6 +329,9 @@ def _block_report_stage(st: BlockState, opts: CallOptions, tm):
         for k, it in enumerate(st.ok_items[kept].tolist()):
             if it in alt:
                 recs[k]["realn"] = True
+    if st.methyl is not None:
+        for r, s_, k_, m_ in zip(recs, st.methyl["status"].tolist(), st.methyl["known"].tolist(), st.methyl["mc"].tolist()):
+            r["m"], r["mc"] = record_values(s_, k_, m_)
     for li, (locus, rd) in enumerate(live):
         a, b = first[li], first[li + 1]
         row = _locus_row(locus, rd, dict(zip(names[a:b], recs[a:b])), opts)
@@ -320,6 +339,8 @@ def _block_report_stage(st: BlockState, opts: CallOptions, tm):
             genotype_row(row, al, li, recs[a:b], cons)
             if "phase" in al:
                 phase_row(row, al, li, recs[a:b], locus)
+            if st.methyl is not None:
+                methyl_row(row, recs[a:b])
         if km is not None:
             kmers_row(row, km, li, recs[a:b], a)
         results.append(row)

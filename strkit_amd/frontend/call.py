@@ -21,14 +21,14 @@ from .fasta import Fasta
 from .gather import _distributed, call_blocks_sharded, deal_locus_blocks
 from .loci import Locus, load_loci, resolve_contig
 from .native import DeviceBam, IndexedBam, NativeBam
-from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, PhasedCallOptions, PoaCallOptions, phased, report_parameters,
+from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, MethylCallOptions, PhasedCallOptions, PoaCallOptions, phased, report_parameters,
                       with_keywords)
 from .phase_block import PhaseRun
 from .reader import open_path
 from .refside import get_loci_with_ref_data, get_locus_with_ref_data, ref_side_of_blocks
 
 # (what moved to the other modules is still offered here under the names it had)
-__all__ = ["CallOptions", "PoaCallOptions", "PhasedCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
+__all__ = ["CallOptions", "PoaCallOptions", "PhasedCallOptions", "MethylCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
 
 
 def call_locus(locus: Locus, bam: BamFile, ref: Fasta, *, ctx: _lib.Context | None = None, opts: CallOptions | None = None,
@@ -58,6 +58,9 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, *, sample_
     if opts.call_alleles and _distributed():
         raise NotImplementedError("call_alleles=True under torch.distributed: the fixed-size records that the ranks gather "
                                   "(call_blocks_sharded) have no fields for calls and sequences yet; run one process")
+    if getattr(opts, "use_methyl", False) and _distributed():
+        raise NotImplementedError("use_methyl=True under torch.distributed: the fixed-size records that the ranks gather "
+                                  "(call_blocks_sharded) have no fields for methylation yet; run one process")
     t_open = time.perf_counter()
     own_reader = isinstance(bam, str)
     # a path: a host reader at once, or a device reader that opens in the background

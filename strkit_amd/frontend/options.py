@@ -113,6 +113,26 @@ class PhasedCallOptions(PoaCallOptions):
 PHASE_OPTION_NAMES = ("use_hp", "snv_vcf", "snv_min_base_qual", "significant_clip_threshold", "phase_params")
 
 
+@dataclass
+class MethylCallOptions(PhasedCallOptions):
+    """PhasedCallOptions plus methylation from MM / ML tags (`strkit call --use-methyl`).  `use_methyl`: every kept
+    read record gets `m` and `mc` (the share and the number of its tract's known CpG sites whose 5mC probability is above the
+    threshold), a called locus whose every peak has a value gets peaks.am / peaks.amc.  `methyl_threshold`: that threshold on the
+    ML scale, 0 .. 255 (127 in the reference's only call).  The switch does not need call_alleles.  A type of its own for the
+    reason PoaCallOptions gives."""
+    use_methyl: bool = False
+    methyl_threshold: int = 127
+
+    def validate(self) -> None:
+        super().validate()
+        v = self.methyl_threshold
+        if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= 255:
+            raise ValueError(f"methyl_threshold must be an integer in 0 .. 255 (the scale of ML): got {v!r}")
+
+
+METHYL_OPTION_NAMES = ("use_methyl", "methyl_threshold")
+
+
 def phased(opts) -> bool:
     """Whether a switch of PhasedCallOptions is on (any options type may be asked)."""
     return bool(getattr(opts, "use_hp", False) or getattr(opts, "snv_vcf", None))
@@ -120,8 +140,10 @@ def phased(opts) -> bool:
 
 def with_keywords(opts: CallOptions | None, **option_keywords) -> CallOptions:
     """`opts` (or the defaults) with the options given by name replaced: dataclasses.replace, after widening a plain
-    CallOptions to PoaCallOptions when one of POA_OPTION_NAMES is among them, and to PhasedCallOptions for PHASE_OPTION_NAMES.  An unknown name is a TypeError."""
+    CallOptions to PoaCallOptions when one of POA_OPTION_NAMES is among them, to PhasedCallOptions for PHASE_OPTION_NAMES, and to MethylCallOptions for METHYL_OPTION_NAMES.  An unknown name is a TypeError."""
     opts = opts or CallOptions()
+    if not isinstance(opts, MethylCallOptions) and any(k in option_keywords for k in METHYL_OPTION_NAMES):
+        opts = MethylCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, PhasedCallOptions) and any(k in option_keywords for k in PHASE_OPTION_NAMES):
         opts = PhasedCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, PoaCallOptions) and any(k in option_keywords for k in POA_OPTION_NAMES):
@@ -147,4 +169,6 @@ def report_parameters(opts: CallOptions, processes: int) -> dict:
             **({"count_kmers": opts.count_kmers} if opts.count_kmers != "none" else {}),
             **({"use_hp": True} if getattr(opts, "use_hp", False) else {}),
             **({"snv_vcf": opts.snv_vcf, "snv_min_base_qual": opts.snv_min_base_qual} if getattr(opts, "snv_vcf", None) else {}),
-            **({"significant_clip_threshold": opts.significant_clip_threshold} if phased(opts) else {})}
+            **({"significant_clip_threshold": opts.significant_clip_threshold} if phased(opts) else {}),
+            **({"use_methyl": True} if getattr(opts, "use_methyl", False) else {}),
+            **({"methyl_threshold": opts.methyl_threshold} if getattr(opts, "use_methyl", False) and opts.methyl_threshold != 127 else {})}

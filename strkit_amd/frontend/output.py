@@ -169,6 +169,10 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
     # gives the bytes it always gave
     extra = ([("NSNV", "1", "Integer", "Number of supporting SNVs for the STR peak-call")] if any(r.get("snvs") for r in report["results"]) else []) + \
             ([("PS", "1", "Integer", "Phase set")] if any(r.get("ps") is not None for r in report["results"]) else [])
+    use_methyl = bool((report.get("parameters") or {}).get("use_methyl"))
+    if use_methyl:      # (output/vcf.py:114-116: declared by the run's switch, not by what the rows carry)
+        extra += [("AM", ".", "Float", "Average methylation level (5-methyl CpG sites) for each allele"),
+                  ("AMC", ".", "Float", "Average number of 5-methyl CpG sites for each allele")]
     if extra:
         formats = tuple(sorted(formats + tuple(extra), key=lambda f: f[0]))
     sample = sample_id or report.get("sample_id") or "sample"
@@ -218,6 +222,9 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
             mmas = row.get("mean_model_align_score")
             keys += ["MMAS", "DPS", "AD"]
             vals += ["." if mmas is None else f"{mmas:.6g}", str(sum(peaks["n_reads"])), ",".join(map(str, peaks["n_reads"]))]
+        if use_methyl and peaks:      # output/vcf.py:343-346: per allele, '.' per peak where the row has none
+            for key in ("am", "amc"):
+                keys.append(key.upper()); vals.append(",".join(f"{x:.6g}" for x in peaks[key]) if peaks.get(key) else ",".join(["."] * n_peaks))
         if call:
             keys.append("MC"); vals.append(",".join(str(int(c)) for c in call))
         if peaks:
