@@ -23,7 +23,7 @@ struct InfBlock {
 };
 
 __global__ void __launch_bounds__(64) k_bgzf_inflate(const uint8_t* comp, const InfBlock* blocks, int n_blocks, uint8_t* data,
-                                                     uint8_t* lens_scratch, int32_t* status) {
+                                                     uint8_t* lens_scratch, unsigned long long* status) {
     __shared__ strk_inf::Tables tabs[64];
     __shared__ uint32_t crc_tab[2][256];
     for (int i = threadIdx.x; i < 256; i += 64) strk_inf::crc_table_entry(crc_tab[0], i);
@@ -63,10 +63,8 @@ __global__ void __launch_bounds__(64) k_bgzf_inflate(const uint8_t* comp, const 
         for (; i < blk.out_len; ++i) c = crc_tab[0][(c ^ out[i]) & 0xffu] ^ (c >> 8);
         if ((c ^ 0xffffffffu) != blk.crc) rc = strk_inf::kErrCrc;
     }
-    if (rc) {
-        atomicMax(&status[0], rc);
-        atomicMin(&status[1], b);
-    }
+    // (block index above the error: the smallest word is the first bad block of the stretch together with its own error)
+    if (rc) atomicMin(status, ((unsigned long long)b << 32) | (unsigned long long)rc);
 }
 
 // Record scan.  Records follow one another without markers, so a chain has to be walked; the .bai linear index gives the
@@ -297,22 +295,22 @@ static int64_t dbam_run_inflate(strk_dbam* d, const std::vector<InfBlock>& block
     if ((rc = d->blocks.ensure(blocks.size() * sizeof(InfBlock))) || (rc = dbam_big_ensure(d->device, d->data, (size_t)total + 16)) ||
         (rc = d->lens.ensure(blocks.size() * (size_t)strk_inf::kLensBytes)) || (rc = d->status.ensure(8)))
         return rc;
-    const int32_t st0[2] = {0, INT32_MAX};
+    const uint64_t st0 = UINT64_MAX;   // no bad block
     HIP_TRY(hipStreamSynchronize(stream));
     HIP_TRY(hipMemset(d->comp.as<uint8_t>() + n_in, 0, 16));
     HIP_TRY(hipMemcpy(d->blocks.p, blocks.data(), blocks.size() * sizeof(InfBlock), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d->status.p, st0, 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d->status.p, &st0, 8, hipMemcpyHostToDevice));
     const int nb = (int)blocks.size();
     d->tic();
     hipLaunchKernelGGL(k_bgzf_inflate, dim3((nb + 63) / 64), dim3(64), 0, 0, d->comp.as<uint8_t>(), d->blocks.as<InfBlock>(), nb,
-                       d->data.as<uint8_t>(), d->lens.as<uint8_t>(), d->status.as<int32_t>());
+                       d->data.as<uint8_t>(), d->lens.as<uint8_t>(), d->status.as<unsigned long long>());
     HIP_TRY(hipGetLastError());
     d->toc();
-    int32_t st[2];
-    HIP_TRY(hipMemcpy(st, d->status.p, 8, hipMemcpyDeviceToHost));
-    if (st[0] != 0)
-        return fail(STRK_E_INVALID, "corrupt BGZF block %d of the stretch at byte %lld (%s)", st[1], (long long)coff,
-                    st[0] == strk_inf::kErrCrc ? "CRC mismatch" : "inflate failed");
+    uint64_t st = 0;
+    HIP_TRY(hipMemcpy(&st, d->status.p, 8, hipMemcpyDeviceToHost));
+    if (st != st0)
+        return fail(STRK_E_INVALID, "corrupt BGZF block %d of the stretch at byte %lld (%s)", (int)(st >> 32), (long long)coff,
+                    (int)(st & 0xffffffffu) == strk_inf::kErrCrc ? "CRC mismatch" : "inflate failed");
     d->n_data = total;
     return total;
 }
@@ -766,8 +764,9 @@ int strk_read_coords_both(const uint32_t* cigar, int32_t n_cigar, int64_t start,
 int64_t strk_bgzf_inflate_sw(const uint8_t* comp, int64_t n_comp, uint8_t* out, int64_t out_cap) {
     if (!comp || n_comp < 0) return fail(STRK_E_INVALID, "bad argument");
     std::vector<strk_fe::BgzfBlock> blocks;
-    int64_t total = 0;
-    if (strk_fe::bgzf_index(comp, n_comp, &blocks, &total)) return fail(STRK_E_INVALID, "not a BGZF stream (or truncated)");
+    int64_t total = 0, bad = 0;
+    if (strk_fe::bgzf_index(comp, n_comp, &blocks, &total, &bad))
+        return fail(STRK_E_INVALID, "not a BGZF stream (or truncated): bad BGZF block at byte %lld", (long long)bad);
     if (!out) return total;
     if (out_cap < total) return fail(STRK_E_NOMEM, "output buffer too small (%lld < %lld)", (long long)out_cap, (long long)total);
     uint32_t tab[256];

@@ -87,10 +87,12 @@ struct BgzfBlock {
     int64_t out_off;
 };
 
-// Walks the block headers.  Returns 0 and fills `blocks`, or -1 if the stream is not BGZF / is truncated.
-inline int bgzf_index(const uint8_t* p, int64_t n, std::vector<BgzfBlock>* blocks, int64_t* total) {
+// Walks the block headers.  Returns 0 and fills `blocks`, or -1 if the stream is not BGZF / is truncated (*bad_off: the
+// offset of the block whose header says so).
+inline int bgzf_index(const uint8_t* p, int64_t n, std::vector<BgzfBlock>* blocks, int64_t* total, int64_t* bad_off = nullptr) {
     int64_t off = 0, out = 0;
     while (off < n) {
+        if (bad_off) *bad_off = off;
         if (off + 18 > n || p[off] != 0x1f || p[off + 1] != 0x8b || p[off + 2] != 8 || !(p[off + 3] & 4)) return -1;
         const int xlen = rd_u16(p + off + 10);
         int64_t x = off + 12;

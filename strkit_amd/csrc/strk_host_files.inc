@@ -184,7 +184,7 @@ int64_t strk_bgzf_inflate_range(const uint8_t* comp, int64_t n_comp, int64_t cof
         int bsize = -1;
         for (int64_t x = 12; x + 4 <= 12 + xlen && off + x + 4 <= n_comp;) {
             const int slen = strk_fe::rd_u16(p + x + 2);
-            if (p[x] == 'B' && p[x + 1] == 'C' && slen == 2) bsize = strk_fe::rd_u16(p + x + 4);
+            if (p[x] == 'B' && p[x + 1] == 'C' && slen == 2 && x + 6 <= 12 + xlen && off + x + 6 <= n_comp) bsize = strk_fe::rd_u16(p + x + 4);
             x += 4 + slen;
         }
         if (bsize < 0 || off + bsize + 1 > n_comp) return fail(STRK_E_INVALID, "truncated BGZF block at byte %lld", (long long)off);
@@ -203,8 +203,9 @@ int64_t strk_bgzf_inflate_range(const uint8_t* comp, int64_t n_comp, int64_t cof
 int64_t strk_bgzf_inflate(const uint8_t* comp, int64_t n_comp, uint8_t* out, int64_t out_cap, int32_t n_threads) {
     if (!comp || n_comp < 0) return fail(STRK_E_INVALID, "bad argument");
     std::vector<strk_fe::BgzfBlock> blocks;
-    int64_t total = 0;
-    if (strk_fe::bgzf_index(comp, n_comp, &blocks, &total)) return fail(STRK_E_INVALID, "not a BGZF stream (or truncated)");
+    int64_t total = 0, bad = 0;
+    if (strk_fe::bgzf_index(comp, n_comp, &blocks, &total, &bad))
+        return fail(STRK_E_INVALID, "not a BGZF stream (or truncated): bad BGZF block at byte %lld", (long long)bad);
     if (!out) return total;   // size query
     if (out_cap < total) return fail(STRK_E_NOMEM, "output buffer too small (%lld < %lld)", (long long)out_cap, (long long)total);
     return bgzf_inflate_blocks(comp, blocks, out, n_threads, false) ? total : fail(STRK_E_INVALID, "corrupt BGZF block (inflate or CRC failed)");

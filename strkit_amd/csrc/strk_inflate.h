@@ -21,8 +21,9 @@
 //     counter retires in order);
 //   * the token loop is a state machine — every iteration a lane either decodes one token or copies up to eight bytes of
 //     a pending match — so that lanes in different states of different streams share one loop body.
-// The same functions compile for the host (tests/test_inflate.py checks them against zlib on every block of a synthetic
-// BAM and on streams of every block type).
+// The same functions compile for the host: tests/test_frontend.py checks them against zlib on the corpus of
+// tests/inflate_cases.py (every block type, code shape, copy path and error return), tests/test_gpu_inflate.py does the same
+// for the device compile, tools/inflate_asan.sh runs the host compile under the sanitizers.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -112,7 +113,8 @@ STRK_INF_HD bool build(const uint8_t* lens, int n, uint8_t* sym, Code* c) {
     });
     c->word[15] = 0;
     if (over) return false;
-    if (left > 0 && used > 1) return false;              // incomplete (a single code of length 1 is allowed: RFC 1951 3.2.7)
+    // incomplete: allowed only for a single code of length 1 (RFC 1951 3.2.7) or no code at all
+    if (left > 0 && (used > 1 || (count[1] & 0xffff) != used)) return false;
     STRK_INF_LOOP
     for (int i = 0; i < n; ++i) {
         const int l = lens[i] & 15;
@@ -402,7 +404,11 @@ STRK_INF_HD int inflate_block(const uint8_t* in, int in_len, uint8_t* out, int o
         if (pos + mlen > out_len) return kErrSize;
         copy_len = mlen; copy_dist = dist;
     }
-    return pos == out_len ? kErrNone : kErrSize;
+    if (pos != out_len) return kErrSize;
+    // the final block's end lies inside the payload, not in the bytes behind it (a payload cut inside the last code, which
+    // the padding happened to complete)
+    if ((int)(s.p - in) * 8 - s.cnt > in_len * 8) return kErrOverrun;
+    return kErrNone;
 }
 
 // CRC-32 (gzip) of `n` bytes, byte at a time over a 256-entry table (crc_table: shared, LDS on the device).

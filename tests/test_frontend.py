@@ -528,7 +528,7 @@ def test_device_inflater_code_on_the_host_equals_zlib(tmp_path):
     """strk_inflate.h (the decoder k_bgzf_inflate runs, one GPU lane per BGZF block) compiled for the host,
     strk_bgzf_inflate_sw: every block of a synthetic BAM, streams of all three block types (stored, fixed, dynamic codes),
     a corrupted payload."""
-    import zlib
+    import inflate_cases as ic
     from strkit_amd import _lib
     from strkit_amd.frontend.bam import bgzf_block
     t = make_dataset(str(tmp_path), n_loci=12, reads_per_locus=8, read_len=3000, seed=21, sub=0.01, indel=0.01)
@@ -539,44 +539,111 @@ def test_device_inflater_code_on_the_host_equals_zlib(tmp_path):
     assert L.strk_bgzf_inflate(comp.ctypes.data, comp.size, a.ctypes.data, a.size, 1) == n
     assert L.strk_bgzf_inflate_sw(comp.ctypes.data, comp.size, b.ctypes.data, b.size) == n
     assert np.array_equal(a, b)
-    rng = np.random.default_rng(4)
-    payloads = [b"", b"A", bytes(rng.integers(256, size=40000, dtype=np.uint8)), b"ACGT" * 9000, bytes(60000),
-                bytes(rng.integers(33, 74, size=65000, dtype=np.uint8))]
-    # runs of every short period and matches of every length at short and long distances, up to the last byte of the block
-    # (the copy paths of the decoder: pattern fill from registers, 8 / 32 / 128 / 264 bytes per trip, byte-wise tail)
-    runs = bytearray()
-    for period in range(1, 41):
-        pat = bytes(rng.integers(256, size=period, dtype=np.uint8))
-        for reps in (3, 11, 40, 300 // period + 2):
-            runs += pat * reps + bytes(rng.integers(256, size=int(rng.integers(1, 9)), dtype=np.uint8))
-    far = bytearray(bytes(rng.integers(256, size=3000, dtype=np.uint8)))
-    for ln in list(range(3, 40)) + [63, 64, 65, 127, 128, 129, 130, 200, 257, 258, 259, 300, 600]:
-        for back in (ln, ln + 1, 31, 32, 33, 127, 128, 129, 263, 264, 265, 2000):
-            if back <= len(far) and back >= 1:
-                far += bytes(far[len(far) - back + i % back] if i >= back else far[len(far) - back + i] for i in range(ln)) if back < ln \
-                    else far[len(far) - back:len(far) - back + ln]
-                far += bytes(rng.integers(256, size=int(rng.integers(0, 4)), dtype=np.uint8))
-    payloads += [bytes(runs[:65000]), bytes(far[:65000]), bytes(far[:60000]) + b"\x07" * 300, b"ab" * 150 + b"xyz" * 100]
-    for raw in payloads:
-        for level, strategy in ((0, zlib.Z_DEFAULT_STRATEGY), (1, zlib.Z_FIXED), (6, zlib.Z_DEFAULT_STRATEGY), (9, zlib.Z_HUFFMAN_ONLY),
-                                (4, zlib.Z_RLE)):
-            co = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
-            body = co.compress(raw) + co.flush()
-            if len(body) + 26 > 65536:
-                continue
-            blk = np.frombuffer(bgzf_block(raw, body), np.uint8)
-            out = np.full(len(raw) + 8, 0xEE, np.uint8)
-            assert L.strk_bgzf_inflate_sw(blk.ctypes.data, blk.size, out.ctypes.data, len(raw)) == len(raw), (len(raw), level, strategy)
-            assert out[:len(raw)].tobytes() == raw and (out[len(raw):] == 0xEE).all()
+    # the payload x strategy matrix of tests/inflate_cases.py: runs of every short period and matches of every length at short
+    # and long distances, up to the last byte of the block (the copy paths of the decoder: pattern fill from registers, 8 / 32 /
+    # 128 / 264 bytes per trip, byte-wise tail), under every level and strategy
+    ic.check_coverage()
+    for name, body, raw, _ in ic.zlib_matrix():
+        blk = np.frombuffer(bgzf_block(raw, body), np.uint8)
+        out = np.full(len(raw) + 8, 0xEE, np.uint8)
+        assert L.strk_bgzf_inflate_sw(blk.ctypes.data, blk.size, out.ctypes.data, len(raw)) == len(raw), name
+        assert out[:len(raw)].tobytes() == raw and (out[len(raw):] == 0xEE).all()
     bad = comp.copy()
     bad[bad.size // 2] ^= 0x21
     assert L.strk_bgzf_inflate_sw(bad.ctypes.data, bad.size, b.ctypes.data, b.size) < 0 and b"BGZF" in L.strk_last_error()
 
 
+def _inflate_with(fn, blk: bytes, cap: int):
+    """(return value, the bytes, whether the guard behind them is whole) of one of the host inflaters on a BGZF file."""
+    comp = np.frombuffer(blk, np.uint8)
+    out = np.full(cap + 8, 0xEE, np.uint8)
+    n = fn(comp.ctypes.data, comp.size, out.ctypes.data, cap)
+    return n, out[:max(n, 0)].tobytes(), bool((out[cap:] == 0xEE).all())
+
+
+def test_both_host_inflaters_equal_zlib_on_the_corpus():
+    """tests/inflate_cases.py, block by block: strk_bgzf_inflate_sw (strk_inflate.h compiled for the host) and strk_bgzf_inflate
+    (the zlib path) give zlib's bytes for every accepted body — every block type, several deflate blocks per BGZF block, the
+    code shapes zlib never writes, every copy branch at its edges — and write nothing behind them."""
+    import inflate_cases as ic
+    from strkit_amd import _lib
+    L = _lib.load()
+    print(ic.check_coverage())
+    for case in ic.accepted():
+        name, _, want = case
+        blk = ic.block_of(case)
+        n, got, whole = _inflate_with(L.strk_bgzf_inflate_sw, blk, len(want))
+        assert n == len(want), (name, n, L.strk_last_error())
+        assert got == want and whole, name
+        n, got, whole = _inflate_with(lambda a, b, c, d: L.strk_bgzf_inflate(a, b, c, d, 1), blk, len(want))
+        assert n == len(want) and got == want and whole, (name, n, L.strk_last_error())
+    # and as one file, in the shuffled order the device test uses
+    comp, _, _, raw = ic.bgzf_file(ic.shuffled(ic.accepted()))
+    for fn in (L.strk_bgzf_inflate_sw, lambda a, b, c, d: L.strk_bgzf_inflate(a, b, c, d, 3)):
+        n, got, whole = _inflate_with(fn, comp, len(raw))
+        assert n == len(raw) and got == raw and whole
+
+
+def test_both_host_inflaters_refuse_the_malformed_bodies():
+    """One body per error return of inflate_block (and a good stream under a wrong CRC, a wrong ISIZE): strk_bgzf_inflate_sw
+    returns a negative value and its message names the error return the body aims at; the zlib path refuses the same blocks."""
+    import inflate_cases as ic
+    from strkit_amd import _lib
+    L = _lib.load()
+    aim = ic.corpus()["aim"]
+    for case in ic.refusals():
+        name = case[0]
+        blk = ic.block_of(case)
+        cap = ic.corpus()["trailer"][name][1]
+        n, _, whole = _inflate_with(L.strk_bgzf_inflate_sw, blk, cap)
+        msg = L.strk_last_error()
+        assert n < 0 and whole and b"corrupt BGZF block" in msg, (name, n, msg)
+        if aim[name] == ic.E_CRC:
+            assert b"CRC" in msg, (name, msg)
+        elif aim[name] is not None:
+            assert b"inflate error %d)" % aim[name] in msg, (name, msg)
+        n, _, whole = _inflate_with(lambda a, b, c, d: L.strk_bgzf_inflate(a, b, c, d, 1), blk, cap)
+        assert n < 0 and whole and b"corrupt BGZF block" in L.strk_last_error(), (name, n)
+
+
+def test_header_walkers_agree_on_foreign_headers():
+    """The BGZF header walk of strk_bgzf_inflate / strk_bgzf_inflate_sw (bgzf_index) and of strk_bgzf_inflate_range, shown
+    headers the project's writer never makes: subfields in front of and behind BC, XLEN above 6, any MTIME / XFL / OS, empty
+    blocks in mid-file — accepted, bytes unchanged; no BC subfield, BSIZE past the file, BSIZE so small that the trailer
+    overlaps the header, ISIZE above 65536 — refused with the byte offset of the block."""
+    import ctypes as C
+    import re
+    import inflate_cases as ic
+    from strkit_amd import _lib
+    L = _lib.load()
+    files = ic.header_files()
+    assert len(files["ok"]) == 9 and len(files["bad"]) == 4
+
+    def ranged(a, b, c, d):
+        nx = C.c_int64(-1)
+        n = L.strk_bgzf_inflate_range(a, b, 0, c, d, C.byref(nx), 1)
+        assert n < 0 or nx.value == b
+        return n
+    walkers = (L.strk_bgzf_inflate_sw, lambda a, b, c, d: L.strk_bgzf_inflate(a, b, c, d, 1), ranged)
+    for name, (comp, raw) in files["ok"].items():
+        for fn in walkers:
+            n, got, whole = _inflate_with(fn, comp, len(raw))
+            assert n == len(raw) and got == raw and whole, (name, n, L.strk_last_error())
+        arr = np.frombuffer(comp, np.uint8)
+        assert L.strk_bgzf_inflate(arr.ctypes.data, arr.size, None, 0, 0) == len(raw), name
+    for name, (comp, at) in files["bad"].items():
+        for fn in walkers:
+            n, _, whole = _inflate_with(fn, comp, 1 << 17)
+            msg = L.strk_last_error()
+            assert n < 0 and whole and re.search(rb"BGZF block.* at byte %d\b" % at, msg), (name, n, msg)
+
+
 def test_inflater_code_is_clean_under_the_sanitizers(tmp_path):
     """tools/inflate_asan.sh: strk_inflate.h compiled for the host with AddressSanitizer + UBSan inflates every block of a
-    synthetic BAM and of streams for every copy path into heap buffers of exactly the block's size (the decoder stores whole
-    words past the end of a match and reads its input up to 16 bytes ahead: never outside the block / the padded payload)."""
+    synthetic BAM and of the accepted corpus of tests/inflate_cases.py (streams for every copy path, block type and code shape)
+    into heap buffers of exactly the block's size (the decoder stores whole words past the end of a match and reads its input
+    up to 16 bytes ahead: never outside the block / the padded payload); the corpus's malformed bodies, in a second file, all
+    come back refused inside the same bounds."""
     import shutil
     import subprocess
     if shutil.which("g++") is None:
@@ -586,6 +653,10 @@ def test_inflater_code_is_clean_under_the_sanitizers(tmp_path):
     if r.returncode != 0 and "sanitize" in r.stderr and "cannot find" in r.stderr:
         pytest.skip("the sanitizer run-time libraries are not installed")
     assert r.returncode == 0 and "clean" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = r.stdout.strip().splitlines()                                       # the accepted files, then the refusals
+    assert len(lines) == 2 and all(ln.endswith(": clean") for ln in lines) and " 0 refusals" in lines[0], r.stdout[-2000:]
+    import inflate_cases as ic
+    assert " %d refusals" % len(ic.refusals()) in lines[1] and lines[1].startswith("0 blocks"), lines[1]
 
 
 def test_indexed_bam_slots_reuse_their_buffers(tmp_path):

@@ -1,6 +1,9 @@
 // The device inflater's code (strk_inflate.h compiles for the host too) under AddressSanitizer / UBSan: every BGZF block of the
 // files given is inflated into a heap buffer of exactly its size from a heap copy of its payload padded by the 16 bytes the
-// decoder may read ahead — a store or a load one byte outside either is reported.  Build and run: tools/inflate_asan.sh
+// decoder may read ahead — a store or a load one byte outside either is reported.  Files behind --refuse hold blocks that
+// must not be accepted (tests/inflate_cases.py: one malformed body per error return of the decoder): each must come back with
+// an error or under a wrong CRC, whatever lies in the padding, and stay inside the same bounds.
+// Build and run: tools/inflate_asan.sh
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -10,8 +13,10 @@
 #include "../strkit_amd/csrc/strk_inflate.h"
 
 int main(int argc, char** argv) {
-    long blocks = 0, bytes = 0, variants = 0;
+    long blocks = 0, bytes = 0, variants = 0, refused = 0;
+    bool refuse = false;
     for (int a = 1; a < argc; ++a) {
+        if (!strcmp(argv[a], "--refuse")) { refuse = true; continue; }
         FILE* f = fopen(argv[a], "rb");
         if (!f) { fprintf(stderr, "cannot open %s\n", argv[a]); return 2; }
         fseek(f, 0, SEEK_END);
@@ -35,6 +40,20 @@ int main(int argc, char** argv) {
             uint8_t* out = (uint8_t*)malloc(isize ? isize : 1);
             strk_inf::Tables* t = (strk_inf::Tables*)malloc(sizeof(strk_inf::Tables));
             uint8_t* lens = (uint8_t*)malloc(strk_inf::kLensBytes);
+            if (refuse) {
+                // zeros behind the payload (the library's host copy), ones, and what a file has there: the trailer and a header
+                const uint8_t pads[3][16] = {{0}, {0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff, 0xff},
+                                             {0x12, 0x34, 0x56, 0x78, 0x48, 0, 0, 0, 0x1f, 0x8b, 8, 4, 0, 0, 0, 0}};
+                for (const auto& pad : pads) {
+                    memcpy(in + in_len, pad, 16);
+                    const int rc = isize ? strk_inf::inflate_block(in, in_len, out, (int)isize, t, lens) : 0;
+                    if (rc == 0 && crc32(0, out, isize) == crc) { fprintf(stderr, "%s: block at %ld: accepted\n", argv[a], off); return 1; }
+                }
+                free(in); free(out); free(t); free(lens);
+                ++refused;
+                off = next;
+                continue;
+            }
             const int rc = isize ? strk_inf::inflate_block(in, in_len, out, (int)isize, t, lens) : 0;
             if (rc) { fprintf(stderr, "%s: block at %ld: error %d\n", argv[a], off, rc); return 1; }
             if (crc32(0, out, isize) != crc) { fprintf(stderr, "%s: block at %ld: CRC mismatch\n", argv[a], off); return 1; }
@@ -66,6 +85,6 @@ int main(int argc, char** argv) {
             off = next;
         }
     }
-    printf("%ld blocks, %ld bytes, %ld truncated / corrupted variants: clean\n", blocks, bytes, variants);
+    printf("%ld blocks, %ld bytes, %ld truncated / corrupted variants, %ld refusals: clean\n", blocks, bytes, variants, refused);
     return 0;
 }
