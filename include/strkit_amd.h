@@ -164,6 +164,13 @@ int strk_init(int device, strk_ctx** out);
 void strk_destroy(strk_ctx* ctx);
 const char* strk_last_error(void);
 const char* strk_version(void);
+/* Consecutive reads whose band items the planning kernel lists in one order, by (band class, prefix rows), in a call of n_reads
+ * reads (small calls use a smaller scope).  For tests and tools that place reads around a block edge. */
+int32_t strk_plan_scope(int32_t n_reads);
+/* The reads of one band class (0..7) in the order the planning kernel of ctx's last batched call listed them: up to `cap`
+ * read indices into out_reads (host memory); returns the length of the list (>= 0) or an error.  For tests of the list
+ * order; valid until the next call on ctx. */
+int strk_band_list(strk_ctx* ctx, int32_t band_class, int32_t* out_reads, int32_t cap);
 /* Forget what the library has learnt about the current sample (the default candidate-window level per motif-length bucket,
  * process-wide): call it when a process moves on to ANOTHER sample (the reference runs one sample per process,
  * call_sample.py:265).  Per-context state (band probation, grid history) goes with strk_destroy. */

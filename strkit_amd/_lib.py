@@ -66,7 +66,7 @@ class StrkStats(C.Structure):
 
 
 # Every symbol include/strkit_amd.h declares (tests check the .so exports exactly these).
-EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk_adaptive_reset", "strk_device_mem", "strk_host_register", "strk_host_unregister",
+EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk_plan_scope", "strk_band_list", "strk_adaptive_reset", "strk_device_mem", "strk_host_register", "strk_host_unregister",
            "strk_host_is_pinned", "strk_repeat_count", "strk_count_loci",
            "strk_count_loci_device", "strk_submit_loci_device", "strk_finish", "strk_score_table",
            "strk_score_ref_table", "strk_ref_repeat_count", "strk_ref_repeat_count_batch", "strk_realign", "strk_realign_i16_flags", "strk_bam_scan",
@@ -119,6 +119,10 @@ def load(build: bool = True):
         L.strk_destroy.argtypes = [C.c_void_p]
         L.strk_last_error.restype = C.c_char_p
         L.strk_version.restype = C.c_char_p
+        L.strk_plan_scope.restype = C.c_int32
+        L.strk_plan_scope.argtypes = [C.c_int32]
+        L.strk_band_list.restype = C.c_int
+        L.strk_band_list.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
         L.strk_adaptive_reset.restype = None
         L.strk_adaptive_reset.argtypes = []
         L.strk_repeat_count.restype = C.c_int
@@ -257,6 +261,11 @@ def load(build: bool = True):
         L.strk_host_is_pinned.argtypes = [C.c_void_p, C.c_int64]
         _lib = L
         return L
+
+
+def plan_scope(n_reads: int) -> int:
+    """Consecutive reads whose band items the planning kernel lists in one order in a call of n_reads reads (strk_plan_scope)."""
+    return int(load().strk_plan_scope(int(n_reads)))
 
 
 def device_mem(device: int = 0) -> tuple[int, int]:

@@ -138,6 +138,7 @@ struct GroupStage {
 
 struct strk_ctx {
     int device = 0;
+    int last_list_stride = 0;   // list_stride of the last call planned on this context (strk_band_list)
     // workspace
     DevBuf read_locus, win_lo, win_n, tab_off, table, cls_list, band_recs, band_recs_w, long_list, counters, scratch, state_i32, state_f64, spec, rhash, rep, exact;
     DevBuf win_lo2, win_n2, tab_off2, table2, items;
@@ -279,6 +280,7 @@ KArgs make_args(strk_ctx* c, const strk_batch* b, int end_flags, int window, int
     a.long_slot = (long long)c->long_slot_ints;
     a.long_waves = kLongWaves;
     a.list_stride = list_stride;
+    c->last_list_stride = list_stride;
     a.band_tune = {kBandSpanW, kBandSlackM8, kBandSpanMaxMotif};
     a.end_flags = end_flags;
     a.window = window;
@@ -310,11 +312,13 @@ void enqueue_scoring(strk_ctx* c, const KArgs& a, int mode, const int32_t* d_ite
     // default bench gave 92.8 M reads/s twice where the unsorted queue gives 103-111 (profiles/r04_sort_wide_always_experiment.txt).
     const bool hist = c->hist.usable(mode, a.band_mode);   // the previous call's queue lengths say something about this one's
     const bool sort_wide = a.band_mode && mode == 0 && !force_generic && (!hist || (c->hist.wide_chunks > 0 && c->hist.wide_chunks <= 8192));
-    hipLaunchKernelGGL(k_plan, dim3((n_items + 255) / 256), dim3(256), 0, st, a, mode, d_items, n_items, force_generic);
+    const int plan_scope = plan_scope_of(n_items);   // small calls: one read per thread over more blocks (strk_plan_order.h)
+    hipLaunchKernelGGL(k_plan, dim3((n_items + plan_scope - 1) / plan_scope), dim3(kPlanThreads), 0, st, a, mode, d_items, n_items, force_generic,
+                       plan_reads_per_thread(n_items));
     // A call that shares the device with other calls in flight takes fifteen sixteenths of the CU slots per kernel: the free
     // slots are what lets the LDS-holding tail kernels of one call (k_dp_band_wide, k_dp_all, k_dp_long) start while another
-    // call's band pass is resident; k_hash / k_plan / k_replay need no LDS and fit NEXT to two band waves per SIMD (2 x 184 of
-    // 512 VGPRs).  tools/grid_sweep2.sh, two calls in flight: 448 blocks 239 M reads/s, 480 -> 246 M, 496 -> 240 M, 512 -> 186 M
+    // call's band pass is resident; k_hash / k_replay need no LDS, k_plan 4 KB, and all three fit NEXT to two band waves per SIMD
+    // (2 x 168 of 512 VGPRs; strk_plan_order.h).  tools/grid_sweep2.sh, two calls in flight: 448 blocks 239 M reads/s, 480 -> 246 M, 496 -> 240 M, 512 -> 186 M
     // (round 2, three calls in flight and 219 VGPRs: 7/8 was the best).
     // ... which pays when ONE kernel carries the call (BASELINE config 2: k_dp_band 1.15 ms, the others 0.13 ms; configs 3 and 5
     // alike: k_dp_all / k_dp_band_wide alone).  Where k_dp_band AND k_dp_band_wide are both large — config 4's shard: 3.4 and 2.0
@@ -884,6 +888,21 @@ extern "C" {
 
 const char* strk_last_error(void) { return g_err.c_str(); }
 const char* strk_version(void) { return "strkit_amd 0.1.0 (gfx950)"; }
+int32_t strk_plan_scope(int32_t n_reads) { return plan_scope_of(n_reads); }
+int strk_band_list(strk_ctx* c, int32_t band_class, int32_t* out_reads, int32_t cap) {
+    if (!c || band_class < 0 || band_class >= kNumBandClasses || cap < 0 || (cap > 0 && !out_reads)) return STRK_E_INVALID;
+    if (c->last_list_stride <= 0 || !c->cls_list.p || !c->counters.p) return 0;
+    if (hipSetDevice(c->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return STRK_E_DEVICE;
+    int32_t n = 0;
+    if (hipMemcpy(&n, c->counters.as<int32_t>() + kCntClass0 + kBandClass0 + band_class, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) return STRK_E_DEVICE;
+    n = std::max(0, std::min(n, (int32_t)c->last_list_stride));
+    const int32_t k = std::min(n, cap);
+    if (k > 0) {   // (read, locus) pairs: every other int
+        const int32_t* src = c->cls_list.as<int32_t>() + (size_t)(kBandClass0 + band_class) * c->last_list_stride * 2;
+        if (hipMemcpy2D(out_reads, sizeof(int32_t), src, 2 * sizeof(int32_t), sizeof(int32_t), (size_t)k, hipMemcpyDeviceToHost) != hipSuccess) return STRK_E_DEVICE;
+    }
+    return n;
+}
 
 void strk_adaptive_reset(void) { g_window.reset(); }
 

@@ -22,7 +22,14 @@ struct BandLayout {
     // class-byte array: selb[pad + x] <-> db[x]; `pad` pad selectors in front and up to pad + kBandHiPad
     // behind, sized so that no column the two passes can ask for (virtual rows, rows beyond |db|, the
     // prefetch) falls outside it: the hot loop indexes it without clamping.
-    int wd, pad, maxdb, maxcol, off_sel, off_cp, off_ct, off_b0, group_bytes, sel_len;
+    // The backward row symbols `ct` (right flank: kBandMaxFlank rows) are read by the backward pass only, which runs BEFORE the
+    // forward pass reads the forward row symbols `cp`.  In layout 0 — the one that sets the kernel's LDS: eight groups per wave —
+    // ct lies on cp's last ct_bytes bytes: the prefix rows that fall there (indices >= cp_tail: only items of more than
+    // cp_tail - G prefix rows have any) are staged between the two passes.  That is what pays for windows of 512 bases in
+    // layout 0: selb and cp grow by 64 bytes per group each, ct's 160 go, and two blocks per CU keep their 4.5 KB for the
+    // other call's k_plan.  (Layout 1 keeps ct to itself: its four groups per wave need less than layout 0's eight either
+    // way, and the 16-lane classes are where the kernel's register allocation peaks.)
+    int wd, pad, maxdb, maxcol, off_sel, off_cp, cp_bytes, ct_bytes, cp_tail, off_ct, off_b0, group_bytes, sel_len;
     static constexpr int OFF_COMB = 0, OFF_MISC = OFF_COMB + kTableMax * 4, OFF_LMAX = OFF_MISC + 16;
     static constexpr int kBandHiPad = kBandRowSlack + 32;
     __host__ __device__ constexpr BandLayout(int c)   // c = layout class (band_class_layout: 0..3)
@@ -30,8 +37,11 @@ struct BandLayout {
           off_sel(OFF_LMAX + (band_class_lmax(c) ? kTableMax * 4 : 0)),
           off_cp(off_sel + ((band_max_db(c) + 2 * ((128 << c) + (8 << c) + 8) + kBandHiPad + 15) & ~15)),
           // forward row symbols: the whole prefix (classes 0, 1) or 256 flank + 256 motif symbols (2, 3)
-          off_ct(off_cp + (band_class_fly(c) ? 512 : ((band_max_db(c) + kBandRowSlack + 2 * (8 << c) + 4 + 15) & ~15))),
-          off_b0(off_ct + ((kBandMaxFlank + 2 * (8 << c) + 4 + 15) & ~15)),
+          cp_bytes(band_class_fly(c) ? 512 : ((band_max_db(c) + kBandRowSlack + 2 * (8 << c) + 4 + 15) & ~15)),
+          ct_bytes((kBandMaxFlank + 2 * (8 << c) + 4 + 15) & ~15),
+          cp_tail(c == 0 ? cp_bytes - ct_bytes : cp_bytes),
+          off_ct(off_cp + cp_tail),
+          off_b0(off_ct + ct_bytes),
           group_bytes(off_b0 + ((band_max_col(c) * 2 + 15) & ~15)),
           sel_len((band_max_db(c) + 2 * ((128 << c) + (8 << c) + 8) + kBandHiPad) & ~3) {}
 };
@@ -329,6 +339,13 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
     uint8_t* const ct = Lg + lay.off_ct;
     short* const b0col = reinterpret_cast<short*>(Lg + lay.off_b0);
     uint8_t* const motifL = FLY ? cp + 256 : Lg + lay.off_b0;   // non-FLY: the motif sits in b0col until that is initialised
+    constexpr bool TAIL = lay.cp_tail < lay.cp_bytes;           // layout 0: ct lies on the end of cp
+    constexpr int kRowTail = lay.cp_tail - (G - 1);             // first prefix row whose symbol lies in ct's bytes (TAIL)
+    // b0col stays 16-bit with windows of 512 bases: it holds the backward pass's last row in G-space, G = H + g (r + j) with
+    // H <= 2 min(r, j), r <= kBandMaxFlank and j <= |db|: at most 2 * 127 + 5 * (127 + 512) = 3 449.  (The forward pass's cells are
+    // 32-bit registers; even their largest value, 2 * 512 + 5 * (512 + kBandRowSlack + 512) = 6 624, is far below 32 767, and layout 1
+    // has held windows of 1 024 bases in the same 16 bits since round 2.)
+    static_assert(2 * kBandMaxFlank + kGap * (kBandMaxFlank + band_max_db(1)) < 32767 + kBandNeg16, "b0col: 16-bit columns, kBandNeg16 as -inf");
 
     // the item's record was fetched by the caller while the previous chunk was being processed
     int r = 0, nfl = 1, ntr = 0, nfr = 1, m = 1, lo = 0, n = 0;
@@ -348,7 +365,7 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
     const bool dbBeg = a.end_flags & 1, dbEnd = a.end_flags & 2, cBeg = a.end_flags & 4, cEnd = a.end_flags & 8;
 
     // ---- stage: selector bytes with pads, row symbols ----
-    if (first) misc[0] = 0;
+    if (first) { misc[0] = 0; misc[1] = act ? q2.z : 0; }   // misc[1]: the motif's offset, for the rows staged between the passes
     wave_lds_sync();
     {
         // pads in front of the window and as far behind it as a pass can reach; the window itself a dword per lane, eight
@@ -416,20 +433,21 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
             // (as far as the longest item of the wave reads: every byte a step can fetch is a valid table offset)
             // Three stretches, a loop each: G - 1 null rows in front, the flank rows (their selector bytes), the motif rows
             // (phase kept per lane), null rows behind.
+            // The rows from kRowTail on lie where ct is staged below: they follow between the two passes.
             const int lenP = wave_max_over_groups(rowsP) + 2 * (G - 1) + 4;
             for (int idx = lig; idx < G - 1; idx += G) cp[idx] = (uint8_t)(8 * kNullSym);
             uint8_t* const cpr = cp + (G - 1);          // cpr[row]
-            for (int row = lig; row < min(nfl, rowsP); row += G) cpr[row] = (uint8_t)(8 * (kBandTblClass0 + selb[lay.pad + row]));
+            for (int row = lig; row < min(min(nfl, rowsP), kRowTail); row += G) cpr[row] = (uint8_t)(8 * (kBandTblClass0 + selb[lay.pad + row]));
             {
                 const int gstep = G % m;
                 int ph = lig % m;
-                for (int row = nfl + lig; row < rowsP; row += G) {
+                for (int row = nfl + lig; row < min(rowsP, kRowTail); row += G) {
                     cpr[row] = (uint8_t)(8 * motifL[ph]);
                     ph += gstep;
                     if (ph >= m) ph -= m;
                 }
             }
-            for (int row = rowsP + lig; row < lenP - (G - 1); row += G) cpr[row] = (uint8_t)(8 * kNullSym);
+            for (int row = rowsP + lig; row < min(lenP - (G - 1), kRowTail); row += G) cpr[row] = (uint8_t)(8 * kNullSym);
         }
         const int lenT = wave_max_over_groups(rowsT) + 2 * (G - 1) + 4;
         for (int idx = lig; idx < lenT; idx += G) {
@@ -473,6 +491,23 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
     band_pass<G, D, true, false, false>(x, ct, run ? rowsT : 0, geo.bdlo, dbEnd, cEnd, 0, 0, 1, geo.cmin, geo.ncol, comb, b0col, lmaxA);
     wave_lds_sync();
     nextC();
+    if (TAIL) {
+        // the prefix rows that share their bytes with ct (BandLayout): flank rows from the selector bytes, motif rows from the
+        // motif itself (its LDS copy made way for the column array), null rows as far as the longest item of the wave reads.
+        // Items of up to kRowTail prefix rows — all but the longest few per cent — have at most the null rows to write.
+        const int lenP = wave_max_over_groups(rowsP) + 2 * (G - 1) + 4;
+        uint8_t* const cpr = cp + (G - 1);
+        const uint8_t* const mo = a.motifs + misc[1];   // (the offset from LDS, not from a register held across the backward pass)
+        int mm = m, row0 = kRowTail + lig;
+        asm volatile("" : "+v"(mm), "+v"(row0));   // (or the division's set-up and the loop's first addresses are computed above the backward pass and held across it)
+        for (int row = row0; row < lenP - (G - 1); row += G) {
+            int sym = kNullSym;
+            if (row < min(nfl, rowsP)) sym = kBandTblClass0 + selb[lay.pad + row];
+            else if (row < rowsP) sym = s_enc[mo[(row - nfl) % mm]];
+            cpr[row] = (uint8_t)(8 * sym);
+        }
+        wave_lds_sync();
+    }
     x.tbl = s_tbl;
     band_pass<G, D, false, FLY, LMAX>(x, cp, run ? rowsP : 0, geo.dlo, dbBeg, cBeg, nEff, nfl + lo * m, m, geo.cmin, geo.ncol, comb, b0col, lmaxA);
     wave_lds_sync();
@@ -548,6 +583,8 @@ __device__ __forceinline__ void band_kernel_body(const KArgs& a) {
     constexpr int kTblBytes = 2 * kBandTblBytes;
     __shared__ __attribute__((aligned(16))) uint8_t lds[kTblBytes + 4 * kBandWaveLds + kLdsSlack];
     __shared__ uint8_t s_enc[256];
+    // two blocks per CU, and beside them the 4.5 KB that a k_plan block of the other call in flight needs (strk_plan_order.h)
+    static_assert(2 * (sizeof(lds) + 256) + 4608 <= 160 * 1024, "band kernels: two blocks per CU with room for k_plan's LDS");
     uint8_t* const s_tbl = lds;
     {
         s_enc[threadIdx.x] = c_enc[threadIdx.x];

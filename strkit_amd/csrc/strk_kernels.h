@@ -25,10 +25,12 @@
 
 #include "strk_scoring.h"
 #include "strk_search.h"
+#include "strk_plan_order.h"
 
 namespace strk {
 
 constexpr int kTableMax = 32;       // max candidates per read in one DP item
+static_assert(kTableMax < 64, "k_plan keeps a band item's table length in six bits");
 constexpr int kNegInf = -(1 << 29);
 constexpr int kFastFlankMax = 127;  // right-flank rows the fast classes stage in LDS (the default flank is 70)
 constexpr int kMotifMax = 256;     // the fast kernel stages the encoded motif in LDS (<= 2 * smallest capacity bytes)
@@ -218,6 +220,12 @@ __device__ inline bool same_read(const KArgs& a, int r, int q) {
     const uint8_t* y = a.seqs + a.seq_off[q];
     const int len = a.nfl[r] + a.ntr[r] + a.nfr[r];
     int i = 0;
+    for (; i + 32 <= len; i += 32) {   // eight loads in flight per test: equal reads are compared to their end, one round trip per 32 bytes
+        unsigned long long u0, u1, u2, u3, v0, v1, v2, v3;
+        __builtin_memcpy(&u0, x + i, 8); __builtin_memcpy(&u1, x + i + 8, 8); __builtin_memcpy(&u2, x + i + 16, 8); __builtin_memcpy(&u3, x + i + 24, 8);
+        __builtin_memcpy(&v0, y + i, 8); __builtin_memcpy(&v1, y + i + 8, 8); __builtin_memcpy(&v2, y + i + 16, 8); __builtin_memcpy(&v3, y + i + 24, 8);
+        if ((u0 ^ v0) | (u1 ^ v1) | (u2 ^ v2) | (u3 ^ v3)) return false;
+    }
     for (; i + 8 <= len; i += 8) {
         unsigned long long u, v;
         __builtin_memcpy(&u, x + i, 8);
@@ -229,121 +237,183 @@ __device__ inline bool same_read(const KArgs& a, int r, int q) {
     return true;
 }
 
+// The earliest read of locus-mates [q0, r) that is byte-identical to read r, or r.  The hashes are scanned four at a time, and the
+// byte-wise comparison stands BEHIND the scan, not inside it: the lanes of a wave find their candidates at different places, and
+// a comparison inside the scan would run once per such place for the whole wave (a third of BASELINE config 2's reads are copies).
+__device__ inline int first_identical(const KArgs& a, int r, int q0) {
+    const unsigned long long h = a.rhash[r];
+    int q = q0;
+    for (;;) {
+        int cand = r;
+        for (; q < r && cand == r; q += 4) {   // (indices beyond r - 1 are clamped to r, whose hash is h: "no earlier read")
+            const unsigned long long h0 = a.rhash[q], h1 = a.rhash[min(q + 1, r)], h2 = a.rhash[min(q + 2, r)], h3 = a.rhash[min(q + 3, r)];
+            const int k = h0 == h ? 0 : (h1 == h ? 1 : (h2 == h ? 2 : (h3 == h ? 3 : 4)));
+            if (k < 4 && q + k < r) cand = q + k;
+        }
+        if (cand == r) return r;
+        if (same_read(a, r, cand)) return cand;
+        q = cand + 1;   // equal hashes, different reads: on with the scan
+    }
+}
+
 // mode 0: windows from est_cn +/- window, table slot r*table_stride;
 // mode 1: windows and table offsets are already in win_lo / win_n / tab_off (strk_score_table,
 //         window-miss rounds); `items` (optional) restricts the launch to a list of reads.
+// A block takes kPlanThreads * rpt consecutive reads (items), rpt per thread: 1 in small calls, kPlanReadsPerThread in large ones (strk_plan_order.h).
 // Class lists are filled with one global atomic per class per block (LDS histogram first).
-__global__ void __launch_bounds__(256) k_plan(KArgs a, int mode, const int32_t* items, int n_items, int force_generic) {
+__global__ void __launch_bounds__(kPlanThreads) k_plan(KArgs a, int mode, const int32_t* items, int n_items, int force_generic, int rpt) {
     __shared__ int s_cnt[kNumLists];
     __shared__ int s_base[kNumLists];
     __shared__ unsigned long long s_cells, s_bytes_band, s_bytes_exact, s_bytes_wide, s_bytes_long, s_cells_k[4];
-    __shared__ __attribute__((aligned(16))) unsigned s_key[256];
+    __shared__ int s_bin[kPlanBins];            // band items of this block per (class, rows) bin, then each bin's cursor
+    __shared__ int s_wsum[kPlanWaves];
     __shared__ int s_below[kNumBandClasses];   // band items of this block in band classes below c
     __shared__ int s_lb[kWinBuckets];   // loci per motif-length bucket (counted at a locus's first read)
-    if (threadIdx.x < kWinBuckets) s_lb[threadIdx.x] = 0;
-    if (threadIdx.x < kNumLists) s_cnt[threadIdx.x] = 0;
-    if (threadIdx.x == 0) { s_cells = 0; s_bytes_band = 0; s_bytes_exact = 0; s_bytes_wide = 0; s_bytes_long = 0; }
-    if (threadIdx.x < 4) s_cells_k[threadIdx.x] = 0;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (tid < kWinBuckets) s_lb[tid] = 0;
+    if (tid < kNumLists) s_cnt[tid] = 0;
+    if (tid == 0) { s_cells = 0; s_bytes_band = 0; s_bytes_exact = 0; s_bytes_wide = 0; s_bytes_long = 0; }
+    if (tid < 4) s_cells_k[tid] = 0;
+    for (int b = tid; b < kPlanBins; b += kPlanThreads) s_bin[b] = 0;
     __syncthreads();
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    int r = 0, l = 0, nfl = 0, ntr = 0, nfr = 0, m = 1, lo = 0, n = 0;
-    if (gid < n_items) {
-        r = items ? items[gid] : gid;
-        // locus of read r: last l with read_off[l] <= r
-        int lo_l = 0, hi_l = a.n_loci;
-        while (hi_l - lo_l > 1) {
-            const int mid = (lo_l + hi_l) >> 1;
-            if (a.read_off[mid] <= r) lo_l = mid; else hi_l = mid;
-        }
-        l = lo_l;
-        a.read_locus[r] = l;
-        m = a.motif_off[l + 1] - a.motif_off[l];
-        if (mode == 0 && r == a.read_off[l] && m >= 1) atomicAdd(&s_lb[win_bucket(m)], 1);
-        nfl = a.nfl[r]; ntr = a.ntr[r]; nfr = a.nfr[r];
-        if (m < 1 || nfl < 0 || ntr < 0 || nfr < 0) {
-            atomicOr(&a.counters[kCntError], kErrBadInput);
-            a.win_n[r] = 0;
-            n = 0;
-        } else if (mode == 0) {
-            const long long est = a.est_cn[r];
-            // the estimate round(|tr| / |motif|) drifts with the copy number (indels accumulate): widen the
-            // window by one size per 128 copies, as far as the table stride allows
-            const long long w = min((long long)a.window_b[win_bucket(m)] + min(max(est, 0ll) >> 7, 7ll), (long long)(a.table_stride - 1) / 2);
-            long long w_lo = est - w, w_hi = est + w;
-            if (w_lo < 0) w_lo = 0;
-            if (w_hi < w_lo) w_hi = w_lo;  // negative estimates: keep a one-entry window at 0
-            if (w_hi - w_lo + 1 > a.table_stride) w_hi = w_lo + a.table_stride - 1;
-            lo = (int)w_lo;
-            n = (int)(w_hi - w_lo + 1);
-            int rep = r;
-            if (a.rhash) {
-                const unsigned long long h = a.rhash[r];
-                for (int q = a.read_off[l]; q < r; ++q)
-                    if (a.rhash[q] == h && same_read(a, r, q)) { rep = q; break; }  // first occurrence
+    // What the second pass over a thread's reads keeps of the first, one word per read: a band item's (class << 18 | n << 12 | bin),
+    // -(n + 1) for the others; locus and window come back from read_locus / win_lo.  The first pass is ONE loop body (the
+    // word goes into its register by selects): unrolled, the reads' bodies interleave and the kernel no longer fits into the
+    // 88 VGPRs that let two of its waves per SIMD run beside a band pass.
+    int p_key[kPlanReadsPerThread];
+#pragma unroll
+    for (int k = 0; k < kPlanReadsPerThread; ++k) p_key[k] = -1;
+#pragma unroll 1
+    for (int j = 0; j < rpt; ++j) {
+        const int gid = blockIdx.x * (kPlanThreads * rpt) + j * kPlanThreads + tid;
+        int r = 0, l = 0, nfl = 0, ntr = 0, nfr = 0, m = 1, lo = 0, n = 0;
+        if (gid < n_items) {
+            r = items ? items[gid] : gid;
+            // locus of read r: last l with read_off[l] <= r
+            int lo_l = 0, hi_l = a.n_loci;
+            while (hi_l - lo_l > 1) {
+                const int mid = (lo_l + hi_l) >> 1;
+                if (a.read_off[mid] <= r) lo_l = mid; else hi_l = mid;
             }
-            a.rep[r] = rep;
-            // no speculative result yet: the kernels that score a read AND search it overwrite this, a read that ends in
-            // the generic kernel (scores only) keeps it and is searched by k_replay on its table
-            if (a.spec) a.spec[r] = make_int4(0, 0, 0, kSpecMiss);
-            a.win_lo[r] = lo;
-            a.win_n[r] = n;
-            a.tab_off[r] = (int64_t)rep * a.table_stride;
-            if (rep != r) {
-                n = 0;  // no DP item: the table (and the speculative search) of `rep` serve this read too
-                atomicAdd(&a.counters[kCntDup], 1);
+            l = lo_l;
+            a.read_locus[r] = l;
+            m = a.motif_off[l + 1] - a.motif_off[l];
+            if (mode == 0 && r == a.read_off[l] && m >= 1) atomicAdd(&s_lb[win_bucket(m)], 1);
+            nfl = a.nfl[r]; ntr = a.ntr[r]; nfr = a.nfr[r];
+            if (m < 1 || nfl < 0 || ntr < 0 || nfr < 0) {
+                atomicOr(&a.counters[kCntError], kErrBadInput);
+                a.win_n[r] = 0;
+                n = 0;
+            } else if (mode == 0) {
+                const long long est = a.est_cn[r];
+                // the estimate round(|tr| / |motif|) drifts with the copy number (indels accumulate): widen the
+                // window by one size per 128 copies, as far as the table stride allows
+                const long long w = min((long long)a.window_b[win_bucket(m)] + min(max(est, 0ll) >> 7, 7ll), (long long)(a.table_stride - 1) / 2);
+                long long w_lo = est - w, w_hi = est + w;
+                if (w_lo < 0) w_lo = 0;
+                if (w_hi < w_lo) w_hi = w_lo;  // negative estimates: keep a one-entry window at 0
+                if (w_hi - w_lo + 1 > a.table_stride) w_hi = w_lo + a.table_stride - 1;
+                lo = (int)w_lo;
+                n = (int)(w_hi - w_lo + 1);
+                const int rep = a.rhash ? first_identical(a, r, a.read_off[l]) : r;
+                a.rep[r] = rep;
+                // no speculative result yet: the kernels that score a read AND search it overwrite this, a read that ends in
+                // the generic kernel (scores only) keeps it and is searched by k_replay on its table
+                if (a.spec) a.spec[r] = make_int4(0, 0, 0, kSpecMiss);
+                a.win_lo[r] = lo;
+                a.win_n[r] = n;
+                a.tab_off[r] = (int64_t)rep * a.table_stride;
+                if (rep != r) {
+                    n = 0;  // no DP item: the table (and the speculative search) of `rep` serve this read too
+                    atomicAdd(&a.counters[kCntDup], 1);
+                }
+            } else {
+                lo = a.win_lo[r];
+                n = a.win_n[r];
             }
-        } else {
-            lo = a.win_lo[r];
-            n = a.win_n[r];
         }
-    }
-    // Long windows (window-miss rounds, explicit tables) are cut into items of <= kTableMax sizes.
-    unsigned long long cells = 0;
-    const unsigned long long ndb = (unsigned long long)nfl + ntr + nfr;
-    int band_list = -1;   // >= 0: the read goes to the band kernel first
-    if (a.band_mode && mode == 0 && n > 0 && n <= kTableMax && !force_generic && r < a.band_limit) {
-        const BandGeo geo = band_geometry(nfl, ntr, nfr, m, lo, n, a.band_tune);
-        if (geo.ok) band_list = kBandClass0 + geo.cls;
-    }
-    if (a.exact && gid < n_items && n > 0) a.exact[r] = band_list < 0;
-    int first_c = -1;
-    for (int k0 = 0; k0 < n; k0 += kTableMax) {
-        const int nn = min(kTableMax, n - k0);
-        const int c = band_list >= 0 ? band_list : classify(nfl, ntr, nfr, m, lo + k0, nn, force_generic, a.ref_mode);
-        if (k0 == 0) first_c = c;
-        atomicAdd(&s_cnt[c], 1);
-        unsigned long long cc = 0;
-        if (c == kGenericClass) {
-            for (int k = 0; k < nn; ++k) cc += ndb * ((unsigned long long)nfl + (unsigned long long)(lo + k0 + k) * m + nfr);
-        } else if (band_list >= 0) {
-            cc = (unsigned long long)band_class_wd(band_list - kBandClass0) * ((unsigned long long)nfl + (unsigned long long)(lo + k0 + nn - 1) * m + nfr);
-        } else {
-            cc = ndb * ((unsigned long long)nfl + (unsigned long long)(lo + k0 + nn - 1) * m + nfr);
+        // Long windows (window-miss rounds, explicit tables) are cut into items of <= kTableMax sizes.
+        unsigned long long cells = 0;
+        const unsigned long long ndb = (unsigned long long)nfl + ntr + nfr;
+        int band_list = -1;   // >= 0: the read goes to the band kernel first
+        if (a.band_mode && mode == 0 && n > 0 && n <= kTableMax && !force_generic && r < a.band_limit) {
+            const BandGeo geo = band_geometry(nfl, ntr, nfr, m, lo, n, a.band_tune);
+            if (geo.ok) band_list = kBandClass0 + geo.cls;
         }
-        cells += cc;
-        if (cc && cell_slot_of_list(c) >= 0) atomicAdd(&s_cells_k[cell_slot_of_list(c) - kCellBand], cc);
-    }
-    if (cells) {
-        atomicAdd(&s_cells, cells);
-        atomicAdd(band_list >= 0 ? &s_bytes_band : &s_bytes_exact, ndb + 16);
-        if (band_list >= 0 && band_class_wide_kernel(band_list - kBandClass0)) atomicAdd(&s_bytes_wide, ndb + 16);   // k_dp_band_wide's classes
-        if (first_c == kLongClass) atomicAdd(&s_bytes_long, ndb + 16);
+        if (a.exact && gid < n_items && n > 0) a.exact[r] = band_list < 0;
+        int first_c = -1;
+        for (int k0 = 0; k0 < n; k0 += kTableMax) {
+            const int nn = min(kTableMax, n - k0);
+            const int c = band_list >= 0 ? band_list : classify(nfl, ntr, nfr, m, lo + k0, nn, force_generic, a.ref_mode);
+            if (k0 == 0) first_c = c;
+            atomicAdd(&s_cnt[c], 1);
+            unsigned long long cc = 0;
+            if (c == kGenericClass) {
+                for (int k = 0; k < nn; ++k) cc += ndb * ((unsigned long long)nfl + (unsigned long long)(lo + k0 + k) * m + nfr);
+            } else if (band_list >= 0) {
+                cc = (unsigned long long)band_class_wd(band_list - kBandClass0) * ((unsigned long long)nfl + (unsigned long long)(lo + k0 + nn - 1) * m + nfr);
+            } else {
+                cc = ndb * ((unsigned long long)nfl + (unsigned long long)(lo + k0 + nn - 1) * m + nfr);
+            }
+            cells += cc;
+            if (cc && cell_slot_of_list(c) >= 0) atomicAdd(&s_cells_k[cell_slot_of_list(c) - kCellBand], cc);
+        }
+        if (cells) {
+            atomicAdd(&s_cells, cells);
+            atomicAdd(band_list >= 0 ? &s_bytes_band : &s_bytes_exact, ndb + 16);
+            if (band_list >= 0 && band_class_wide_kernel(band_list - kBandClass0)) atomicAdd(&s_bytes_wide, ndb + 16);   // k_dp_band_wide's classes
+            if (first_c == kLongClass) atomicAdd(&s_bytes_long, ndb + 16);
+        }
+        int key = -(n + 1);
+        if (band_list >= 0) {
+            const int bin = plan_bin(band_list - kBandClass0, nfl + (lo + n - 1) * m);
+            atomicAdd(&s_bin[bin], 1);
+            key = ((band_list - kBandClass0) << 18) | (n << 12) | bin;   // (n <= kTableMax)
+        }
+#pragma unroll
+        for (int k = 0; k < kPlanReadsPerThread; ++k) p_key[k] = k == j ? key : p_key[k];
     }
     __syncthreads();
-    if (threadIdx.x < kNumLists) {
-        const int c = threadIdx.x;
+    if (tid < kNumLists) {
+        const int c = tid;
         s_base[c] = s_cnt[c] ? atomicAdd(&a.counters[kCntClass0 + c], s_cnt[c]) : 0;
     }
+    // Band items of a block are listed in the order of (band class, bin of the prefix rows, read): strk_plan_order.h.
+    // Exclusive scan of the histogram: a thread's own bins, the lanes in front of it, the waves in front of its wave.
+    int bin_cnt[kPlanBinsPerThread], own = 0;
+#pragma unroll
+    for (int k = 0; k < kPlanBinsPerThread; ++k) {
+        const int b = tid * kPlanBinsPerThread + k;
+        bin_cnt[k] = b < kPlanBins ? s_bin[b] : 0;
+        own += bin_cnt[k];
+    }
+    int incl = own;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int v = __shfl_up(incl, o);
+        if (lane >= o) incl += v;
+    }
+    if (lane == 63) s_wsum[wave] = incl;
     __syncthreads();
-    if (threadIdx.x < kNumBandClasses) {
+    if (tid < kNumBandClasses) {
         int below = 0;
-        for (int k = 0; k < (int)threadIdx.x; ++k) below += s_cnt[kBandClass0 + k];
-        s_below[threadIdx.x] = below;
+        for (int k = 0; k < tid; ++k) below += s_cnt[kBandClass0 + k];
+        s_below[tid] = below;
+    }
+    {
+        int pre = incl - own;
+        for (int w = 0; w < wave; ++w) pre += s_wsum[w];
+#pragma unroll
+        for (int k = 0; k < kPlanBinsPerThread; ++k) {
+            const int b = tid * kPlanBinsPerThread + k;
+            if (b < kPlanBins) s_bin[b] = pre;
+            pre += bin_cnt[k];
+        }
     }
     __syncthreads();
-    if (threadIdx.x < kNumLists) s_cnt[threadIdx.x] = 0;
-    if (threadIdx.x < kWinBuckets && s_lb[threadIdx.x]) atomicAdd(&a.counters[kCntLociB + threadIdx.x], s_lb[threadIdx.x]);
-    if (threadIdx.x == 0 && s_cells) {
+    if (tid < kNumLists) s_cnt[tid] = 0;
+    if (tid < kWinBuckets && s_lb[tid]) atomicAdd(&a.counters[kCntLociB + tid], s_lb[tid]);
+    if (tid == 0 && s_cells) {
         atomicAdd(a.cells, s_cells);
         if (s_bytes_band) atomicAdd(a.cells + 2, s_bytes_band);
         if (s_bytes_exact) atomicAdd(a.cells + 3, s_bytes_exact);
@@ -352,44 +422,64 @@ __global__ void __launch_bounds__(256) k_plan(KArgs a, int mode, const int32_t* 
         for (int k = 0; k < 4; ++k)
             if (s_cells_k[k]) atomicAdd(a.cells + kCellBand + k, s_cells_k[k]);
     }
-    __syncthreads();
-    // Band items of a block are listed in the order of (band class, prefix rows): the band kernel runs the 8 (4, 2, 1) items of
-    // a chunk in lock-step for as many steps as the longest one needs (chunks of a 256-read block in arrival order: 8.5 % more
-    // steps than the items need; sorted by rows: 4 %).  rank = items of this block that sort before mine.
-    int band_rank = 0;
-    {
-        // 32-bit keys (class | prefix rows | thread): items that sort before mine = keys below mine, four per LDS read; those of
-        // the lower classes are the same number for every item of a class (s_below)
-        const unsigned mine = band_list >= 0 ? ((unsigned)(band_list - kBandClass0) << 28) |
-                                                   ((unsigned)min(nfl + (lo + n - 1) * m, (1 << 20) - 1) << 8) | threadIdx.x
-                                             : ~0u;
-        s_key[threadIdx.x] = mine;
-        __syncthreads();
-        if (band_list >= 0) {
-            const uint4* k4 = reinterpret_cast<const uint4*>(s_key);
-            for (int q = 0; q < 64; ++q) {
-                const uint4 o = k4[q];
-                band_rank += (o.x < mine) + (o.y < mine) + (o.z < mine) + (o.w < mine);
+    // Slots.  The wave's j-th reads: rank among the wave's items of the same bin and that bin's first lane, by ballots (as many
+    // rounds as the 64 reads have distinct bins: reads of a locus have about the same rows); then the waves take turns in read
+    // order, and a bin's first lane moves the bin's cursor by the size of its group.  The slot takes the bin's place in p_key.
+#pragma unroll
+    for (int j = 0; j < kPlanReadsPerThread; ++j) {
+        if (j >= rpt) break;   // (the same for every thread: the barriers below stay whole)
+        const int bin = p_key[j] >= 0 ? (p_key[j] & 0xfff) : -1;
+        int rank = 0, group = 0, leader = 0;
+        unsigned long long todo = __ballot(bin >= 0);
+        while (todo) {
+            const int first = __ffsll((long long)todo) - 1;
+            const int b = __shfl(bin, first);
+            const unsigned long long same = __ballot(bin == b);
+            if (bin == b) {
+                rank = __popcll(same & ((1ull << lane) - 1));
+                group = __popcll(same);
+                leader = first;
             }
-            band_rank -= s_below[band_list - kBandClass0];
+            todo &= ~same;
         }
-    }
-    for (int k0 = 0; k0 < n; k0 += kTableMax) {
-        const int nn = min(kTableMax, n - k0);
-        const int c = band_list >= 0 ? band_list : classify(nfl, ntr, nfr, m, lo + k0, nn, force_generic, a.ref_mode);
-        const int idx = s_base[c] + (band_list >= 0 ? band_rank : atomicAdd(&s_cnt[c], 1));
-        if (idx < a.list_stride) {
-            a.cls_list[(size_t)c * a.list_stride * 2 + 2 * idx] = r;
-            a.cls_list[(size_t)c * a.list_stride * 2 + 2 * idx + 1] = band_list >= 0 ? l : k0;   // band items: the locus (k0 is 0)
-            if (band_list >= 0) {   // the band kernel fetches an item with one level of loads (and one chunk ahead)
-                int4* rec = a.band_recs + ((size_t)(band_list - kBandClass0) * a.list_stride + idx) * 3;
-                const long long so = a.seq_off[r];
-                rec[0] = make_int4(r, l, nfl, ntr);
-                rec[1] = make_int4(nfr, m, lo, n);
-                rec[2] = make_int4((int)(so & 0xffffffffll), (int)(so >> 32), a.motif_off[l], a.est_cn[r]);
+        int base = 0;
+        for (int w = 0; w < kPlanWaves; ++w) {
+            if (w == wave && bin >= 0 && lane == leader) {
+                base = s_bin[bin];
+                s_bin[bin] = base + group;
             }
-        } else {
-            atomicOr(&a.counters[kCntError], kErrList);
+            __syncthreads();
+        }
+        base = __shfl(base, leader);
+        if (bin >= 0) p_key[j] = (p_key[j] & ~0xfff) | (base + rank);
+    }
+#pragma unroll
+    for (int j = 0; j < kPlanReadsPerThread; ++j) {
+        const int band_cls = p_key[j] >= 0 ? (p_key[j] >> 18) : -1;
+        const int n = p_key[j] >= 0 ? ((p_key[j] >> 12) & 63) : -(p_key[j] + 1);
+        if (n <= 0) continue;
+        const int gid = blockIdx.x * (kPlanThreads * rpt) + j * kPlanThreads + tid;
+        const int r = items ? items[gid] : gid;
+        const int l = a.read_locus[r], lo = a.win_lo[r];
+        const int nfl = a.nfl[r], ntr = a.ntr[r], nfr = a.nfr[r], m = a.motif_off[l + 1] - a.motif_off[l];
+        const int band_list = band_cls >= 0 ? kBandClass0 + band_cls : -1;
+        for (int k0 = 0; k0 < n; k0 += kTableMax) {
+            const int nn = min(kTableMax, n - k0);
+            const int c = band_list >= 0 ? band_list : classify(nfl, ntr, nfr, m, lo + k0, nn, force_generic, a.ref_mode);
+            const int idx = s_base[c] + (band_list >= 0 ? (p_key[j] & 0xfff) - s_below[band_cls] : atomicAdd(&s_cnt[c], 1));
+            if (idx < a.list_stride) {
+                a.cls_list[(size_t)c * a.list_stride * 2 + 2 * idx] = r;
+                a.cls_list[(size_t)c * a.list_stride * 2 + 2 * idx + 1] = band_list >= 0 ? l : k0;   // band items: the locus (k0 is 0)
+                if (band_list >= 0) {   // the band kernel fetches an item with one level of loads (and one chunk ahead)
+                    int4* rec = a.band_recs + ((size_t)band_cls * a.list_stride + idx) * 3;
+                    const long long so = a.seq_off[r];
+                    rec[0] = make_int4(r, l, nfl, ntr);
+                    rec[1] = make_int4(nfr, m, lo, n);
+                    rec[2] = make_int4((int)(so & 0xffffffffll), (int)(so >> 32), a.motif_off[l], a.est_cn[r]);
+                }
+            } else {
+                atomicOr(&a.counters[kCntError], kErrList);
+            }
         }
     }
 }

@@ -171,7 +171,8 @@ STRK_HD constexpr int band_class_layout(int c) { return c & 3; }
 STRK_HD constexpr int band_class_G(int c) { return 8 << (c & 3); }
 STRK_HD constexpr int band_class_D(int c) { return c >= 4 ? 12 : 16; }
 STRK_HD constexpr int band_class_wd(int c) { return band_class_G(c) * band_class_D(c); }
-STRK_HD constexpr int band_max_db(int c) { return (c & 3) == 0 ? 448 : ((c & 3) == 1 ? 1024 : ((c & 3) == 2 ? 4096 : 12288)); }
+// (layout 0 holds windows of up to 512 bases since round 19: a HiFi read of 449-512 bases needs a band of 128 diagonals, not 16 lanes)
+STRK_HD constexpr int band_max_db(int c) { return (c & 3) == 0 ? 512 : ((c & 3) == 1 ? 1024 : ((c & 3) == 2 ? 4096 : 12288)); }
 STRK_HD constexpr int band_max_col(int c) { return (c & 3) == 0 ? 320 : ((c & 3) == 1 ? 512 : ((c & 3) == 2 ? 1024 : 1536)); }
 STRK_HD constexpr bool band_class_fly(int c) { return (c & 3) >= 2; }
 // classes that track the running maximum of the last column (alignments that end there above the fork row): all but the

@@ -13,7 +13,11 @@ Calibration (round 4, BASELINE config 2 at 10 000 loci): 20 410 scored reads and
 20 410 items and ~500 M modelled — good for ratios.
 
 The model follows the library: the dedupe (byte-identical reads of a locus), k_plan's window rule at +-6 (+-8 for motifs of
-1-2 bases), band_geometry with BandTune's inner span, k_plan's block-local (class, rows) order.
+1-2 bases), band_geometry with BandTune's inner span, k_plan's block-local (class, bin of the rows, read) order.
+
+Parameters of the block-local order: the sort scope (reads one block of k_plan orders; 0: the whole call), the row bins of its
+counting sort (rows >> shift per layout class; None: exact rows) and the largest window of layout class 0 (448: the LDS layout
+of rounds 4-18; 512 since round 19: what a band of 128 diagonals can hold).  The last table sweeps them.
 
     python tools/band_order_model.py [n_loci]        # default 1000 loci of config 2; figures scale linearly
 """
@@ -24,7 +28,7 @@ from collections import Counter
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from strkit_amd.synth import make_config
 
-MAX_DB = (448, 1024, 4096, 12288)
+MAX_DB = (512, 1024, 4096, 12288)
 MAX_COL = (320, 512, 1024, 1536)
 ROW_SLACK, NARROW_SLACK, CHUNK_COST = 96, 22, 1600
 
@@ -33,8 +37,13 @@ def band_wd(c):
     return (8 << (c & 3)) * (12 if c >= 4 else 16)
 
 
-def band_class(nfl, ntr, nfr, m, lo, n, span_w):
+BIN_SHIFT = (2, 3, 6, 7)   # strk_plan_order.h: plan_bin_shift per layout class
+SCOPE = 2048               # strk_plan_order.h: kPlanScope (calls of 32 768 reads and more; smaller ones: 512)
+
+
+def band_class(nfl, ntr, nfr, m, lo, n, span_w, max_db0=None):
     """strk_search.h: band_geometry's class (-1: not eligible); span_w = 64 is the whole table."""
+    max_db = (max_db0 or MAX_DB[0],) + MAX_DB[1:]
     ndb = nfl + ntr + nfr
     t = max((n - 1) // 2 - span_w, 0)
     c_lo, c_hi = lo + t, lo + n - 1 - t
@@ -47,7 +56,7 @@ def band_class(nfl, ntr, nfr, m, lo, n, span_w):
         slack = NARROW_SLACK if (c >= 4 and smin < NARROW_SLACK) else smin
         if span_hi - span_lo + 1 + 2 * slack > w:
             continue
-        if ndb > MAX_DB[c & 3] or (n - 1) * m + w > MAX_COL[c & 3] or rows > MAX_DB[c & 3] + ROW_SLACK:
+        if ndb > max_db[c & 3] or (n - 1) * m + w > MAX_COL[c & 3] or rows > max_db[c & 3] + ROW_SLACK:
             continue
         if (c & 3) >= 1 and w * 5 > (ndb + 1) * 4:
             return -1
@@ -75,8 +84,8 @@ def items_of(b):
     return out, dups
 
 
-ORDERS = {   # per class: the key the items of a class are listed by (None: k_plan's order inside each 256-read block)
-    "block-local (today)": None,
+ORDERS = {   # per class: the key the items of a class are listed by (None: k_plan's order inside each block of `scope` reads)
+    "block-local (today)": None,          # (scope, bins, class-0 limit: model()'s parameters)
     "call-wide by rows": lambda x: (x[1],),
     "buckets of 4 rows": lambda x: (x[1] >> 2, x[5]),
     "buckets of 8 rows": lambda x: (x[1] >> 3, x[5]),
@@ -84,19 +93,20 @@ ORDERS = {   # per class: the key the items of a class are listed by (None: k_pl
 }
 
 
-def model(items, span_w, order, test_free):
+def model(items, span_w, order, test_free, scope=SCOPE, bins=BIN_SHIFT, max_db0=None):
     recs = []   # (class, rows, fork0, nfr, m, read)
     for (r, l, nfl, ntr, nfr, m, lo, n) in items:
-        c = band_class(nfl, ntr, nfr, m, lo, n, span_w if m <= 6 else 64)
+        c = band_class(nfl, ntr, nfr, m, lo, n, span_w if m <= 6 else 64, max_db0)
         if c >= 0 and c & 3 < 2:   # k_dp_band's classes
             recs.append((c, nfl + (lo + n - 1) * m, nfl + lo * m, nfr, m, r))
     per = {}
     if ORDERS[order] is None:
         blocks = {}
         for x in recs:
-            blocks.setdefault((x[5] // 256, x[0]), []).append(x)
+            blocks.setdefault((x[5] // scope if scope else 0, x[0]), []).append(x)
         for (_, c), v in sorted(blocks.items()):
-            per.setdefault(c, []).extend(sorted(v, key=lambda x: (x[1], x[5])))
+            sh = bins[c & 3] if bins else 0
+            per.setdefault(c, []).extend(sorted(v, key=lambda x: (x[1] >> sh, x[5])))
     else:
         for x in recs:
             per.setdefault(x[0], []).append(x)
@@ -136,6 +146,16 @@ def main():
                 cl = " ".join(f"{(8 << (c & 3))}x{12 if c >= 4 else 16}:{k}" for c, k in sorted(classes.items()))
                 print(f"   {order:22s} items {cl}   wave-steps {steps:9d}   fork-block steps {fork_steps:8d}   "
                       f"instructions {instr / 1e6:7.2f} M   x {instr / base:.3f}")
+    # the block-local order by sort scope, row bins and class-0 window limit (whole table, test-free steps); 1.000 = 256 reads,
+    # exact rows, 448 bases: the tree of rounds 15-18
+    ref = model(items, 64, "block-local (today)", True, 256, None, 448)[1]
+    print("-- block-local order: sort scope x row bins x largest class-0 window (band around the whole table, test-free steps)")
+    print(f"   {'scope (reads)':14s} {'exact rows, 448':>16s} {'bins, 448':>10s} {'exact rows, 512':>16s} {'bins, 512':>10s}")
+    for scope in (256, 1024, 2048, 4096, 0):
+        row = [model(items, 64, "block-local (today)", True, scope, b, db0)[1] / ref for db0 in (448, 512) for b in (None, BIN_SHIFT)]
+        print(f"   {str(scope) if scope else 'whole call':14s} {row[0]:16.3f} {row[1]:10.3f} {row[2]:16.3f} {row[3]:10.3f}")
+    over = [x for x in items if x[2] + x[3] + x[4] > 448]
+    print(f"   items with windows over 448 bases: {len(over)} of {len(items)} ({sum(1 for x in over if x[2] + x[3] + x[4] > 512)} over 512)")
 
 
 if __name__ == "__main__":
