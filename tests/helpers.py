@@ -71,6 +71,17 @@ def oracle_count(b: LocusBatch, max_iters=50, lsr=3, step=1, tie_rule=0, flags=1
     return res
 
 
+def oracle_count_pool(b: LocusBatch, threads=16, **kw):
+    """oracle_count with the loci spread over a thread pool (the oracle is a C library that keeps no state between calls and
+    runs without the interpreter lock): for batches of a few deep loci, where one core would take several seconds."""
+    from concurrent.futures import ThreadPoolExecutor
+    oracle.lib()
+    order = sorted(range(b.n_loci), key=lambda l: int(b.read_off[l]) - int(b.read_off[l + 1]))     # deepest first
+    with ThreadPoolExecutor(max(1, min(threads, 16, b.n_loci))) as pool:
+        parts = dict(zip(order, pool.map(lambda l: oracle_count(b.locus_slice(l, l + 1), **kw), order)))
+    return {k: np.concatenate([parts[l][k] for l in range(b.n_loci)]) if b.n_loci else np.zeros(0, np.int32) for k in ("cn", "score", "n_iters", "start")}
+
+
 def py_search(start, step, lsr, max_iters, tie_last, narrow, table):
     """The read-side search as a plain Python loop over a {size: score} table (control flow of repeats.py:100-151 as
     strk_search.h states it), with the schedules of local_search_range the library offers (strk_search.h: LsrSchedule).
@@ -229,3 +240,75 @@ def hip_runtime():
         except OSError:
             continue
     pytest.fail("the HIP runtime library was not found")
+
+
+# ---- HiFi-like loci, the resident-buffer entry point and the end of a context's band probation (shared by the band tests) ----
+def hifi_seq(rng, n):
+    return "".join(ALPHA_ACGT[i] for i in rng.integers(4, size=n))
+
+
+def hifi_motif(rng, m):
+    while True:
+        s = hifi_seq(rng, m)
+        if all(s != s[:p] * (m // p) for p in range(1, m) if m % p == 0):
+            return s
+
+
+def hifi_locus(rng, motif, nfl, ntr, nfr, n_reads):
+    """Reads of exactly nfl + ntr + nfr bases: the tract is the motif repeated and cut at ntr bases, now and then with one
+    substitution (a HiFi read's error rate); the flanks differ from read to read, so every read is an item of its own."""
+    m = len(motif)
+    reads = []
+    for k in range(n_reads):
+        tr = list((motif * (ntr // m + 1))[:ntr])
+        if tr and k % 3 == 1:
+            i = int(rng.integers(len(tr)))
+            tr[i] = ALPHA_ACGT[(ALPHA_ACGT.index(tr[i]) + 1) % 4]
+        reads.append((hifi_seq(rng, nfl), "".join(tr), hifi_seq(rng, nfr)))
+    return motif, reads
+
+
+def device_count(b, ctx, flags=15, **kw):
+    """strk_count_loci_device on resident copies of the batch (device buffers of the test's own, through the HIP runtime)."""
+    import ctypes as C
+
+    from strkit_amd import _lib
+    from strkit_amd.batch import make_params
+    hip = hip_runtime()
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipFree.argtypes = [C.c_void_p]
+    assert hip.hipSetDevice(ctx.device) == 0
+    held = []
+
+    def dev(arr):
+        arr = np.ascontiguousarray(arr)
+        d = C.c_void_p()
+        assert hip.hipMalloc(C.byref(d), max(arr.nbytes, 16)) == 0
+        held.append(d)
+        if arr.nbytes:
+            assert hip.hipMemcpy(d, arr.ctypes.data, arr.nbytes, 1) == 0   # hipMemcpyHostToDevice
+        return d.value
+    try:
+        dt = dict(seqs=np.uint8, seq_off=np.int64, nfl=np.int32, ntr=np.int32, nfr=np.int32, est_cn=np.int32, read_off=np.int32,
+                  motifs=np.uint8, motif_off=np.int32)
+        sb = _lib.StrkBatch(n_reads=b.n_reads, n_loci=b.n_loci, **{k: dev(np.asarray(getattr(b, k), t)) for k, t in dt.items()})
+        host = np.zeros((4, b.n_reads), np.int32)
+        d_out = dev(host)
+        p = make_params(end_flags=flags, **kw)
+        st = _lib.StrkStats()
+        _lib.check(_lib.load().strk_count_loci_device(ctx.handle, C.byref(sb), C.byref(p), *[C.c_void_p(d_out + 4 * k * b.n_reads) for k in range(4)],
+                                                      None, C.byref(st)))
+        assert hip.hipMemcpy(host.ctypes.data, d_out, host.nbytes, 2) == 0   # hipMemcpyDeviceToHost
+    finally:
+        for d in held:
+            hip.hipFree(d)
+    return {k: host[j] for j, k in enumerate(("cn", "score", "n_iters", "start"))}, st.as_dict()
+
+
+def end_probation(ctx):
+    """A context's first calls band only their first 2 048 reads: one clean call of 90 reads ends that."""
+    from strkit_amd.batch import count_loci
+    rng = np.random.default_rng(1900)
+    _, st = count_loci(LocusBatch.from_reads([hifi_locus(rng, hifi_motif(rng, 4), 60, 80, 60, 30) for _ in range(3)]), ctx=ctx, with_stats=True)
+    assert st["n_band_reads"] == 90 and st["n_band_fallback"] < 45

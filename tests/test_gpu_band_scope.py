@@ -2,80 +2,15 @@
 LDS bytes with the backward row symbols are staged between the two passes), and one block of k_plan orders the band items of
 strk_plan_scope() reads by a counting sort.  Results must equal the CPU oracle through the host-buffer and the resident-buffer
 entry points, the planning must lose or duplicate no read at a block edge, and list order must not change from run to run."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
-from helpers import oracle_count
+from helpers import device_count as _device_count, end_probation as _end_probation, hifi_locus as _hifi_locus, hifi_motif as _motif, oracle_count
 from strkit_amd.synth import LocusBatch, make_config
 
 pytestmark = pytest.mark.gpu
 KEYS = ("cn", "score", "n_iters", "start")
-BASES = "ACGT"
 ROW_SLACK = 96     # strk_search.h: kBandRowSlack
-
-
-def _seq(rng, n):
-    return "".join(BASES[i] for i in rng.integers(4, size=n))
-
-
-def _motif(rng, m):
-    while True:
-        s = _seq(rng, m)
-        if all(s != s[:p] * (m // p) for p in range(1, m) if m % p == 0):
-            return s
-
-
-def _hifi_locus(rng, motif, nfl, ntr, nfr, n_reads):
-    """Reads of exactly nfl + ntr + nfr bases: the tract is the motif repeated and cut at ntr bases, now and then with one
-    substitution (a HiFi read's error rate); the flanks differ from read to read, so every read is an item of its own."""
-    m = len(motif)
-    reads = []
-    for k in range(n_reads):
-        tr = list((motif * (ntr // m + 1))[:ntr])
-        if tr and k % 3 == 1:
-            i = int(rng.integers(len(tr)))
-            tr[i] = BASES[(BASES.index(tr[i]) + 1) % 4]
-        reads.append((_seq(rng, nfl), "".join(tr), _seq(rng, nfr)))
-    return motif, reads
-
-
-def _device_count(b, ctx, flags=15, **kw):
-    """strk_count_loci_device on resident copies of the batch (device buffers of the test's own, through the HIP runtime)."""
-    from helpers import hip_runtime
-    from strkit_amd import _lib
-    from strkit_amd.batch import make_params
-    hip = hip_runtime()
-    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
-    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
-    hip.hipFree.argtypes = [C.c_void_p]
-    assert hip.hipSetDevice(ctx.device) == 0
-    held = []
-
-    def dev(arr):
-        arr = np.ascontiguousarray(arr)
-        d = C.c_void_p()
-        assert hip.hipMalloc(C.byref(d), max(arr.nbytes, 16)) == 0
-        held.append(d)
-        if arr.nbytes:
-            assert hip.hipMemcpy(d, arr.ctypes.data, arr.nbytes, 1) == 0   # hipMemcpyHostToDevice
-        return d.value
-    try:
-        dt = dict(seqs=np.uint8, seq_off=np.int64, nfl=np.int32, ntr=np.int32, nfr=np.int32, est_cn=np.int32, read_off=np.int32,
-                  motifs=np.uint8, motif_off=np.int32)
-        sb = _lib.StrkBatch(n_reads=b.n_reads, n_loci=b.n_loci, **{k: dev(np.asarray(getattr(b, k), t)) for k, t in dt.items()})
-        host = np.zeros((4, b.n_reads), np.int32)
-        d_out = dev(host)
-        p = make_params(end_flags=flags, **kw)
-        st = _lib.StrkStats()
-        _lib.check(_lib.load().strk_count_loci_device(ctx.handle, C.byref(sb), C.byref(p), *[C.c_void_p(d_out + 4 * k * b.n_reads) for k in range(4)],
-                                                      None, C.byref(st)))
-        assert hip.hipMemcpy(host.ctypes.data, d_out, host.nbytes, 2) == 0   # hipMemcpyDeviceToHost
-    finally:
-        for d in held:
-            hip.hipFree(d)
-    return {k: host[j] for j, k in enumerate(KEYS)}, st.as_dict()
 
 
 def _same(got, exp, b, what, loci=None):
@@ -83,14 +18,6 @@ def _same(got, exp, b, what, loci=None):
     for k in KEYS:
         bad = np.nonzero(got[k][:r1] != exp[k][:r1])[0]
         assert bad.size == 0, (what, k, int(bad.size), int(bad[0]), [int(got[x][bad[0]]) for x in KEYS], [int(exp[x][bad[0]]) for x in KEYS])
-
-
-def _end_probation(ctx):
-    """A context's first calls band only their first 2 048 reads: one clean call of 90 reads ends that."""
-    from strkit_amd.batch import count_loci
-    rng = np.random.default_rng(1900)
-    _, st = count_loci(LocusBatch.from_reads([_hifi_locus(rng, _motif(rng, 4), 60, 80, 60, 30) for _ in range(3)]), ctx=ctx, with_stats=True)
-    assert st["n_band_reads"] == 90 and st["n_band_fallback"] < 45
 
 
 # ---- windows around the old (448) and the new (512) limit of layout class 0 -------------------------------------------------
