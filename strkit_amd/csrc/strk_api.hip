@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
+#include <cassert>
 #include <chrono>
 #include <cmath>
 #include <condition_variable>
@@ -140,7 +141,7 @@ struct strk_ctx {
     int device = 0;
     int last_list_stride = 0;   // list_stride of the last call planned on this context (strk_band_list)
     // workspace
-    DevBuf read_locus, win_lo, win_n, tab_off, table, cls_list, band_recs, band_recs_w, long_list, counters, scratch, state_i32, state_f64, spec, rhash, rep, exact;
+    DevBuf read_locus, win_lo, win_n, tab_off, table, ub, cls_list, band_recs, band_recs_w, long_list, counters, scratch, state_i32, state_f64, spec, rhash, rep, exact;
     DevBuf win_lo2, win_n2, tab_off2, table2, items;
     // staging for the host-buffer entry points: the arrays of a host batch (upload_batch; strk_repeat_count's fast path keeps
     // its one read's arrays there), the four result arrays of strk_count_loci
@@ -231,7 +232,8 @@ int check_params(const strk_params* p, strk_params* out) {
 }
 
 // Common workspace sizing for a batch with n_reads / n_loci and at most n_items DP items.
-int ensure_workspace(strk_ctx* c, int n_reads, int n_loci, size_t table_ints, size_t n_items) {
+// band_tables: the call may run the band kernels, which write a bound beside every table entry (KArgs::ub: the table's size again).
+int ensure_workspace(strk_ctx* c, int n_reads, int n_loci, size_t table_ints, size_t n_items, bool band_tables = false) {
     const size_t nr = (size_t)std::max(n_reads, 1), nl = (size_t)std::max(n_loci, 1);
     int rc;
     if ((rc = c->read_locus.ensure(nr * 4))) return rc;
@@ -239,6 +241,7 @@ int ensure_workspace(strk_ctx* c, int n_reads, int n_loci, size_t table_ints, si
     if ((rc = c->win_n.ensure(nr * 4))) return rc;
     if ((rc = c->tab_off.ensure(nr * 8))) return rc;
     if ((rc = c->table.ensure(std::max<size_t>(table_ints, 1) * 4))) return rc;
+    if (band_tables && (rc = c->ub.ensure(std::max<size_t>(table_ints, 1) * 4))) return rc;
     if ((rc = c->cls_list.ensure((size_t)kNumLists * std::max<size_t>(n_items, 1) * 2 * 4))) return rc;
     if ((rc = c->band_recs.ensure((size_t)kNumBandClasses * std::max<size_t>(n_items, 1) * 3 * sizeof(int4)))) return rc;
     if ((rc = c->counters.ensure(kCountersAllBytes))) return rc;
@@ -268,6 +271,7 @@ KArgs make_args(strk_ctx* c, const strk_batch* b, int end_flags, int window, int
     a.win_n = c->win_n.as<int32_t>();
     a.tab_off = c->tab_off.as<int64_t>();
     a.table = c->table.as<int32_t>();
+    a.ub = c->ub.as<int32_t>();   // (sized by the calls that can run the band kernels: ensure_workspace)
     a.cls_list = c->cls_list.as<int32_t>();
     a.band_recs = c->band_recs.as<int4>();
     a.band_recs_w = a.band_recs;   // (k_sort_wide's copy when that kernel is launched: enqueue_scoring)
@@ -332,6 +336,11 @@ void enqueue_scoring(strk_ctx* c, const KArgs& a, int mode, const int32_t* d_ite
     auto predicted_blocks = [&](int chunks, int full) { return c->hist.predicted_blocks(hist, chunks, a.n_reads, full); };
     if (time_dp) (void)hipEventRecord(c->ev[kEvHead], st);
     const bool band = a.band_mode && mode == 0 && !force_generic;
+    // The band kernels leave their tables unsearched: the certificate search from the estimate, and the listing of the reads that
+    // fail it, are step 1 of k_replay's first pass (strk_replay.h), which needs spec[] to store to.  A band call without that pass
+    // would turn every band read into an event of the walk and break the fall-back counts: only submit_device turns the band on,
+    // and it gives both.
+    assert(!band || (pre_replay && a.spec));
     int band_blocks = 1;
     if (band && time_dp) {
         // Whole-grid mode (two large kernels per call): which way two calls in flight share the device is decided by their phase.
@@ -345,7 +354,8 @@ void enqueue_scoring(strk_ctx* c, const KArgs& a, int mode, const int32_t* d_ite
             (void)hipStreamWaitEvent(st, g_band_chain_ev, 0);
     }
     if (band) {
-        // banded first pass: certified reads are done, the others are appended to the exact lists below
+        // banded first pass: band scores and their bounds per read; the first k_replay pass below searches them and appends the
+        // reads that do not certify to the exact lists
         band_blocks = std::max(1, std::min(256 * kBandBlocksPerCU * sixteenths / 16, (a.list_stride + 3) / 4));
         hipLaunchKernelGGL(k_dp_band, dim3(band_blocks), dim3(256), 0, st, a);
     }
@@ -366,7 +376,8 @@ void enqueue_scoring(strk_ctx* c, const KArgs& a, int mode, const int32_t* d_ite
         hipLaunchKernelGGL(k_dp_band_wide, dim3(predicted_blocks(c->hist.wide_chunks, wide_full)), dim3(256), 0, st, aw);
     }
     if (time_dp) (void)hipEventRecord(c->ev[kEvWide], st);
-    // first k_replay pass (strk_replay.h): as far as the certified band tables carry each locus, before the exact kernels
+    // first k_replay pass (strk_replay.h): the certificate search of the band tables, then each locus as far as certified tables
+    // carry it, before the exact kernels
     if (band && pre_replay) hipLaunchKernelGGL(k_replay, dim3(a.n_loci), dim3(64), 0, st, a, *pre_replay);
     if (time_dp) (void)hipEventRecord(c->ev[kEvPre], st);
     if (!force_generic) {
@@ -490,7 +501,7 @@ int submit_device(strk_ctx* c, const strk_batch* b, const strk_params* params, i
     if (!out_cn || !out_score || !out_n || !out_start) return fail(STRK_E_INVALID, "output pointer is NULL");
     HIP_TRY(hipSetDevice(c->device));
     const int ts = std::min(kTableMax - 1, 2 * (p.window + 7) + 1);   // room for k_plan's per-read widening
-    if ((rc = ensure_workspace(c, b->n_reads, b->n_loci, (size_t)b->n_reads * ts, (size_t)b->n_reads))) return rc;
+    if ((rc = ensure_workspace(c, b->n_reads, b->n_loci, (size_t)b->n_reads * ts, (size_t)b->n_reads, !p.no_band))) return rc;
     KArgs a = make_args(c, b, p.end_flags, p.window, ts, b->n_reads, &p);
     ReplayArgs rp;
     rp.max_iters = p.max_iters; rp.lsr = p.local_search_range; rp.step = p.step_size;

@@ -1,4 +1,5 @@
-// strk_dp_band.h — diagonal-owned banded first pass k_dp_band / k_dp_band_wide with in-kernel certificate
+// strk_dp_band.h — diagonal-owned banded first pass k_dp_band / k_dp_band_wide: band scores and their bounds
+// (the certificate search on them runs in k_replay, a lane per read: strk_replay.h)
 // Part of strk_kernels.h: included at its end, after the shared definitions (KArgs, counters, k_hash, k_plan).
 #pragma once
 
@@ -517,51 +518,17 @@ __device__ __forceinline__ void band_wave(const KArgs& a, bool act, int4 q0, int
             const int R = nfl + (lo + k) * m;
             int sc = max(comb[k], -(1 << 28)) - g * (R + nfr + ndb);
             if (LMAX && cEnd) sc = max(sc, max(lmaxA[k], -(1 << 28)) - g * ndb);   // ends in the last column, in band
-            comb[k] = sc;
-            a.table[(long long)r * a.table_stride + k] = sc;   // (a band item is the first of its copies: its own table slot)
+            // (a band item is the first of its copies: its own slot of the table and of the bounds)
+            a.table[(long long)r * a.table_stride + k] = sc;
+            a.ub[(long long)r * a.table_stride + k] = band_ub(geo, nfl, ntr, nfr, m, lo + k, a.end_flags);
         }
     }
-    // the bounds of all candidates at once, one per lane (the search below runs on one lane and would otherwise
-    // evaluate band_ub once per window entry); b0col is free after the forward pass
-    int* const ubA = reinterpret_cast<int*>(b0col);
-    if (run)
-        for (int k = lig; k < n; k += G) ubA[k] = band_ub(geo, nfl, ntr, nfr, m, lo + k, a.end_flags);
-    wave_lds_sync();
-    // The search is replayed with the certificate from the ESTIMATE only.  (Replaying it from the starts the caller's feedback
-    // can turn the estimate into — est +- 1, 2: five lanes, one start each — was tried so that k_replay would never meet an
-    // uncertain table: half of the HiFi reads then fail, because a search window that does not hold the best size has a
-    // maximum 5 |motif| to 7 |motif| per size below it, under the 2 * len(diagonal) bound of its inexact entries.  Reads that
-    // turn out uncertain from their real start are re-scored on the device instead: k_replay's append lists, strk_replay.h.)
-    if (act && first) {
-        bool certified = false;
-        if (run) {
-            SeenMask64 seen;
-            auto ub = [&](int k) { return ubA[k]; };
-            const CertResult cr = search_replay_cert(q2.w, a.step, a.lsr, a.max_iters, a.tie_last, comb, lo, n, seen, ub, a.narrow);
-            if (!cr.uncertain) {
-                certified = true;
-                a.spec[r] = make_int4(cr.res.cn, cr.res.score, cr.res.n_explored,
-                                      (cr.res.miss ? kSpecMiss : 0) | (cr.res.empty ? kSpecEmpty : 0));
-            }
-        }
-        if (!certified) {   // hand the read to the exact kernels (they run after this one)
-            const int c = classify(nfl, ntr, nfr, m, lo, n, 0, 0);
-            const int idx = atomicAdd(&a.counters[kCntClass0 + c], 1);
-            if (idx < a.list_stride) {
-                int32_t* gl = a.cls_list + (size_t)c * a.list_stride * 2;
-                gl[2 * idx] = r;
-                gl[2 * idx + 1] = 0;
-            } else {
-                atomicOr(&a.counters[kCntError], kErrList);
-            }
-            a.exact[r] = 1;
-            atomicAdd(&a.counters[kCntBandFallback], 1);
-            if (c != kGenericClass) {
-                const unsigned long long cc = (unsigned long long)ndb * ((unsigned long long)nfl + (unsigned long long)(lo + n - 1) * m + nfr);
-                atomicAdd(a.cells, cc);
-                atomicAdd(a.cells + cell_slot_of_list(c), cc);
-            }
-        }
+    // The certificate search on (S_band, band_ub) is k_replay's (strk_replay.h): a lane per read there, where it kept one lane
+    // of a group busy here while the others waited.  spec[r] keeps k_plan's kSpecMiss: with exact[r] == 0 that reads "band
+    // table present, not searched yet".  Only an item the passes did not run for is handed on from here.
+    if (act && first && !run) {
+        band_read_to_exact(a, r, nfl, ntr, nfr, m, lo, n);   // the exact kernels run after this one
+        a.exact[r] = 1;
     }
     wave_lds_sync();
 }

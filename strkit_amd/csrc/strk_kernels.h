@@ -78,6 +78,7 @@ struct KArgs {
     int32_t* win_n;       // [n_reads]
     int64_t* tab_off;     // [n_reads]
     int32_t* table;       // score table
+    int32_t* ub;          // band_ub of every entry a band kernel wrote to `table` (same shape and stride; k_replay's certificate search)
     int32_t* cls_list;    // [kNumLists * list_stride * 2]  (read, chunk start) pairs
     int4* band_recs;      // [kNumBandClasses * list_stride * 3]  everything a band item needs, written by k_plan:
                           //   (read, locus, nfl, ntr) (nfr, m, lo, n) (seq_off lo, seq_off hi, motif_off, est_cn)
@@ -96,7 +97,9 @@ struct KArgs {
     unsigned long long* scratch_used;
     long long long_slot;        // int32 units per k_dp_long wave
     int32_t long_waves;
-    int4* spec;           // [n_reads] speculative search result for start == est_cn (or NULL)
+    int4* spec;           // [n_reads] search result for start == est_cn (or NULL): k_plan writes kSpecMiss, the exact kernels their own
+                          //    search, pass 1 of k_replay the certified search of a band table; kSpecMiss with exact[r] == 0 reads
+                          //    "band table present, not searched yet"
     unsigned long long* rhash;  // [n_reads] content hash of each read window (dedupe) or NULL
     int32_t* rep;         // [n_reads] earliest identical read of the same locus (itself if none)
     int32_t list_stride;
@@ -151,7 +154,7 @@ constexpr int kErrScratch = 2;    // generic scratch exhausted
 constexpr int kErrEmpty = 4;      // nothing scored for some read
 constexpr int kErrList = 8;       // a class list is full (more items than the call sized its lists for)
 constexpr int kErrLongSlot = 16;  // a window too long for a k_dp_long scratch slot
-constexpr int kSpecMiss = 1, kSpecEmpty = 2;
+// (kSpecMiss / kSpecEmpty, the flags of KArgs::spec: strk_search.h, with the walk that reads them)
 
 // ---------------------------------------------------------------------------------------------
 // Plan: per read -> locus id, candidate window, table slot, kernel class.
@@ -168,6 +171,26 @@ __device__ inline int classify(int nfl, int ntr, int nfr, int m, int lo, int n, 
         rows <= (1 << 20))
         return kLongClass;
     return kGenericClass;
+}
+
+// A read of the band kernels goes to the exact kernels after all (the band did not run for it, or its search does not certify
+// on the band table): entry in its exact class's list, the fall-back and cell counters.  The caller sets exact[r].
+__device__ inline void band_read_to_exact(const KArgs& a, int r, int nfl, int ntr, int nfr, int m, int lo, int n) {
+    const int c = classify(nfl, ntr, nfr, m, lo, n, 0, 0);
+    const int idx = atomicAdd(&a.counters[kCntClass0 + c], 1);
+    if (idx < a.list_stride) {
+        int32_t* gl = a.cls_list + (size_t)c * a.list_stride * 2;
+        gl[2 * idx] = r;
+        gl[2 * idx + 1] = 0;
+    } else {
+        atomicOr(&a.counters[kCntError], kErrList);
+    }
+    atomicAdd(&a.counters[kCntBandFallback], 1);
+    if (c != kGenericClass) {
+        const unsigned long long cc = (unsigned long long)(nfl + ntr + nfr) * ((unsigned long long)nfl + (unsigned long long)(lo + n - 1) * m + nfr);
+        atomicAdd(a.cells, cc);
+        atomicAdd(a.cells + cell_slot_of_list(c), cc);
+    }
 }
 
 // ---------------------------------------------------------------------------------------------

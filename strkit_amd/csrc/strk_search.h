@@ -11,7 +11,7 @@
 //     that size has not been scored yet (:136-151);
 //   * the loop stops when the stack is empty or n >= max_iters (:106);
 //   * the result is the first maximum of the {size: score} dict in insertion order (:154).
-// The same function runs on the device (one lane per locus) and on the host (window-miss path).
+// The same function runs on the device (k_replay and the exact kernels) and on the host (window-miss path).
 #pragma once
 #include <stdint.h>
 
@@ -142,8 +142,9 @@ STRK_HD SearchResult search_replay(int32_t start, int32_t step, int32_t lsr0, in
 // each half has no more diagonal moves than d has cells on that side, and reaching d from any other
 // start/end diagonal costs 5 per step while gaining at most 2.  Hence
 //     S[i] <= max(S_band[i], band_ub(i)),
-// and an entry with S_band[i] >= band_ub(i) is exact.  The search is replayed on (S_band, band_ub)
-// with search_replay_cert(); whenever a comparison could be changed by an inexact entry the read is
+// and an entry with S_band[i] >= band_ub(i) is exact.  The band kernels store both per candidate (KArgs::table, KArgs::ub) and
+// search nothing themselves; k_replay replays the search on (S_band, band_ub) with search_replay_cert(), every read of a locus
+// in a lane of its own (strk_replay.h, step 1); whenever a comparison could be changed by an inexact entry the read is
 // re-scored by the exact kernels.  BASELINE's band = 64/128/512 are widths at which HiFi reads of the
 // named configs certify; noisy (ONT-like) reads mostly do not and take the exact path.
 // ---------------------------------------------------------------------------------------------
@@ -420,6 +421,137 @@ STRK_HD int32_t feedback_start(int32_t est, double* frac) {
 // call_locus.py:1161: frac += new_offset / max(read_cn, 1)   (float64 true division)
 STRK_HD void feedback_update(double* frac, int32_t cn, int32_t start) {
     *frac += (double)(cn - start) / (double)(cn > 1 ? cn : 1);
+}
+
+// ---------------------------------------------------------------------------------------------
+// The walk over the reads of a locus in caller order (k_replay, strk_replay.h).
+//
+// The feedback fraction changes only at a read whose result differs from its start count (feedback_update adds 0 otherwise)
+// or whose start offset resets it (feedback_start).  Between two such reads — EVENTS — every read is decided by values it
+// already has: its start is its estimate, and the search from the estimate has been run and stored (kSpec* flags 0).  k_replay
+// gives every read of a batch of 64 a lane, finds the first event with one ballot, commits the QUIET reads in front of it at
+// once and takes only the event through the serial code.  replay_quiet is the predicate both sides share;
+// replay_walk_serial and replay_walk_events restate the two walks for the host (tools/replay_walk_asan.cpp checks one
+// against the other; the kernel's own ballots and lane reads are checked on the device, tests/test_gpu_replay_events.py).
+// ---------------------------------------------------------------------------------------------
+constexpr int32_t kSpecMiss = 1, kSpecEmpty = 2;   // flags of a stored search result (KArgs::spec, .w)
+
+struct WalkRead {
+    int32_t est;                     // the caller's start estimate
+    int32_t cn, score, n_explored;   // result of the search from the estimate (meaningful with flags == 0 or kSpecEmpty)
+    int32_t flags;                   // kSpecMiss: no such result (not searched, uncertain, or the search left the window); kSpecEmpty
+    int32_t pending;                 // 1: the read's table is still to be written by the exact kernels (pass 1 only)
+};
+struct WalkOut {
+    int32_t cn, score, n_explored, start;
+};
+constexpr int32_t kWalkNext = 0, kWalkRescore = 1, kWalkMiss = 2;   // what a read leaves the walk with (kStop* of strk_replay.h)
+
+STRK_HD bool same_double_bits(double x, double y) {
+    uint64_t a, b;
+    __builtin_memcpy(&a, &x, 8);
+    __builtin_memcpy(&b, &y, 8);
+    return a == b;
+}
+
+// A quiet read under the fraction `frac`: the serial code would take its stored result, write it out with start == est and leave
+// `frac` as it is.  With the feedback off only the stored result is asked for.  (A pending table is never read by the serial
+// code while the stored result is taken; the test keeps such a read on the serial path all the same.)
+STRK_HD bool replay_quiet(const WalkRead& rd, int32_t feedback, double frac) {
+    if (rd.flags != 0) return false;
+    if (!feedback) return true;
+    if (rd.pending) return false;
+    double f = frac;
+    const int32_t start = feedback_start(rd.est, &f);
+    return start == rd.est && same_double_bits(f, frac) && rd.cn == start;
+}
+
+// One read through the serial code.  search(i, start, &uncertain) scores read i from `start` on its table (the moved start, or
+// no stored result) and returns a SearchResult; `uncertain` says that a band table could not certify it.
+template <class Search>
+STRK_HD int32_t replay_walk_step(const WalkRead& rd, int32_t i, int32_t feedback, int32_t pre_exact, double* frac, WalkOut* out,
+                                 const Search& search) {
+    int32_t start = rd.est;
+    double frac_try = *frac;
+    if (feedback) start = feedback_start(rd.est, &frac_try);
+    SearchResult res = {0, 0, 0, 0, 0, 0, 0};
+    if (start == rd.est && !(rd.flags & kSpecMiss)) {
+        res.cn = rd.cn;
+        res.score = rd.score;
+        res.n_explored = rd.n_explored;
+        res.empty = (rd.flags & kSpecEmpty) ? 1 : 0;
+    } else {
+        if (pre_exact && rd.pending) return kWalkRescore;
+        int32_t uncertain = 0;
+        res = search(i, start, &uncertain);
+        if (uncertain && pre_exact) return kWalkRescore;
+        if (uncertain) res.miss = 1;
+    }
+    if (res.miss) return kWalkMiss;
+    *frac = frac_try;
+    if (res.empty) {
+        res.cn = 0;
+        res.score = 0;
+    }
+    out->cn = res.cn;
+    out->score = res.score;
+    out->n_explored = res.n_explored;
+    out->start = start;
+    if (feedback && !res.empty && res.cn != start) feedback_update(frac, res.cn, start);
+    return kWalkNext;
+}
+
+// The walk read by read.  Returns how the locus stopped; *next is the first read not finished.
+template <class Search>
+STRK_HD int32_t replay_walk_serial(const WalkRead* rd, int32_t n, int32_t feedback, int32_t pre_exact, double* frac, WalkOut* out,
+                                   int32_t* next, const Search& search) {
+    int32_t i = 0, how = kWalkNext;
+    for (; i < n; ++i) {
+        how = replay_walk_step(rd[i], i, feedback, pre_exact, frac, out + i, search);
+        if (how != kWalkNext) break;
+    }
+    *next = i;
+    return how;
+}
+
+// The walk as k_replay runs it: batches of 64 reads, lane j of a batch owns read base + j.  Every lane tests replay_quiet under the
+// current fraction; the ballot (here: a loop over the lanes) finds the first lane at or behind `pos` that is not quiet; the quiet
+// lanes in front of it commit; that one read goes through replay_walk_step; the walk goes on behind it with the new fraction.
+// on_event(lane, base) is called for every read that takes the serial code.
+template <class Search, class OnEvent>
+STRK_HD int32_t replay_walk_events(const WalkRead* rd, int32_t n, int32_t feedback, int32_t pre_exact, double* frac, WalkOut* out,
+                                   int32_t* next, const Search& search, const OnEvent& on_event) {
+    int32_t done_all = 0, how = kWalkNext;
+    for (int32_t base = 0; base < n && how == kWalkNext; base += 64) {
+        const int32_t cnt = n - base < 64 ? n - base : 64;
+        int32_t pos = 0;
+        while (pos < cnt) {
+            uint64_t loud = 0;   // ballot of the lanes that are not quiet (lanes without a read count as such)
+            for (int32_t j = 0; j < 64; ++j)
+                if (j >= cnt || !replay_quiet(rd[base + j], feedback, *frac)) loud |= (uint64_t)1 << j;
+            loud &= ~(uint64_t)0 << pos;
+            int32_t ev = 64;
+            for (int32_t j = 0; j < 64 && ev == 64; ++j)
+                if ((loud >> j) & 1) ev = j;
+            if (ev > cnt) ev = cnt;
+            for (int32_t j = pos; j < ev; ++j) {
+                const WalkRead& q = rd[base + j];
+                out[base + j].cn = q.cn;
+                out[base + j].score = q.score;
+                out[base + j].n_explored = q.n_explored;
+                out[base + j].start = q.est;
+            }
+            pos = ev;
+            if (ev >= cnt) break;
+            on_event(ev, base);
+            how = replay_walk_step(rd[base + ev], base + ev, feedback, pre_exact, frac, out + base + ev, search);
+            if (how != kWalkNext) break;
+            pos = ev + 1;
+        }
+        done_all = base + pos;
+    }
+    *next = done_all;
+    return how;
 }
 
 }  // namespace strk
