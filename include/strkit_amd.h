@@ -309,6 +309,23 @@ int strk_call_alleles(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off /*[
                       int32_t* out_ci99 /*[4n]*/, double* out_means, double* out_weights, double* out_stdevs /*[2n]*/,
                       int32_t* out_peak_n_reads /*[2n]*/, int32_t* out_read_peak /*[n_reads], -1 = none*/, strk_stats* stats);
 
+/* ---- allele calling with one to six alleles per locus -------------------------------------------------------------------
+ * strk_call_alleles for n_alleles[l] in 1 .. STRK_MAX_ALLELES (a ploidy configuration may give any count, strkit/ploidy.py):
+ * a GMM of n_alleles components per resample whose useless components are removed round by round (allele.py:78-123) and
+ * filled up again by a weighted draw (:276-288).  The whole rule: DESIGN.md §15.  For n_alleles <= 2 the results are those
+ * of strk_call_alleles, byte for byte.  A locus with more than one distinct copy number and fewer reads than alleles is
+ * STRK_ALLELE_TOO_FEW.  Reads get a peak only when at most two peaks are called (out_modal_n <= 2, on the first out_modal_n
+ * rows); otherwise out_read_peak is -1, out_peak_n_reads 0 and the status STRK_ALLELE_CALLED.
+ * Inputs and checks as strk_call_alleles.  The per-locus outputs have a fixed row stride of STRK_MAX_ALLELES:
+ * out_call[6l+a], out_ci95[12l+2a .. +1] and out_ci99, out_means, out_weights, out_stdevs [6l+a]; out_peak_n_reads[2l+peak];
+ * unused integer slots are -1, unused doubles NaN. */
+#define STRK_MAX_ALLELES 6
+int strk_call_alleles_n(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off /*[n_loci+1]*/, const int32_t* cn, const double* w,
+                        const int32_t* n_alleles, const uint64_t* seed, const strk_allele_params* p,
+                        int32_t* out_status, int32_t* out_modal_n, int32_t* out_call /*[6n]*/, int32_t* out_ci95 /*[12n]*/,
+                        int32_t* out_ci99 /*[12n]*/, double* out_means, double* out_weights, double* out_stdevs /*[6n]*/,
+                        int32_t* out_peak_n_reads /*[2n]*/, int32_t* out_read_peak /*[n_reads], -1 = none*/, strk_stats* stats);
+
 /* ---- phased allele calls: reads grouped by haplotags or by SNVs -------------------------------------------------------
  * Stands where the reference separates the reads of a locus before it calls alleles (call_locus.py:1381-1495):
  * call_alleles_with_haplotags (:222-288) for reads that carry HP / PS tags, else call_alleles_with_incorporated_snvs

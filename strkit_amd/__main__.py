@@ -38,6 +38,11 @@ def build_parser() -> argparse.ArgumentParser:
     c.add_argument("--max-mdn-poa-length", type=int, default=5000,
                    help="--consensus-method poa: an allele whose median read length is above this keeps its best representative")
     c.add_argument("--n-alleles", type=int, choices=(1, 2), default=2, help="alleles per locus, all contigs")
+    c.add_argument("--ploidy", "--sex-chr", "-x", dest="ploidy", default=None, metavar="NAME|PATH",
+                   help="ploidy configuration of the sample: haploid, diploid_autosomes, diploid_xx/XX, diploid_xy/XY, or a JSON file "
+                        "(default, overrides per contig pattern, ignored contig patterns; up to 6 alleles).  Every contig is called "
+                        "with its own number of alleles and loci on contigs without one are left out; replaces --n-alleles "
+                        "(needs --call-alleles)")
     c.add_argument("--count-kmers", "-k", nargs="?", type=str, default="none", const="peak", choices=("none", "peak", "read", "both"),
                    help="count the motif-sized k-mers of every read's repeat tract (GPU): per read, summed per allele (peak; the "
                         "default when the flag stands alone; needs --call-alleles), or both")
@@ -71,6 +76,16 @@ def main(argv=None) -> int:
         ap.error(f"--count-kmers {a.count_kmers} needs --call-alleles")
     if (a.use_hp or a.incorporate_snvs) and not a.call_alleles:
         ap.error("--use-hp / --incorporate-snvs need --call-alleles")
+    if a.ploidy is not None:
+        if not a.call_alleles:
+            ap.error("--ploidy needs --call-alleles")
+        if a.n_alleles != 2:
+            ap.error("--ploidy and --n-alleles are two ways to say the same thing: give one of them")
+        from .ploidy import load_ploidy_config
+        try:
+            load_ploidy_config(a.ploidy)
+        except ValueError as e:
+            ap.error(str(e))
     if not 0 <= a.methyl_threshold <= 255:
         ap.error("--methyl-threshold must be in 0 .. 255")
     import os
@@ -93,6 +108,7 @@ def main(argv=None) -> int:
                       **(dict(use_hp=a.use_hp, snv_vcf=a.incorporate_snvs, snv_min_base_qual=a.snv_min_base_qual,
                               significant_clip_threshold=a.significant_clip_threshold) if a.use_hp or a.incorporate_snvs else {}),
                       **(dict(use_methyl=True, methyl_threshold=a.methyl_threshold) if a.use_methyl else {}),
+                      **(dict(ploidy=a.ploidy) if a.ploidy is not None else {}),
                       **(dict(call_alleles=True, consensus=a.consensus or bool(a.vcf), seed=a.seed, n_alleles=a.n_alleles)
                          if a.call_alleles else {}))
     if world > 1:

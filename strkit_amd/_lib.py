@@ -73,7 +73,7 @@ EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk
            "strk_extract_reads", "strk_bgzf_inflate", "strk_bgzf_inflate_range", "strk_bam_names", "strk_bam_scan_piece",
            "strk_dbam_open", "strk_dbam_close", "strk_dbam_release_cache", "strk_dbam_inflate", "strk_dbam_inflate_file", "strk_dbam_inflate_file_range", "strk_dbam_file_ms", "strk_dbam_download", "strk_dbam_data", "strk_bgzf_inflate_sw",
            "strk_dbam_download_seqs", "strk_dbam_kernel_ms", "strk_dbam_voffsets", "strk_dbam_scan", "strk_dbam_extract", "strk_dbam_names", "strk_count_loci_dseqs", "strk_read_coords_both", "strk_call_alleles",
-           "strk_call_alleles_phased",
+           "strk_call_alleles_phased", "strk_call_alleles_n",
            "strk_best_representatives", "strk_best_representatives_dseqs",
            "strk_count_kmers", "strk_count_kmers_dseqs", "strk_count_kmers_ws",
            "strk_consensus", "strk_consensus_dseqs", "strk_consensus_ws",
@@ -208,6 +208,8 @@ def load(build: bool = True):
         L.strk_call_alleles.restype = C.c_int
         L.strk_call_alleles.argtypes = ([C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.POINTER(StrkAlleleParams)]
                                         + [C.c_void_p] * 10 + [C.POINTER(StrkStats)])
+        L.strk_call_alleles_n.restype = C.c_int
+        L.strk_call_alleles_n.argtypes = L.strk_call_alleles.argtypes
         L.strk_call_alleles_phased.restype = C.c_int
         L.strk_call_alleles_phased.argtypes = ([C.c_void_p, C.c_int32] + [C.c_void_p] * 5
                                                + [C.POINTER(StrkAlleleParams), C.POINTER(StrkPhaseParams)] + [C.c_void_p] * 5

@@ -16,6 +16,7 @@ from ._lib import ptr
 
 CALLED, TOO_FEW, EMPTY_PEAK = 0, 1, 2
 ASSIGN_SINGLE, ASSIGN_DIST = "single", "dist"
+MAX_ALLELES = 6   # STRK_MAX_ALLELES: the row stride of call_alleles_n_batch's per-locus outputs
 
 
 @dataclass(frozen=True)
@@ -83,12 +84,12 @@ def batch_inputs(read_off, cns, weights, n_alleles, seeds):
     return read_off, cns, weights, n_alleles, seeds, n_loci
 
 
-def batch_outputs(n_loci: int, n_reads: int) -> dict:
-    """The arrays a batched allele call fills: ALLELE_KEYS per locus and read_peak per read."""
+def batch_outputs(n_loci: int, n_reads: int, width: int = 2) -> dict:
+    """The arrays a batched allele call fills: ALLELE_KEYS per locus (`width` allele slots) and read_peak per read."""
     return dict(status=np.empty(n_loci, np.int32), modal_n=np.empty(n_loci, np.int32),
-                call=np.empty((n_loci, 2), np.int32), ci95=np.empty((n_loci, 2, 2), np.int32),
-                ci99=np.empty((n_loci, 2, 2), np.int32), means=np.empty((n_loci, 2)),
-                weights=np.empty((n_loci, 2)), stdevs=np.empty((n_loci, 2)),
+                call=np.empty((n_loci, width), np.int32), ci95=np.empty((n_loci, width, 2), np.int32),
+                ci99=np.empty((n_loci, width, 2), np.int32), means=np.empty((n_loci, width)),
+                weights=np.empty((n_loci, width)), stdevs=np.empty((n_loci, width)),
                 peak_n_reads=np.empty((n_loci, 2), np.int32), read_peak=np.empty(n_reads, np.int32))
 
 
@@ -104,6 +105,26 @@ def call_alleles_batch(read_off, cns, weights, n_alleles, seeds, params: AlleleP
     cp = params._c()
     st = _lib.StrkStats()
     _lib.check(_lib.load().strk_call_alleles(
+        ctx.handle, n_loci, *map(ptr, (read_off, cns, weights, n_alleles, seeds)), C.byref(cp),
+        *[ptr(out[k]) for k in (*ALLELE_KEYS, "read_peak")], C.byref(st)))
+    if with_stats:
+        return out, st.as_dict()
+    return out
+
+
+def call_alleles_n_batch(read_off, cns, weights, n_alleles, seeds, params: AlleleParams | None = None, ctx=None,
+                         with_stats: bool = False):
+    """call_alleles_batch for one to MAX_ALLELES alleles per locus (strk_call_alleles_n, kernel k_alleles_n).
+    Same arguments; call, means, weights, stdevs are [L, 6] and ci95, ci99 [L, 6, 2], unused slots -1 / NaN;
+    peak_n_reads stays [L, 2].  A locus whose modal number of peaks is above 2 has no read peaks (read_peak -1, counts 0).
+    For n_alleles <= 2 the first two slots are call_alleles_batch's, byte for byte."""
+    params = params or AlleleParams()
+    ctx = ctx or _lib.default_context()
+    read_off, cns, weights, n_alleles, seeds, n_loci = batch_inputs(read_off, cns, weights, n_alleles, seeds)
+    out = batch_outputs(n_loci, cns.shape[0], MAX_ALLELES)
+    cp = params._c()
+    st = _lib.StrkStats()
+    _lib.check(_lib.load().strk_call_alleles_n(
         ctx.handle, n_loci, *map(ptr, (read_off, cns, weights, n_alleles, seeds)), C.byref(cp),
         *[ptr(out[k]) for k in (*ALLELE_KEYS, "read_peak")], C.byref(st)))
     if with_stats:
@@ -170,13 +191,15 @@ class CallData:
 
 
 def call_data_from_batch(out: dict, l: int, n_alleles: int) -> CallData | None:
-    """Locus l of a call_alleles_batch result as CallData (None when it had too few reads)."""
+    """Locus l of a call_alleles_batch or call_alleles_n_batch result as CallData (None when it had too few reads).  With
+    more than two peaks called no read has a peak, and n_reads is empty."""
     if int(out["status"][l]) == TOO_FEW:
         return None
     a = int(n_alleles)
+    k = int(out["modal_n"][l])
     return CallData(out["call"][l, :a], out["ci95"][l, :a], out["ci99"][l, :a], out["means"][l, :a],
-                    out["weights"][l, :a], out["stdevs"][l, :a], int(out["modal_n"][l]),
-                    n_reads=out["peak_n_reads"][l, :int(out["modal_n"][l])], status=int(out["status"][l]))
+                    out["weights"][l, :a], out["stdevs"][l, :a], k,
+                    n_reads=out["peak_n_reads"][l, :k if k <= 2 else 0], status=int(out["status"][l]))
 
 
 def _param(params, name, default):
@@ -212,8 +235,8 @@ def call_alleles(repeats_fwd, repeats_rev, read_weights_fwd, read_weights_rev, p
                         np.asarray(read_weights_rev, dtype=np.float64).ravel()))
     if seed is None:
         seed = int(np.random.default_rng().integers(0, 1 << 63))
-    out = call_alleles_batch(np.array([0, cns.shape[0]], np.int32), cns, w, [int(n_alleles)],
-                             [int(seed) & ((1 << 64) - 1)], p, ctx)
+    batch = call_alleles_n_batch if int(n_alleles) > 2 else call_alleles_batch
+    out = batch(np.array([0, cns.shape[0]], np.int32), cns, w, [int(n_alleles)], [int(seed) & ((1 << 64) - 1)], p, ctx)
     cd = call_data_from_batch(out, 0, n_alleles)
     if cd is not None:
         cd.read_peaks = out["read_peak"].copy()

@@ -1,0 +1,113 @@
+// Host side of strk_call_alleles_n (DESIGN.md §15): the input check (strk_alleles_n_check.h), then the pieces and launches of
+// strk_call_alleles with k_alleles_n, its workspace and its wider rows.  Shares the piece constants, allele_rule_args,
+// allele_threads and piece_offsets of strk_host_alleles.inc.
+// Part of strk_api.hip: included inside its anonymous namespace, after strk_host_alleles.inc; not a stand-alone header.
+
+// The caller's arrays: status, modal_n [L]; call, means, weights, stdevs [L][6]; ci95, ci99 [L][6][2]; peak_n_reads [L][2];
+// read_peak per read.
+struct AlleleNOut {
+    int32_t *status, *modal_n, *call, *ci95, *ci99;
+    double *means, *weights, *stdevs;
+    int32_t *peak_n_reads, *read_peak;
+    bool complete() const {
+        return status && modal_n && call && ci95 && ci99 && means && weights && stdevs && peak_n_reads && read_peak;
+    }
+};
+
+// The per-locus rows of a piece as k_alleles_n wrote them into the caller's arrays at loci l0 .. l0 + nl.
+void scatter_alleles_n(const AlleleNOut& out, int32_t l0, int32_t nl, const int32_t* oi, const double* od) {
+    constexpr int M = kMaxAlleles;
+    for (int32_t l = 0; l < nl; ++l) {
+        const int32_t* s = oi + (size_t)l * kAlleleNOutI;
+        const double* t = od + (size_t)l * kAlleleNOutD;
+        const size_t g = (size_t)(l0 + l);
+        out.status[g] = s[0];
+        out.modal_n[g] = s[1];
+        for (int e = 0; e < M; ++e) {
+            out.call[M * g + e] = s[kAlleleNCall + e];
+            out.means[M * g + e] = t[e];
+            out.weights[M * g + e] = t[M + e];
+            out.stdevs[M * g + e] = t[2 * M + e];
+        }
+        for (int e = 0; e < 2 * M; ++e) {
+            out.ci95[2 * M * g + e] = s[kAlleleNCi95 + e];
+            out.ci99[2 * M * g + e] = s[kAlleleNCi99 + e];
+        }
+        for (int e = 0; e < 2; ++e) out.peak_n_reads[2 * g + e] = s[kAlleleNPeak + e];
+    }
+}
+
+int call_alleles_n_impl(strk_ctx* c, const char* fn, const strk_alleles_check::Input& in, const AlleleNOut& out, strk_stats* stats) {
+    if (stats) memset(stats, 0, sizeof *stats);
+    {
+        strk_groups::Message m;
+        if (const int rc = strk_alleles_n_check::check(in, {kAlleleMaxReads, kAlleleMaxBootstrap, kAlleleMaxInit}, kMaxAlleles, &m))
+            return fail(rc, "%s: %s", fn, m.text);
+    }
+    const int32_t n_loci = in.n_loci;
+    if (n_loci == 0) return 0;
+    if (!out.complete()) return fail(STRK_E_INVALID, "%s: NULL argument", fn);
+    const strk_allele_params* p = in.p;
+    const int32_t* read_off = in.read_off;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t st;
+    if (const int rc = side_stream(c, &st)) return rc;
+    const int B = p->num_bootstrap;
+    std::vector<int64_t> ws_off;
+    std::vector<int32_t> off_rel, oi;
+    std::vector<double> od;
+    auto locus_ws = [&](size_t l) {
+        const int n = read_off[l + 1] - read_off[l];
+        return (int64_t)(n >= p->min_reads ? allele_n_ws_bytes(n, B, in.n_alleles[l]) : 0);
+    };
+    for (int32_t l0 = 0, l1; l0 < n_loci; l0 = l1) {
+        // one piece: loci in caller order while their workspace fits the budget
+        int64_t wsum = 0;
+        l1 = (int32_t)strk_groups::cut_piece((size_t)l0, (size_t)n_loci, locus_ws, (int64_t)kAlleleWsBudget, kAllelePieceLoci,
+                                             ws_off, &wsum);
+        const int32_t nl = l1 - l0, r0 = read_off[l0], nr = read_off[l1] - r0;
+        piece_offsets(read_off, l0, nl, off_rel);
+        const size_t snl = (size_t)nl, snr = std::max<size_t>(nr, 1);
+        Carve ci, co;
+        const size_t i_off = ci.take((snl + 1) * 4), i_cn = ci.take(snr * 4), i_w = ci.take(snr * 8), i_nal = ci.take(snl * 4),
+                     i_seed = ci.take(snl * 8), i_wsoff = ci.take(snl * 8);
+        const size_t o_i = co.take(snl * kAlleleNOutI * 4), o_d = co.take(snl * kAlleleNOutD * 8), o_rp = co.take(snr * 4);
+        int rc;
+        if ((rc = c->al_in.ensure(ci.bytes))) return rc;
+        if ((rc = c->al_ws.ensure(std::max<size_t>((size_t)wsum, 256)))) return rc;
+        if ((rc = c->al_out.ensure(co.bytes))) return rc;
+        AlleleArgs a = allele_rule_args(p);
+        a.read_off = c->al_in.at<int32_t>(i_off);
+        a.cn = c->al_in.at<int32_t>(i_cn);
+        a.w = c->al_in.at<double>(i_w);
+        a.n_alleles = c->al_in.at<int32_t>(i_nal);
+        a.seed = c->al_in.at<uint64_t>(i_seed);
+        a.ws_off = c->al_in.at<int64_t>(i_wsoff);
+        a.ws = c->al_ws.as<char>();
+        a.out_i = c->al_out.at<int32_t>(o_i);
+        a.out_d = c->al_out.at<double>(o_d);
+        a.read_peak = c->al_out.at<int32_t>(o_rp);
+        a.n_loci = nl;
+        a.min_reads = p->min_reads;
+        a.min_allele_reads = p->min_allele_reads;
+        char* di = c->al_in.as<char>();
+        HIP_TRY(hipMemcpyAsync(di + i_off, off_rel.data(), (snl + 1) * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(di + i_cn, in.cn + r0, (size_t)nr * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(di + i_w, in.w + r0, (size_t)nr * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(di + i_nal, in.n_alleles + l0, snl * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(di + i_seed, in.seed + l0, snl * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(di + i_wsoff, ws_off.data(), snl * 8, hipMemcpyHostToDevice, st));
+        oi.resize(snl * kAlleleNOutI);
+        od.resize(snl * kAlleleNOutD);
+        if ((rc = timed_launch(c, st, stats, fn, "allele kernel", 1, [&] {
+                hipLaunchKernelGGL(k_alleles_n, dim3(nl), dim3(allele_threads(B)), 0, st, a);
+            }, [&] {
+                HIP_TRY(hipMemcpyAsync(oi.data(), a.out_i, oi.size() * 4, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(od.data(), a.out_d, od.size() * 8, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipMemcpyAsync(out.read_peak + r0, a.read_peak, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
+                return 0;
+            }))) return rc;
+        scatter_alleles_n(out, l0, nl, oi.data(), od.data());
+    }
+    return 0;
+}

@@ -21,14 +21,25 @@ from .fasta import Fasta
 from .gather import _distributed, call_blocks_sharded, deal_locus_blocks
 from .loci import Locus, load_loci, resolve_contig
 from .native import DeviceBam, IndexedBam, NativeBam
-from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, MethylCallOptions, PhasedCallOptions, PoaCallOptions, phased, report_parameters,
-                      with_keywords)
+from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, MethylCallOptions, PhasedCallOptions, PloidyCallOptions, PoaCallOptions,
+                      allele_counts, phased, report_parameters, with_keywords)
 from .phase_block import PhaseRun
 from .reader import open_path
 from .refside import get_loci_with_ref_data, get_locus_with_ref_data, ref_side_of_blocks
 
 # (what moved to the other modules is still offered here under the names it had)
-__all__ = ["CallOptions", "PoaCallOptions", "PhasedCallOptions", "MethylCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
+__all__ = ["CallOptions", "PoaCallOptions", "PhasedCallOptions", "MethylCallOptions", "PloidyCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
+
+
+def ploidy_blocks(blocks, opts):
+    """The blocks of a run without the loci that its ploidy configuration leaves out (a contig that is ignored, or has 0
+    alleles: strkit/call/loci.py:224-230), and how many those are.  The loci that stay keep their t_idx, hence their seeds.
+    Without a configuration: the blocks as they are."""
+    if getattr(opts, "ploidy", None) is None:
+        return blocks, 0
+    config = allele_counts(opts)
+    kept = [[locus for locus in block if config.called(locus.contig)] for block in blocks]
+    return [b for b in kept if b], sum(len(b) for b in blocks) - sum(len(b) for b in kept)
 
 
 def call_locus(locus: Locus, bam: BamFile, ref: Fasta, *, ctx: _lib.Context | None = None, opts: CallOptions | None = None,
@@ -73,6 +84,8 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, *, sample_
         # a locus is called when its contig exists, under either spelling, in both files
         both = {c for c in (opener or bam).references if resolve_contig(ref.references, c) is not None}
         blocks = load_loci(loci_file, opts.flank_size, contigs=both, processes=processes)
+        n_loaded = sum(len(b) for b in blocks)
+        blocks, n_ploidy_ignored = ploidy_blocks(blocks, opts)
         tm_pre: dict = {}
         ref_cache = None
         if opener is not None and not _distributed():
@@ -86,7 +99,6 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, *, sample_
         bam, t_open, t_wait = opener.result()
     with open(loci_file) as fh:                  # the catalog's size (the lines parse_loci_bed yields), without parsing them again
         n_catalog = sum(1 for raw in fh if raw.strip() and not raw.lstrip().startswith("#"))
-    n_loaded = sum(len(b) for b in blocks)
     if n_loaded < n_catalog:
         print(f"strkit_amd: {n_catalog - n_loaded} of {n_catalog} catalog loci lie on contigs that the alignment file or "
               f"the reference does not have; they are not called", file=sys.stderr)
@@ -121,7 +133,8 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, *, sample_
             "caller": {"name": "strkit_amd", "version": _lib.load().strk_version().decode()},
             "parameters": report_parameters(opts, processes),
             "contigs": sorted({r["contig"] for r in results}),
-            "catalog": {"num_loci": len(results), "num_loci_unknown_contig": n_catalog - n_loaded},
+            "catalog": {"num_loci": len(results), "num_loci_unknown_contig": n_catalog - n_loaded,
+                        **({"num_loci_ploidy_ignored": n_ploidy_ignored} if getattr(opts, "ploidy", None) is not None else {})},
             "results": results,
             "errors": errors,
             "avg_read_depth": n_depth / max(1, sum(1 for r in results if "reads" in r)),
@@ -198,6 +211,7 @@ def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = Non
     re-run locus by locus so that only the locus that fails is lost; `stage times["errors"]` lists them."""
     opts = opts or CallOptions()
     opts.validate()
+    blocks, _ = ploidy_blocks(blocks, opts)
     phase_run = PhaseRun(opts) if phased(opts) else None     # the candidate SNVs and the renumbering of the phase sets: one per run
     ctx = ctx or _lib.default_context()
     run_block = _call_block_native if isinstance(bam, (NativeBam, IndexedBam, DeviceBam)) else _call_block_python

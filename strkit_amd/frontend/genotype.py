@@ -9,15 +9,19 @@ import time
 
 import numpy as np
 
-from ..alleles import CALLED, TOO_FEW, AlleleParams, call_alleles_batch, call_data_from_batch, locus_seeds
+from ..alleles import CALLED, MAX_ALLELES, TOO_FEW, AlleleParams, call_alleles_batch, call_alleles_n_batch, call_data_from_batch, locus_seeds
 from ..consensus import METHOD_NAMES, best_representatives_packed, consensus_packed
 from ..kmers import count_kmers_packed, dicts_of
+from .options import allele_counts
 
 __all__ = ["n_alleles_of", "call_block_alleles", "call_block_alleles_phased", "peak_groups", "block_consensus", "genotype_row", "block_kmers", "kmers_row"]
 
 
 def n_alleles_of(n_alleles, contig: str) -> int:
-    """`n_alleles`: one number for every contig or a dict per contig (2 where a contig is not named)."""
+    """`n_alleles`: one number for every contig, a dict per contig (2 where a contig is not named), or a ploidy configuration
+    (options.allele_counts; 0 for a contig that it leaves out)."""
+    if hasattr(n_alleles, "n_of"):
+        return int(n_alleles.n_of(contig) or 0)
     if isinstance(n_alleles, dict):
         return int(n_alleles.get(contig, n_alleles.get(contig[3:] if contig.startswith("chr") else "chr" + contig, 2)))
     return int(n_alleles)
@@ -38,10 +42,12 @@ def call_block_alleles(loci, n_kept: np.ndarray, cns: np.ndarray, ws: np.ndarray
     sel = ~bad_locus[owner]
     sums = np.bincount(owner[sel], weights=w[sel], minlength=n_loci)
     n_sel = np.where(bad_locus, 0, n_kept)
-    nal = np.array([n_alleles_of(opts.n_alleles, l.contig) for l in loci], np.int32)
+    counts = allele_counts(opts)
+    nal = np.array([n_alleles_of(counts, l.contig) for l in loci], np.int32)
     seeds = locus_seeds(opts.seed, np.array([l.t_idx for l in loci], np.int64))
-    out, st = call_alleles_batch(np.concatenate(([0], np.cumsum(n_sel))).astype(np.int32), np.asarray(cns, np.int32)[sel],
-                                 w[sel] / sums[owner[sel]], nal, seeds, opts.allele_params or AlleleParams(), ctx, with_stats=True)
+    batch = call_alleles_n_batch if n_loci and int(nal.max()) > 2 else call_alleles_batch     # (wider rows)
+    out, st = batch(np.concatenate(([0], np.cumsum(n_sel))).astype(np.int32), np.asarray(cns, np.int32)[sel],
+                    w[sel] / sums[owner[sel]], nal, seeds, opts.allele_params or AlleleParams(), ctx, with_stats=True)
     rp = np.full(owner.shape[0], -1, np.int32)
     rp[sel] = out["read_peak"]
     out["read_peak"] = rp
@@ -69,20 +75,42 @@ def call_block_alleles_phased(loci, n_kept: np.ndarray, cns: np.ndarray, ws: np.
     sel = ~bad_locus[owner]
     sums = np.bincount(owner[sel], weights=w[sel], minlength=n_loci)
     n_sel = np.where(bad_locus, 0, n_kept)
-    nal = np.array([n_alleles_of(opts.n_alleles, l.contig) for l in loci], np.int32)
+    counts = allele_counts(opts)
+    nal = np.array([n_alleles_of(counts, l.contig) for l in loci], np.int32)
     seeds = locus_seeds(opts.seed, np.array([l.t_idx for l in loci], np.int64))
+    # a locus of more than two alleles is never phased: it sits out the phased call (as a locus without reads) and takes the
+    # plain call below
+    wide = np.flatnonzero((nal > 2) & ~bad_locus)
+    if wide.size:
+        bad_locus = bad_locus | (nal > 2)
+        sel = ~bad_locus[owner]
+        n_sel = np.where(bad_locus, 0, n_kept)
     used = phase.without(bad_locus, n_kept)
     pp = opts.phase_params or PhaseParams()
     if pp.snv_quality_threshold != opts.snv_min_base_qual:
         import dataclasses
         pp = dataclasses.replace(pp, snv_quality_threshold=int(opts.snv_min_base_qual))
     out, st = call_alleles_phased_batch(np.concatenate(([0], np.cumsum(n_sel))).astype(np.int32), np.asarray(cns, np.int32)[sel],
-                                        w[sel] / sums[owner[sel]], nal, seeds, hp=used.hp, ps=used.ps, snv_off=used.snv_off,
+                                        w[sel] / sums[owner[sel]], np.minimum(nal, 2), seeds, hp=used.hp, ps=used.ps, snv_off=used.snv_off,
                                         snv_base=used.snv_base, snv_qual=used.snv_qual, params=opts.allele_params or AlleleParams(),
                                         phase_params=pp, fallback=True, ctx=ctx, with_stats=True)
     rp = np.full(owner.shape[0], -1, np.int32)
     rp[sel] = out["read_peak"]
     out["read_peak"] = rp
+    if wide.size:
+        reads = np.flatnonzero(np.isin(owner, wide))
+        sub, sub_st = call_alleles_n_batch(np.concatenate(([0], np.cumsum(n_kept[wide]))).astype(np.int32), np.asarray(cns, np.int32)[reads],
+                                           w[reads] / sums[owner[reads]], nal[wide], seeds[wide], opts.allele_params or AlleleParams(), ctx,
+                                           with_stats=True)
+        for k in ("call", "ci95", "ci99", "means", "weights", "stdevs"):      # the block's rows at the wider stride
+            row = np.full((n_loci, MAX_ALLELES) + out[k].shape[2:], np.nan if out[k].dtype.kind == "f" else -1, out[k].dtype)
+            row[:, :2] = out[k]
+            row[wide] = sub[k]
+            out[k] = row
+        for k in ("status", "modal_n", "peak_n_reads"):
+            out[k][wide] = sub[k]
+        rp[reads] = sub["read_peak"]
+        st["kernel_ms"] += sub_st["kernel_ms"]
     out["n_alleles"] = nal
     out["read_off"] = np.concatenate(([0], np.cumsum(n_kept))).astype(np.int64)
     out["phase"] = phase
@@ -103,7 +131,7 @@ def peak_groups(al: dict, tract_len: np.ndarray, opts):
     n_loci = al["status"].shape[0]
     owner = np.repeat(np.arange(n_loci), np.diff(al["read_off"]))
     called = al["status"] == CALLED
-    modal = np.where(called, al["modal_n"], 0).astype(np.int64)
+    modal = np.where(called & (al["modal_n"] <= 2), al["modal_n"], 0).astype(np.int64)   # (more peaks: no read has one)
     g_first = np.concatenate(([0], np.cumsum(modal)))            # first group of every locus
     n_groups = int(g_first[-1])
     group_locus = np.repeat(np.arange(n_loci), modal)
@@ -237,9 +265,10 @@ def genotype_row(row: dict, al: dict, li: int, recs: list[dict], cons: dict | No
     if status == TOO_FEW:
         return
     a = int(al["read_off"][li])
-    for k, p in enumerate(al["read_peak"][a:a + len(recs)].tolist()):
-        recs[k]["p"] = p
-    row["read_peaks_called"] = True
+    if int(al["modal_n"][li]) <= 2:     # with more peaks no read is labelled (call_locus.py:1536)
+        for k, p in enumerate(al["read_peak"][a:a + len(recs)].tolist()):
+            recs[k]["p"] = p
+        row["read_peaks_called"] = True
     scs = [r["sc"] for r in recs if r["sc"] is not None]
     row["mean_model_align_score"] = math.fsum(scs) / len(scs) if scs else None
     if status != CALLED:

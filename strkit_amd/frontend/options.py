@@ -133,6 +133,36 @@ class MethylCallOptions(PhasedCallOptions):
 METHYL_OPTION_NAMES = ("use_methyl", "methyl_threshold")
 
 
+@dataclass
+class PloidyCallOptions(MethylCallOptions):
+    """MethylCallOptions plus the ploidy configuration of the sample (`strkit call --ploidy / --sex-chr`; strkit_amd/ploidy.py).
+    `ploidy`: the name of a bundled configuration, the path of a JSON file or a dict of its layout.  Every contig is then called
+    with its own number of alleles (1 .. alleles.MAX_ALLELES) and loci on a contig that is ignored or has 0 are
+    left out of the run.  It replaces `n_alleles`, which must stay at its default.  A type of its own for the reason
+    PoaCallOptions gives."""
+    ploidy: str | dict | None = None
+
+    def validate(self) -> None:
+        super().validate()
+        if self.ploidy is not None:
+            from ..ploidy import load_ploidy_config
+            load_ploidy_config(self.ploidy)
+            if self.n_alleles != CallOptions.n_alleles:
+                raise ValueError(f"ploidy and n_alleles ({self.n_alleles!r}) are two ways to say the same thing: give one of them")
+
+
+PLOIDY_OPTION_NAMES = ("ploidy",)
+
+
+def allele_counts(opts):
+    """What genotype.n_alleles_of takes for a run: its ploidy configuration where one is set, else its n_alleles."""
+    ploidy = getattr(opts, "ploidy", None)
+    if ploidy is None:
+        return opts.n_alleles
+    from ..ploidy import load_ploidy_config
+    return load_ploidy_config(ploidy)
+
+
 def phased(opts) -> bool:
     """Whether a switch of PhasedCallOptions is on (any options type may be asked)."""
     return bool(getattr(opts, "use_hp", False) or getattr(opts, "snv_vcf", None))
@@ -140,8 +170,11 @@ def phased(opts) -> bool:
 
 def with_keywords(opts: CallOptions | None, **option_keywords) -> CallOptions:
     """`opts` (or the defaults) with the options given by name replaced: dataclasses.replace, after widening a plain
-    CallOptions to PoaCallOptions when one of POA_OPTION_NAMES is among them, to PhasedCallOptions for PHASE_OPTION_NAMES, and to MethylCallOptions for METHYL_OPTION_NAMES.  An unknown name is a TypeError."""
+    CallOptions to PoaCallOptions when one of POA_OPTION_NAMES is among them, to PhasedCallOptions for PHASE_OPTION_NAMES, to
+    MethylCallOptions for METHYL_OPTION_NAMES, and to PloidyCallOptions for PLOIDY_OPTION_NAMES.  An unknown name is a TypeError."""
     opts = opts or CallOptions()
+    if not isinstance(opts, PloidyCallOptions) and any(k in option_keywords for k in PLOIDY_OPTION_NAMES):
+        opts = PloidyCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, MethylCallOptions) and any(k in option_keywords for k in METHYL_OPTION_NAMES):
         opts = MethylCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, PhasedCallOptions) and any(k in option_keywords for k in PHASE_OPTION_NAMES):
@@ -171,4 +204,5 @@ def report_parameters(opts: CallOptions, processes: int) -> dict:
             **({"snv_vcf": opts.snv_vcf, "snv_min_base_qual": opts.snv_min_base_qual} if getattr(opts, "snv_vcf", None) else {}),
             **({"significant_clip_threshold": opts.significant_clip_threshold} if phased(opts) else {}),
             **({"use_methyl": True} if getattr(opts, "use_methyl", False) else {}),
-            **({"methyl_threshold": opts.methyl_threshold} if getattr(opts, "use_methyl", False) and opts.methyl_threshold != 127 else {})}
+            **({"methyl_threshold": opts.methyl_threshold} if getattr(opts, "use_methyl", False) and opts.methyl_threshold != 127 else {}),
+            **({"ploidy": opts.ploidy} if getattr(opts, "ploidy", None) is not None else {})}

@@ -161,7 +161,11 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
     lengths of the header.  Loci without reference data have no anchor and are skipped, as the reference does
     (output/vcf.py:184-186).  `n_alleles` (one number, or a dict per contig): the report's own when not given, else 2."""
     if n_alleles is None:
-        n_alleles = (report.get("parameters") or {}).get("n_alleles", 2)
+        params = report.get("parameters") or {}
+        n_alleles = params.get("n_alleles", 2)
+        if params.get("ploidy") is not None:      # the run's ploidy configuration says how many alleles a contig has
+            from ..ploidy import load_ploidy_config
+            n_alleles = load_ploidy_config(params["ploidy"])
     formats = _FORMATS
     if any(_has_seqs(r) for r in report["results"]):
         formats = _FORMATS[:1] + _SEQ_FORMATS + _FORMATS[1:]
@@ -221,7 +225,8 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
         if peaks:
             mmas = row.get("mean_model_align_score")
             keys += ["MMAS", "DPS", "AD"]
-            vals += ["." if mmas is None else f"{mmas:.6g}", str(sum(peaks["n_reads"])), ",".join(map(str, peaks["n_reads"]))]
+            # (a call of more than two peaks labels no read: no depth per allele)
+            vals += ["." if mmas is None else f"{mmas:.6g}", str(sum(peaks["n_reads"])), ",".join(map(str, peaks["n_reads"])) or "."]
         if use_methyl and peaks:      # output/vcf.py:343-346: per allele, '.' per peak where the row has none
             for key in ("am", "amc"):
                 keys.append(key.upper()); vals.append(",".join(f"{x:.6g}" for x in peaks[key]) if peaks.get(key) else ",".join(["."] * n_peaks))
@@ -234,6 +239,8 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
             keys += ["ANCL", "CONS"]
             vals += [",".join(str(len(ar[1])) for ar in raw if ar is not None), ",".join(cons) if cons else "."]
         if reads:
+            if n_peaks is not None and not row.get("read_peaks_called", True):
+                n_peaks = None      # a call whose reads carry no peak: one group over all kept reads, as rows without a call
             keys += ["MCRL", "SLR"]
             vals += [",".join(mcrl_field(reads, n_peaks)), ",".join(slr_field(reads, n_peaks))]
         lines.append("\t".join((row["contig"], str(start0 + 1), row["locus_id"], ref_allele, alt, ".", ".", info, ":".join(keys), ":".join(vals))))

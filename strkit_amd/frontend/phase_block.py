@@ -13,6 +13,7 @@ from ..alleles import AlleleParams
 from ..phasing import ASSIGN_HP, ASSIGN_NAMES, ASSIGN_NONE, ASSIGN_SNV, ASSIGN_SNV_DIST, SNV_CALLED
 from . import phase_inputs as pi
 from .genotype import n_alleles_of
+from .options import allele_counts
 from .snv_vcf import read_snv_vcf
 
 MAX_CELLS = (512 << 20) // 2      # cells (a base and a quality byte each) of one phase_cells call: DESIGN.md §9's 512 MB
@@ -70,11 +71,12 @@ def _candidates(run: PhaseRun, loci, spans):
 def _gates(loci, opts, kept_locus, realigned, cn) -> np.ndarray:
     """Per locus whether the SNV step is allowed (phase_inputs.snv_step_allowed)."""
     ok = np.zeros(len(loci), bool)
+    counts = allele_counts(opts)
     for l, locus in enumerate(loci):
         m = kept_locus == l
         re_, cns = realigned[m], cn[m]
         rare = any(not (cns[~re_] == c).any() for c in cns[re_])
-        ok[l] = pi.snv_step_allowed(n_alleles_of(opts.n_alleles, locus.contig), int(re_.sum()), rare)
+        ok[l] = pi.snv_step_allowed(n_alleles_of(counts, locus.contig), int(re_.sum()), rare)
     return ok
 
 

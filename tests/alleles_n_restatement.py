@@ -1,0 +1,259 @@
+"""CPU restatement of the allele-calling rule for one to six alleles per locus, which k_alleles_n
+(strkit_amd/csrc/strk_alleles_n.h) runs on the device.
+
+Test infrastructure only: the product never imports this file.  It stands on alleles_restatement.py (the stream, the
+resampling, the single Gaussian, the percentiles, the peak assignment) and generalises what that file writes for two
+components: k-means++ for c centres, EM with c components, fit_gmm's loop that removes useless components round by round
+(strkit/call/allele.py:78-123) and the weighted draw that fills the kept fit up to n_alleles again (:276-288).  For
+n_alleles <= 2 every operation is the one alleles_restatement performs, in its order, so the results are equal to the bit.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from alleles_restatement import (CALLED, EMPTY_PEAK, EPS32, EPS64, SMALL_ALLELE_MIN, TOO_FEW, Params, _seqsum,
+                                 _weighted_log_prob, assign_peaks, mix64, percentile_iicdf, single_gaussian, uniforms)
+
+MAX_ALLELES = 6
+
+
+def local_trials(c: int) -> int:
+    """sklearn's n_local_trials = 2 + int(log(n_clusters))."""
+    return 2 + int(np.floor(np.log(c)))
+
+
+def kmeanspp_seeds_c(C: np.ndarray, v: np.ndarray, m: int, key: int, bidx: np.ndarray, init: int, c: int, r: int = 0):
+    """sklearn's _kmeans_plusplus for c clusters on counts, in reduction round r.  Returns the distinct-value index of the
+    c seeds per row ([rows, c])."""
+    R, d = C.shape
+    Cf = C.astype(np.float64)
+    cum = np.cumsum(C, axis=1)
+    s0 = np.minimum(np.floor(uniforms(key, 1, bidx, init, 64 * r) * m), m - 1)
+    idx = np.empty((R, c), dtype=np.int64)
+    idx[:, 0] = (cum <= s0[:, None]).sum(axis=1)
+    dd = v[None, :] - v[idx[:, 0]][:, None]
+    D2 = dd * dd   # minD^2 to the centres chosen so far
+    for q in range(1, c):
+        S = np.cumsum(Cf * D2, axis=1)
+        pot = S[:, -1]
+        best_k = best_pot = best_D2 = None
+        for t in range(local_trials(c)):
+            target = uniforms(key, 1, bidx, init, 64 * r + 8 * (q - 1) + 1 + t) * pot
+            ok = (C > 0) & (S >= target[:, None])
+            k = np.where(ok.any(axis=1), ok.argmax(axis=1), d - 1)
+            dc = v[None, :] - v[k][:, None]
+            new_D2 = np.minimum(D2, dc * dc)
+            cand = _seqsum(Cf * new_D2)
+            if t == 0:
+                best_k, best_pot, best_D2 = k, cand, new_D2
+            else:
+                better = cand < best_pot
+                best_k = np.where(better, k, best_k)
+                best_pot = np.where(better, cand, best_pot)
+                best_D2 = np.where(better[:, None], new_D2, best_D2)
+        idx[:, q] = best_k
+        D2 = best_D2
+    return idx
+
+
+def em_fit_c(C: np.ndarray, v: np.ndarray, m: int, seeds: np.ndarray, p: Params):
+    """EM of a spherical GMM from seed values seeds[rows, c].  Returns means, vars, weights (rows x c), the lower bound
+    and the iteration count, as sklearn's fit with n_init=1 would.  Sums over the components run in index order."""
+    R, d = C.shape
+    c = seeds.shape[1]
+    Cf = C.astype(np.float64)
+    nz = C > 0
+    v2 = v * v
+    nk0 = 1.0 + 10 * EPS64
+    means = seeds / nk0
+    var = (seeds * seeds) / nk0 - means * means + p.reg_covar
+    weights = np.full((R, c), nk0 / m)
+    lb = np.full(R, -np.inf)
+    n_iter = np.zeros(R, dtype=np.int64)
+    active = np.ones(R, dtype=bool)
+    for it in range(1, p.max_iter + 1):
+        a = np.nonzero(active)[0]
+        if a.size == 0:
+            break
+        Ca, nza = Cf[a], nz[a]
+        pc = 1.0 / np.sqrt(var[a])
+        with np.errstate(divide="ignore", invalid="ignore", under="ignore"):
+            wl = [_weighted_log_prob(v[None, :], v2[None, :], means[a, j:j + 1], pc[:, j:j + 1], weights[a, j:j + 1])
+                  for j in range(c)]
+            mx = wl[0]
+            for j in range(1, c):
+                mx = np.maximum(mx, wl[j])
+            se = np.exp(wl[0] - mx)
+            for j in range(1, c):
+                se = se + np.exp(wl[j] - mx)
+            lse = mx + np.log(se)
+            resp = [np.exp(wl[j] - lse) for j in range(c)]
+        new_lb = _seqsum(np.where(nza, Ca * lse, 0.0)) / m
+        nk, mm, vv = [], [], []
+        for j in range(c):
+            cr = np.where(nza, Ca * resp[j], 0.0)
+            nkj = _seqsum(cr) + 10 * EPS64
+            mean = _seqsum(cr * v[None, :]) / nkj
+            nk.append(nkj)
+            mm.append(mean)
+            vv.append(_seqsum(cr * v2[None, :]) / nkj - mean * mean + p.reg_covar)
+        tot = nk[0]
+        for j in range(1, c):
+            tot = tot + nk[j]
+        means[a], var[a], weights[a] = np.stack(mm, 1), np.stack(vv, 1), np.stack([x / tot for x in nk], 1)
+        change = new_lb - lb[a]
+        lb[a] = new_lb
+        n_iter[a] = it
+        active[a[np.abs(change) < p.tol]] = False
+    return means, var, weights, lb, n_iter
+
+
+def fit_gmm_c(C, v, m, key, bidx, p: Params, c: int, r: int = 0):
+    """GaussianMixture(c, k-means++, n_init, spherical).fit on each row: the best lower bound over the inits, the first
+    on ties."""
+    best = None
+    for init in range(p.n_init):
+        idx = kmeanspp_seeds_c(C, v, m, key, bidx, init, c, r)
+        means, var, weights, lb, _ = em_fit_c(C, v, m, v[idx], p)
+        if best is None:
+            best = [means, var, weights, lb]
+            continue
+        take = (lb > best[3]) | (best[3] == -np.inf)
+        for t, new in zip(best, (means, var, weights, lb)):
+            t[take] = new[take]
+    return best[0], best[1], best[2]
+
+
+def useless_components(gm, gw, c: int, p: Params):
+    """The number of components of each row's c-component fit that fit_gmm's two filters remove."""
+    allele_filter = (p.min_allele_reads - 0.1) / p.num_bootstrap
+    if c > 2:
+        thr = np.full(gm.shape[0], 1.0 / (p.filter_factor * c))
+    else:
+        sw = gm[:, 1] < gm[:, 0]
+        lo = np.where(sw, gm[:, 1], gm[:, 0])
+        hi = np.where(sw, gm[:, 0], gm[:, 1])
+        strict = (p.force_gm_filter != 0) | (hi < p.expansion_ratio * np.maximum(lo, SMALL_ALLELE_MIN))
+        thr = np.where(strict, 1.0 / (p.filter_factor * c), EPS32)
+    return c - ((gw > allele_filter) & (gw > thr[:, None])).sum(axis=1)
+
+
+def fit_rows_n(C, v, m, n_alleles, key, bidx, p: Params):
+    """fit_gmm (allele.py:57-123), the fill-up (:276-288) and the sort by mean on each row.  Returns k (the kept fit's
+    component count), means, weights, stdevs (rows x n_alleles)."""
+    R = C.shape[0]
+    A = n_alleles
+    k = np.ones(R, dtype=np.int64)
+    means = np.zeros((R, A))
+    weights = np.ones((R, A))
+    var = np.zeros((R, A))
+    sm, sv = single_gaussian(C, v, m)
+    means[:, 0], var[:, 0] = sm, sv
+    if A > 1:
+        c_of = np.where((C > 0).sum(axis=1) > 1, A, 1)
+        r_of = np.zeros(R, dtype=np.int64)
+        while np.any(c_of > 1):
+            for c, r in sorted({(int(x), int(y)) for x, y in zip(c_of, r_of) if x > 1}):
+                idx = np.nonzero((c_of == c) & (r_of == r))[0]
+                gm, gv, gw = fit_gmm_c(C[idx], v, m, key, bidx[idx], p, c, r)
+                nu = useless_components(gm, gw, c, p)
+                keep = (nu == 0) | (c - nu <= 0)   # none useless; or all of them: the loop ends with this fit
+                j = idx[keep]
+                k[j] = c
+                means[j, :c], var[j, :c], weights[j, :c] = gm[keep], gv[keep], gw[keep]
+                c_of[j] = 0
+                c_of[idx[~keep]] = c - nu[~keep]
+                r_of[idx[~keep]] += 1
+    stdevs = np.sqrt(var)
+    # rng.choice(k, size=A - k, p=w / sum |w|): a uniform against the CDF divided by its last entry, side="right"
+    for kk in range(1, A):
+        rows = np.nonzero(k == kk)[0]
+        if rows.size == 0:
+            continue
+        # the kept fit's components in the order of their means: the draw must not rest on how an init happened to label them
+        order = np.argsort(means[rows, :kk], axis=1, kind="stable")
+        for arr in (means, weights, stdevs):
+            arr[rows, :kk] = np.take_along_axis(arr[rows, :kk], order, axis=1)
+        w = weights[rows, :kk]
+        cdf = np.cumsum(w / _seqsum(np.abs(w))[:, None], axis=1)
+        cdf = cdf / cdf[:, -1:]
+        for t in range(A - kk):
+            u = uniforms(key, 2, bidx[rows], 0, t)
+            pick = np.minimum((cdf <= u[:, None]).sum(axis=1), kk - 1)
+            for arr in (means, weights, stdevs):
+                arr[rows, kk + t] = arr[rows, pick]
+    order = np.argsort(means, axis=1, kind="stable")
+    return k, *(np.take_along_axis(a, order, axis=1) for a in (means, weights, stdevs))
+
+
+def call_locus_n(cn, w, n_alleles: int, seed: int, p: Params = Params(), width: int = MAX_ALLELES) -> dict:
+    """The whole rule for one locus; the per-allele fields are padded to `width` slots (-1 / NaN)."""
+    cn = np.asarray(cn, dtype=np.int32)
+    w = np.asarray(w, dtype=np.float64)
+    n = cn.shape[0]
+    A = int(n_alleles)
+    out = dict(status=TOO_FEW, modal_n=0, call=[-1] * width, ci95=[-1] * 2 * width, ci99=[-1] * 2 * width,
+               means=[np.nan] * width, weights=[np.nan] * width, stdevs=[np.nan] * width, peak_n_reads=[0, 0],
+               read_peak=np.full(n, -1, np.int32), median_tie=False, median_cands=[])
+    if n < p.min_reads:
+        return out
+    v_int = np.unique(cn)
+    median_tie = False
+    median_cands = []
+    if v_int.shape[0] == 1:
+        val = int(v_int[0])
+        modal_n = 1
+        means = [float(val)] * A
+        weights = [1.0 / A] * A
+        stdevs = [0.0] * A
+        calls = [val] * A
+        ci95 = [[val, val]] * A
+        ci99 = ci95
+    elif n < A:
+        return out   # sklearn refuses n_samples < n_components
+    else:
+        B = p.num_bootstrap
+        key = mix64(seed)
+        v = v_int.astype(np.float64)
+        d = v.shape[0]
+        didx = np.searchsorted(v_int, cn)
+        cdf = np.cumsum(w)
+        cdf /= cdf[-1]
+        bidx = np.arange(B, dtype=np.int64)
+        u = uniforms(key, 0, bidx[:, None], 0, np.arange(n)[None, :])
+        pick = np.searchsorted(cdf, u, side="right")
+        C = np.zeros((B, d), dtype=np.int64)
+        np.add.at(C, (np.repeat(bidx, n), didx[pick].ravel()), 1)
+        k, bm, bw, bs = fit_rows_n(C, v, n, A, key, bidx, p)
+        calls, ci95, ci99, means, weights, stdevs = [], [], [], [], [], []
+        mid = B // 2
+        for a in range(A):
+            order = np.argsort(bm[:, a], kind="stable")
+            row = bm[order, a]
+            ci95.append([int(np.rint(percentile_iicdf(row, 2.5))), int(np.rint(percentile_iicdf(row, 97.5)))])
+            ci99.append([int(np.rint(percentile_iicdf(row, 0.5))), int(np.rint(percentile_iicdf(row, 99.5)))])
+            means.append(float(row[mid]))
+            calls.append(int(np.rint(row[mid])))
+            weights.append(float(bw[order[mid], a]))
+            stdevs.append(float(bs[order[mid], a]))
+            near = np.abs(bm[:, a] - row[mid]) <= 1e-9 * abs(row[mid])
+            median_tie |= bool(np.any(near & ((bw[:, a] != weights[-1]) | (bs[:, a] != stdevs[-1]))))
+            median_cands.append((bw[near, a].copy(), bs[near, a].copy()))
+        tot = weights[0]
+        for x in weights[1:]:
+            tot = tot + x
+        weights = [x / tot for x in weights]
+        counts = np.bincount(k, minlength=MAX_ALLELES + 1)
+        modal_n = int(np.argmax(counts))   # the first, so the smaller, on ties
+    if modal_n <= 2:
+        labels, cnt = assign_peaks(cn, modal_n, means, weights, stdevs)
+        status = EMPTY_PEAK if min(cnt[:modal_n]) == 0 else CALLED
+    else:   # "We cannot call read-level cluster labels with >2 peaks"
+        labels, cnt, status = np.full(n, -1, np.int32), [0, 0], CALLED
+    pad = width - A
+    out.update(status=status, modal_n=modal_n, call=list(calls) + [-1] * pad,
+               ci95=[x for c in ci95 for x in c] + [-1, -1] * pad, ci99=[x for c in ci99 for x in c] + [-1, -1] * pad,
+               means=list(means) + [np.nan] * pad, weights=list(weights) + [np.nan] * pad,
+               stdevs=list(stdevs) + [np.nan] * pad, peak_n_reads=[cnt[0], cnt[1]], read_peak=labels,
+               median_tie=v_int.shape[0] > 1 and median_tie, median_cands=median_cands)
+    return out
