@@ -1,4 +1,4 @@
-"""Allele calling on the GPU: bootstrapped GMM genotypes per locus (strk_call_alleles, kernel k_alleles).
+"""Allele calling on the GPU: bootstrapped GMM genotypes per locus (strk_call_alleles / strk_call_alleles_n, kernel k_alleles_w).
 
 Drop-in for STRkit's call_alleles (strkit/call/allele.py:176-336) plus the distance-based peak assignment of
 call_locus.py:1536-1600.  The algorithm is the reference's with one specified random stream instead of numpy's
@@ -93,23 +93,28 @@ def batch_outputs(n_loci: int, n_reads: int, width: int = 2) -> dict:
                 peak_n_reads=np.empty((n_loci, 2), np.int32), read_peak=np.empty(n_reads, np.int32))
 
 
+def _call_batch(width: int, read_off, cns, weights, n_alleles, seeds, params, ctx, with_stats: bool):
+    """One library call for many loci through the entry point whose rows have `width` allele slots."""
+    params = params or AlleleParams()
+    ctx = ctx or _lib.default_context()
+    read_off, cns, weights, n_alleles, seeds, n_loci = batch_inputs(read_off, cns, weights, n_alleles, seeds)
+    out = batch_outputs(n_loci, cns.shape[0], width)
+    cp = params._c()
+    st = _lib.StrkStats()
+    entry = _lib.load().strk_call_alleles if width == 2 else _lib.load().strk_call_alleles_n
+    _lib.check(entry(ctx.handle, n_loci, *map(ptr, (read_off, cns, weights, n_alleles, seeds)), C.byref(cp),
+                     *[ptr(out[k]) for k in (*ALLELE_KEYS, "read_peak")], C.byref(st)))
+    if with_stats:
+        return out, st.as_dict()
+    return out
+
+
 def call_alleles_batch(read_off, cns, weights, n_alleles, seeds, params: AlleleParams | None = None, ctx=None,
                        with_stats: bool = False):
     """One library call for many loci.  Locus l owns cns/weights[read_off[l]:read_off[l+1]].  Returns a dict of numpy
     arrays: status, modal_n [L]; call, means, weights, stdevs, peak_n_reads [L, 2]; ci95, ci99 [L, 2, 2];
     read_peak [n_reads] (-1: no call).  Slot 1 of a one-allele locus is -1 / NaN."""
-    params = params or AlleleParams()
-    ctx = ctx or _lib.default_context()
-    read_off, cns, weights, n_alleles, seeds, n_loci = batch_inputs(read_off, cns, weights, n_alleles, seeds)
-    out = batch_outputs(n_loci, cns.shape[0])
-    cp = params._c()
-    st = _lib.StrkStats()
-    _lib.check(_lib.load().strk_call_alleles(
-        ctx.handle, n_loci, *map(ptr, (read_off, cns, weights, n_alleles, seeds)), C.byref(cp),
-        *[ptr(out[k]) for k in (*ALLELE_KEYS, "read_peak")], C.byref(st)))
-    if with_stats:
-        return out, st.as_dict()
-    return out
+    return _call_batch(2, read_off, cns, weights, n_alleles, seeds, params, ctx, with_stats)
 
 
 def call_alleles_n_batch(read_off, cns, weights, n_alleles, seeds, params: AlleleParams | None = None, ctx=None,
@@ -118,18 +123,7 @@ def call_alleles_n_batch(read_off, cns, weights, n_alleles, seeds, params: Allel
     Same arguments; call, means, weights, stdevs are [L, 6] and ci95, ci99 [L, 6, 2], unused slots -1 / NaN;
     peak_n_reads stays [L, 2].  A locus whose modal number of peaks is above 2 has no read peaks (read_peak -1, counts 0).
     For n_alleles <= 2 the first two slots are call_alleles_batch's, byte for byte."""
-    params = params or AlleleParams()
-    ctx = ctx or _lib.default_context()
-    read_off, cns, weights, n_alleles, seeds, n_loci = batch_inputs(read_off, cns, weights, n_alleles, seeds)
-    out = batch_outputs(n_loci, cns.shape[0], MAX_ALLELES)
-    cp = params._c()
-    st = _lib.StrkStats()
-    _lib.check(_lib.load().strk_call_alleles_n(
-        ctx.handle, n_loci, *map(ptr, (read_off, cns, weights, n_alleles, seeds)), C.byref(cp),
-        *[ptr(out[k]) for k in (*ALLELE_KEYS, "read_peak")], C.byref(st)))
-    if with_stats:
-        return out, st.as_dict()
-    return out
+    return _call_batch(MAX_ALLELES, read_off, cns, weights, n_alleles, seeds, params, ctx, with_stats)
 
 
 class CallData:

@@ -1,6 +1,7 @@
-// strk_alleles_check.h — the input that strk_call_alleles and strk_call_alleles_phased share (loci as read_off[L + 1] over
-// cn / w, n_alleles and seed per locus, one strk_allele_params) and the one check of it.  Nothing of HIP in here: the header
-// compiles with the host compiler alone (tools/phase_asan.cpp drives it; tests/test_host.py builds and runs that program).
+// strk_alleles_check.h — the input that strk_call_alleles, strk_call_alleles_n and strk_call_alleles_phased share (loci as
+// read_off[L + 1] over cn / w, n_alleles and seed per locus, one strk_allele_params) and the one check of it.  Nothing of HIP
+// in here: the header compiles with the host compiler alone (tools/phase_asan.cpp and tools/alleles_n_asan.cpp drive it;
+// tests/test_host.py and tests/test_alleles_n_host.py build and run those programs).
 #pragma once
 
 #include <cmath>
@@ -22,11 +23,11 @@ struct Input {
 };
 
 struct Limits {
-    int max_reads, max_bootstrap, max_init;
+    int max_reads, max_bootstrap, max_init, max_alleles;
 };
 
 // Returns 0, or strk_groups::kInvalid and in `msg` what is wrong (the caller puts the function's name in front): the rule's
-// parameters, then every locus (its reads in order and at most max_reads, one or two alleles, every weight finite and > 0).
+// parameters, then every locus (its reads in order and at most max_reads, 1 .. max_alleles alleles, every weight finite and > 0).
 // A call of no loci is valid whatever its arrays are, but not without its parameters.  min_allele_reads is not looked at:
 // only the phased call needs it >= 1 (strk_phase_check.h).
 inline int check(const Input& in, const Limits& lim, strk_groups::Message* msg) {
@@ -51,7 +52,9 @@ inline int check(const Input& in, const Limits& lim, strk_groups::Message* msg) 
         const int64_t n = (int64_t)in.read_off[l + 1] - in.read_off[l];
         if (n < 0) return msg->invalid("locus %d: read_off is decreasing", l);
         if (n > lim.max_reads) return msg->invalid("locus %d: %lld reads (at most %d)", l, (long long)n, lim.max_reads);
-        if (in.n_alleles[l] != 1 && in.n_alleles[l] != 2) return msg->invalid("locus %d: n_alleles %d is not 1 or 2", l, in.n_alleles[l]);
+        if (in.n_alleles[l] < 1 || in.n_alleles[l] > lim.max_alleles)
+            return lim.max_alleles == 2 ? msg->invalid("locus %d: n_alleles %d is not 1 or 2", l, in.n_alleles[l])
+                                        : msg->invalid("locus %d: n_alleles %d is outside 1..%d", l, in.n_alleles[l], lim.max_alleles);
         for (int32_t r = in.read_off[l]; r < in.read_off[l + 1]; ++r)
             if (!std::isfinite(in.w[r]) || !(in.w[r] > 0.0)) return msg->invalid("locus %d: read %d has weight %g", l, r, in.w[r]);
     }

@@ -3,15 +3,13 @@
 //   strk_host.h     the calling thread's error message (fail, HIP_TRY) and the owning types: DevBuf, PinnedBuf, Stream, Event
 //   strk_policy.h   the adaptive policies as plain state machines: default window, band gate, grid history (no HIP in it)
 //   strk_groups.h   groups of byte strings as three calls take them: the view, its one check, the piece cutter (no HIP in it)
-//   strk_alleles_check.h, strk_phase_check.h   the input of the two allele calls and its checks (no HIP in them)
-//   strk_alleles_n_check.h   the check of strk_call_alleles_n's input: one to six alleles per locus (no HIP in it)
+//   strk_alleles_check.h, strk_phase_check.h   the input of the three allele calls and its checks (no HIP in them)
 //   strk_realign_plan.h   strk_realign's input check, chunks and workspace layout (no HIP in it)
 // and the other parts live in include fragments spliced into this file:
 //   strk_host_miss.inc       window-miss rounds                       strk_host_pipe.inc       the pinned-slot host pipeline
 //   strk_host_ref.inc        reference side                           strk_host_realign.inc    realignment
-//   strk_host_alleles.inc    allele calling                           strk_host_consensus.inc  best representatives
+//   strk_host_alleles.inc    allele calling, 2 or 6 slots per locus   strk_host_consensus.inc  best representatives
 //   strk_host_kmers.inc      distinct windows (k-mer counts)                 strk_host_phase.inc      phased allele calls
-//   strk_host_alleles_n.inc  allele calling, one to six alleles per locus
 //   strk_host_files.inc      the CPU-only file front end (its parser: strk_frontend.h)
 //   strk_dbam.inc            (at the end) the alignment file on the device: BGZF inflater, record scan, read extraction
 //   strk_phase_inputs.inc    (after it) tags, SNV cells and useful SNVs for the phased call: host twins and device entry points (walks and kernels: strk_phase_inputs.h)
@@ -26,7 +24,6 @@
 #include "strk_policy.h"
 #include "strk_groups.h"
 #include "strk_phase_check.h"
-#include "strk_alleles_n_check.h"
 #include "strk_phase_inputs.h"
 #include "strk_methyl.h"
 
@@ -53,7 +50,6 @@
 #include "strk_frontend.h"
 #include "strk_inflate.h"
 #include "strk_alleles.h"
-#include "strk_alleles_n.h"
 #include "strk_phase.h"
 #include "strk_consensus.h"
 #include "strk_kmers.h"
@@ -892,7 +888,6 @@ int check_groups(const char* fn, const strk_groups::View& v, int max_group, int 
 }
 
 #include "strk_host_alleles.inc"
-#include "strk_host_alleles_n.inc"
 #include "strk_host_phase.inc"
 #include "strk_host_consensus.inc"
 #include "strk_host_kmers.inc"
@@ -1122,7 +1117,7 @@ int strk_call_alleles(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off, co
     static_assert(STRK_ALLELE_CALLED == 0 && STRK_ALLELE_TOO_FEW == 1 && STRK_ALLELE_EMPTY_PEAK == 2, "include/strkit_amd.h <-> strk_alleles.h");
     const AlleleOut out{out_status, out_modal_n, out_call, out_ci95, out_ci99, out_means, out_weights, out_stdevs, out_peak_n_reads,
                         out_read_peak};
-    return call_alleles_impl(ctx, fn, {n_loci, read_off, cn, w, n_alleles, seed, p}, out, stats);
+    return call_alleles_impl<2>(ctx, fn, {n_loci, read_off, cn, w, n_alleles, seed, p}, out, stats);
 }
 
 int strk_call_alleles_n(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off, const int32_t* cn, const double* w,
@@ -1133,10 +1128,10 @@ int strk_call_alleles_n(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off, 
     const char* fn = "strk_call_alleles_n";
     if (!ctx) return fail(STRK_E_INVALID, "%s: ctx is NULL", fn);
     if (ctx->pending) return fail(STRK_E_INVALID, "%s: a submitted call is pending on this context", fn);
-    static_assert(STRK_MAX_ALLELES == kMaxAlleles, "include/strkit_amd.h <-> strk_alleles_n.h");
-    const AlleleNOut out{out_status, out_modal_n, out_call, out_ci95, out_ci99, out_means, out_weights, out_stdevs, out_peak_n_reads,
-                         out_read_peak};
-    return call_alleles_n_impl(ctx, fn, {n_loci, read_off, cn, w, n_alleles, seed, p}, out, stats);
+    static_assert(STRK_MAX_ALLELES == kMaxAlleles, "include/strkit_amd.h <-> strk_alleles.h");
+    const AlleleOut out{out_status, out_modal_n, out_call, out_ci95, out_ci99, out_means, out_weights, out_stdevs, out_peak_n_reads,
+                        out_read_peak};
+    return call_alleles_impl<kMaxAlleles>(ctx, fn, {n_loci, read_off, cn, w, n_alleles, seed, p}, out, stats);
 }
 
 int strk_call_alleles_phased(strk_ctx* ctx, int32_t n_loci, const int32_t* read_off, const int32_t* cn, const double* w,

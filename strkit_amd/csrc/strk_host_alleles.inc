@@ -1,15 +1,17 @@
-// Host side of strk_call_alleles (strkit/call/allele.py:176-336 + call_locus.py:1536-1600): input checks (strk_alleles_check.h),
-// pieces, launches; and what strk_call_alleles_phased (strk_host_phase.inc) shares with it: the piece constants, AlleleOut and
-// its scatter, the rule's part of an AlleleArgs, the piece-relative offsets.
+// Host side of strk_call_alleles and strk_call_alleles_n (strkit/call/allele.py:176-336 + call_locus.py:1536-1600; DESIGN.md
+// §9, §15): input checks (strk_alleles_check.h), pieces, launches, for rows of W = 2 or kMaxAlleles allele slots; and what
+// strk_call_alleles_phased (strk_host_phase.inc) shares with it: the piece constants, AlleleOut and its scatter, the rule's
+// part of an AlleleArgs, the piece-relative offsets.
 // Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf and Carve of strk_host.h, and
 // strk_ctx, side_stream and timed_launch defined there); not a stand-alone header.
 // ---------------------------------------------------------------------------------------------
-// Allele calling: strk_call_alleles
+// Allele calling: strk_call_alleles, strk_call_alleles_n
 // ---------------------------------------------------------------------------------------------
 constexpr size_t kAlleleWsBudget = (size_t)512 << 20;   // workspace bytes of one piece (a larger single locus runs alone)
 constexpr int kAllelePieceLoci = 32768;
 
-// The caller's arrays: status, modal_n [L]; call, means, weights, stdevs, peak_n_reads [L][2]; ci95, ci99 [L][4]; read_peak per read.
+// The caller's arrays, W allele slots per locus: status, modal_n [L]; call, means, weights, stdevs [L][W]; ci95, ci99 [L][W][2];
+// peak_n_reads [L][2]; read_peak per read.
 struct AlleleOut {
     int32_t *status, *modal_n, *call, *ci95, *ci99;
     double *means, *weights, *stdevs;
@@ -19,26 +21,28 @@ struct AlleleOut {
     }
 };
 
-// The per-locus rows of a piece as they came down (`stride` ints of oi per locus, the first kAlleleOutI laid out as k_alleles
-// writes them; kAlleleOutD doubles of od) into the caller's arrays at loci l0 .. l0 + nl.
+// The per-locus rows of a piece as they came down (`stride` ints of oi per locus, the first AlleleRow<W>::kOutI laid out as
+// k_alleles_w<W> writes them; AlleleRow<W>::kOutD doubles of od) into the caller's arrays at loci l0 .. l0 + nl.
+template <int W>
 void scatter_alleles(const AlleleOut& out, int32_t l0, int32_t nl, const int32_t* oi, int stride, const double* od) {
+    using R = AlleleRow<W>;
     for (int32_t l = 0; l < nl; ++l) {
         const int32_t* s = oi + (size_t)l * stride;
-        const double* t = od + (size_t)l * kAlleleOutD;
+        const double* t = od + (size_t)l * R::kOutD;
         const size_t g = (size_t)(l0 + l);
         out.status[g] = s[0];
         out.modal_n[g] = s[1];
-        for (int e = 0; e < 2; ++e) {
-            out.call[2 * g + e] = s[2 + e];
-            out.peak_n_reads[2 * g + e] = s[12 + e];
-            out.means[2 * g + e] = t[e];
-            out.weights[2 * g + e] = t[2 + e];
-            out.stdevs[2 * g + e] = t[4 + e];
+        for (int e = 0; e < W; ++e) {
+            out.call[W * g + e] = s[R::kCall + e];
+            out.means[W * g + e] = t[e];
+            out.weights[W * g + e] = t[W + e];
+            out.stdevs[W * g + e] = t[2 * W + e];
         }
-        for (int e = 0; e < 4; ++e) {
-            out.ci95[4 * g + e] = s[4 + e];
-            out.ci99[4 * g + e] = s[8 + e];
+        for (int e = 0; e < 2 * W; ++e) {
+            out.ci95[2 * W * g + e] = s[R::kCi95 + e];
+            out.ci99[2 * W * g + e] = s[R::kCi99 + e];
         }
+        for (int e = 0; e < 2; ++e) out.peak_n_reads[2 * g + e] = s[R::kPeak + e];
     }
 }
 
@@ -57,7 +61,7 @@ AlleleArgs allele_rule_args(const strk_allele_params* p) {
     return a;
 }
 
-int allele_threads(int B) { return std::min(256, (B + 63) / 64 * 64); }   // block size of k_alleles
+int allele_threads(int B) { return std::min(256, (B + 63) / 64 * 64); }   // block size of k_alleles_w
 
 // off[l0 .. l0 + nl] of a call as the offsets of a piece that begins at l0
 void piece_offsets(const int32_t* off, int32_t l0, int32_t nl, std::vector<int32_t>& rel) {
@@ -65,11 +69,13 @@ void piece_offsets(const int32_t* off, int32_t l0, int32_t nl, std::vector<int32
     for (int32_t l = 0; l <= nl; ++l) rel[l] = off[l0 + l] - off[l0];
 }
 
+// W = 2: k_alleles, at most two alleles per locus, two workspace rows.  W = kMaxAlleles: k_alleles_n, a locus's n_alleles rows.
+template <int W>
 int call_alleles_impl(strk_ctx* c, const char* fn, const strk_alleles_check::Input& in, const AlleleOut& out, strk_stats* stats) {
     if (stats) memset(stats, 0, sizeof *stats);
     {
         strk_groups::Message m;
-        if (const int rc = strk_alleles_check::check(in, {kAlleleMaxReads, kAlleleMaxBootstrap, kAlleleMaxInit}, &m))
+        if (const int rc = strk_alleles_check::check(in, {kAlleleMaxReads, kAlleleMaxBootstrap, kAlleleMaxInit, W}, &m))
             return fail(rc, "%s: %s", fn, m.text);
     }
     const int32_t n_loci = in.n_loci;
@@ -80,13 +86,14 @@ int call_alleles_impl(strk_ctx* c, const char* fn, const strk_alleles_check::Inp
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st;
     if (const int rc = side_stream(c, &st)) return rc;
+    using R = AlleleRow<W>;
     const int B = p->num_bootstrap;
     std::vector<int64_t> ws_off;
     std::vector<int32_t> off_rel, oi;
     std::vector<double> od;
     auto locus_ws = [&](size_t l) {
         const int n = read_off[l + 1] - read_off[l];
-        return (int64_t)(n >= p->min_reads ? allele_ws_bytes(n, B) : 0);
+        return (int64_t)(n >= p->min_reads ? allele_ws_bytes(n, B, W == 2 ? 2 : in.n_alleles[l]) : 0);
     };
     for (int32_t l0 = 0, l1; l0 < n_loci; l0 = l1) {
         // one piece: loci in caller order while their workspace fits the budget
@@ -99,7 +106,7 @@ int call_alleles_impl(strk_ctx* c, const char* fn, const strk_alleles_check::Inp
         Carve ci, co;
         const size_t i_off = ci.take((snl + 1) * 4), i_cn = ci.take(snr * 4), i_w = ci.take(snr * 8), i_nal = ci.take(snl * 4),
                      i_seed = ci.take(snl * 8), i_wsoff = ci.take(snl * 8);
-        const size_t o_i = co.take(snl * kAlleleOutI * 4), o_d = co.take(snl * kAlleleOutD * 8), o_rp = co.take(snr * 4);
+        const size_t o_i = co.take(snl * R::kOutI * 4), o_d = co.take(snl * R::kOutD * 8), o_rp = co.take(snr * 4);
         int rc;
         if ((rc = c->al_in.ensure(ci.bytes))) return rc;
         if ((rc = c->al_ws.ensure(std::max<size_t>((size_t)wsum, 256)))) return rc;
@@ -125,17 +132,17 @@ int call_alleles_impl(strk_ctx* c, const char* fn, const strk_alleles_check::Inp
         HIP_TRY(hipMemcpyAsync(di + i_nal, in.n_alleles + l0, snl * 4, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(di + i_seed, in.seed + l0, snl * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(di + i_wsoff, ws_off.data(), snl * 8, hipMemcpyHostToDevice, st));
-        oi.resize(snl * kAlleleOutI);
-        od.resize(snl * kAlleleOutD);
+        oi.resize(snl * R::kOutI);
+        od.resize(snl * R::kOutD);
         if ((rc = timed_launch(c, st, stats, fn, "allele kernel", 1, [&] {
-                hipLaunchKernelGGL(k_alleles, dim3(nl), dim3(allele_threads(B)), 0, st, a);
+                hipLaunchKernelGGL(k_alleles_w<W>, dim3(nl), dim3(allele_threads(B)), 0, st, a);
             }, [&] {
                 HIP_TRY(hipMemcpyAsync(oi.data(), a.out_i, oi.size() * 4, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipMemcpyAsync(od.data(), a.out_d, od.size() * 8, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipMemcpyAsync(out.read_peak + r0, a.read_peak, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
                 return 0;
             }))) return rc;
-        scatter_alleles(out, l0, nl, oi.data(), kAlleleOutI, od.data());
+        scatter_alleles<W>(out, l0, nl, oi.data(), R::kOutI, od.data());
     }
     return 0;
 }

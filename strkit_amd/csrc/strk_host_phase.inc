@@ -44,7 +44,7 @@ int call_alleles_phased_impl(strk_ctx* c, const char* fn, const strk_phase_check
     };
     auto locus_ws = [&](size_t l) {   // ... and k_alleles' for the locus's two groups, whose reads are at most the locus's
         const int n = read_off[l + 1] - read_off[l];
-        return group_ws(l) + (int64_t)(n >= p->min_reads ? allele_ws_bytes(n, B) + allele_ws_bytes(0, B) + 1024 : 0);
+        return group_ws(l) + (int64_t)(n >= p->min_reads ? allele_ws_bytes(n, B, 2) + allele_ws_bytes(0, B, 2) + 1024 : 0);
     };
     for (int32_t l0 = 0, l1; l0 < n_loci; l0 = l1) {
         int64_t wsum = 0;
@@ -183,7 +183,7 @@ int call_alleles_phased_impl(strk_ctx* c, const char* fn, const strk_phase_check
                 return 0;
             }))) return rc;
         if (stats) stats->n_sub_batches += 1;
-        scatter_alleles(out.al, l0, nl, oi.data(), kPhaseOutI, od.data());
+        scatter_alleles<2>(out.al, l0, nl, oi.data(), kPhaseOutI, od.data());
         for (int32_t l = 0; l < nl; ++l) {
             const int32_t* s = oi.data() + (size_t)l * kPhaseOutI + kAlleleOutI;
             out.method[l0 + l] = s[0];

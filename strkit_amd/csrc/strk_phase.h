@@ -13,7 +13,7 @@
 // k_phase_pack    the groups' reads (cn, renormalised w) packed one group behind the other, with the CSR offsets and workspace
 //                 offsets that k_alleles takes.  A block's base offset is the sum of the sizes in front of it, which every block
 //                 forms for itself: no block waits for another.
-// k_alleles       (strk_alleles.h, unchanged) over the 2 L groups as single-allele loci.
+// k_alleles       (strk_alleles.h: k_alleles_w<2>) over the 2 L groups as single-allele loci.
 // k_phase_finish  one workgroup per locus: peak order, the combined call, every read's peak, the SNV calls (E).
 // Nothing here counts with an atomic where the order of the reads decides a tie; the LDS atomics of k_phase_group form sums,
 // minima and maxima only.
@@ -424,7 +424,7 @@ __global__ void __launch_bounds__(256) k_phase_pack(PhaseArgs a) {
         const int sz = a.gsz[g], p0 = (g & 1) ? a.gsz[g - 1] : 0;
         a.goff[g] = s_off[tid];
         if (g == 2 * a.n_loci - 1) a.goff[g + 1] = s_off[tid + 1];
-        a.gws_off[g] = a.aws_base[l] + ((g & 1) ? (int64_t)allele_ws_layout(nullptr, a.gsz[g - 1], a.B, nullptr) : 0);
+        a.gws_off[g] = a.aws_base[l] + ((g & 1) ? (int64_t)allele_ws_layout(nullptr, a.gsz[g - 1], a.B, 2, nullptr) : 0);
         double s = 0.0;   // the group's weights, summed in group order
         for (int j = 0; j < sz; ++j) s = s + a.w[r0 + a.perm[r0 + p0 + j]];
         s_sum[tid] = s;

@@ -26,7 +26,7 @@ struct Input : strk_alleles_check::Input {
 // SNVs) is the number of cells in front of locus l: the sum of reads x SNVs of the loci before it.
 inline int check(const Input& in, const Limits& lim, std::vector<int64_t>& cell_off, strk_groups::Message* msg) {
     cell_off.clear();
-    if (const int rc = strk_alleles_check::check(in, {lim.max_reads, lim.max_bootstrap, lim.max_init}, msg)) return rc;
+    if (const int rc = strk_alleles_check::check(in, {lim.max_reads, lim.max_bootstrap, lim.max_init, 2}, msg)) return rc;
     if (!in.pp) return msg->invalid("params is NULL");
     if (in.n_loci == 0) return 0;
     const strk_phase_params* pp = in.pp;

@@ -1,5 +1,5 @@
 """CPU restatement of the allele-calling rule for one to six alleles per locus, which k_alleles_n
-(strkit_amd/csrc/strk_alleles_n.h) runs on the device.
+(strkit_amd/csrc/strk_alleles.h) runs on the device.
 
 Test infrastructure only: the product never imports this file.  It stands on alleles_restatement.py (the stream, the
 resampling, the single Gaussian, the percentiles, the peak assignment) and generalises what that file writes for two

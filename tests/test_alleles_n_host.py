@@ -1,5 +1,5 @@
 """CPU: the C surface of strk_call_alleles_n without a device: the declaration, the export, refusals that need no context,
-and the host-only input check (strk_alleles_n_check.h) under its own driver."""
+and the host-only input check (strk_alleles_check.h with a limit of six alleles) under its own driver."""
 import os
 import re
 import shutil
@@ -20,7 +20,7 @@ def test_the_entry_point_is_declared_exported_and_refuses_a_null_context():
     assert lib.strk_call_alleles_n.argtypes == lib.strk_call_alleles.argtypes
     rc = lib.strk_call_alleles_n(None, 0, *([None] * 5), None, *([None] * 10), None)
     assert rc == _lib.STRK_E_INVALID and b"strk_call_alleles_n" in lib.strk_last_error()
-    # the two-allele entry point keeps its own check: strk_alleles_check.h is as it was
+    # the two-allele entry point keeps its own words for a count that is not 1 or 2
     old = open(os.path.join(ROOT, "strkit_amd", "csrc", "strk_alleles_check.h")).read()
     assert "n_alleles %d is not 1 or 2" in old
 

@@ -1,4 +1,4 @@
-// Host-only driver of strk_alleles_n_check.h (the input check of strk_call_alleles_n): random valid calls of one to six alleles
+// Host-only driver of strk_alleles_check.h under the limits of strk_call_alleles_n: random valid calls of one to six alleles
 // per locus and every refusal, on arrays of exactly their length, so that a sanitizer build sees any read beyond them.
 //   g++ -O1 -g -std=c++17 -fsanitize=address,undefined -fno-sanitize-recover=all -o alleles_n_check tools/alleles_n_asan.cpp && ./alleles_n_check
 // Counts its own failures; prints "<checks> checks, <n> failed" and exits 0 without one.
@@ -7,7 +7,7 @@
 #include <random>
 #include <vector>
 
-#include "../strkit_amd/csrc/strk_alleles_n_check.h"
+#include "../strkit_amd/csrc/strk_alleles_check.h"
 
 namespace {
 
@@ -66,10 +66,10 @@ Call random_call(std::mt19937& rng, int n_loci) {
     return c;
 }
 
-const strk_alleles_check::Limits kLim{65535, 1024, 15};
+const strk_alleles_check::Limits kLim{65535, 1024, 15, 6};
 
 int check(const Call& c, strk_groups::Message* m, int max_alleles = 6) {
-    return strk_alleles_n_check::check(c.input(), kLim, max_alleles, m);
+    return strk_alleles_check::check(c.input(), {kLim.max_reads, kLim.max_bootstrap, kLim.max_init, max_alleles}, m);
 }
 
 bool refused(const Call& c, const char* word) {
@@ -96,15 +96,15 @@ int main() {
         in.n_loci = 0;
         in.read_off = nullptr;
         in.cn = nullptr;
-        expect(strk_alleles_n_check::check(in, kLim, 6, &m) == 0, "a call of no loci is valid");
+        expect(strk_alleles_check::check(in, kLim, &m) == 0, "a call of no loci is valid");
         in.p = nullptr;
-        expect(strk_alleles_n_check::check(in, kLim, 6, &m) == strk_groups::kInvalid && std::strstr(m.text, "params"), "params NULL");
+        expect(strk_alleles_check::check(in, kLim, &m) == strk_groups::kInvalid && std::strstr(m.text, "params"), "params NULL");
         in = c.input();
         in.n_loci = -1;
-        expect(strk_alleles_n_check::check(in, kLim, 6, &m) == strk_groups::kInvalid, "n_loci < 0");
+        expect(strk_alleles_check::check(in, kLim, &m) == strk_groups::kInvalid, "n_loci < 0");
         in = c.input();
         in.seed = nullptr;
-        expect(strk_alleles_n_check::check(in, kLim, 6, &m) == strk_groups::kInvalid && std::strstr(m.text, "NULL"), "NULL argument");
+        expect(strk_alleles_check::check(in, kLim, &m) == strk_groups::kInvalid && std::strstr(m.text, "NULL"), "NULL argument");
     }
     for (int t = 0; t < 100; ++t) {
         const int n_loci = 2 + (int)(rng() % 20);

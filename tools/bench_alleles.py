@@ -1,5 +1,5 @@
-"""Throughput of strk_call_alleles (k_alleles) on HiFi-shaped diploid loci: 30 reads each, B = 100 (defaults), and of
-strk_call_alleles_n (k_alleles_n) on loci of `--n-alleles` alleles.
+"""Throughput of strk_call_alleles (k_alleles = k_alleles_w<2>) on HiFi-shaped diploid loci: 30 reads each, B = 100
+(defaults), and of strk_call_alleles_n (k_alleles_n = k_alleles_w<6>, the same kernel template) on loci of `--n-alleles` alleles.
 
 usage: python tools/bench_alleles.py [N_LOCI ...] [--reps R] [--n-alleles A] [--entry two|n]
 `--n-alleles A`: loci with A alleles (neighbours 5 to 19 apart), called with n_alleles = A; above 2 through strk_call_alleles_n.

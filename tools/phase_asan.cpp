@@ -58,7 +58,7 @@ int g_failed = 0, g_refusals = 0;
 void expect_plain(const Call& c, bool ok, const char* what, const char* needle = "") {
     strk_groups::Message m;
     m.text[0] = 0;
-    const int rc = strk_alleles_check::check(c.input(), {65535, 1024, 15}, &m);
+    const int rc = strk_alleles_check::check(c.input(), {65535, 1024, 15, 2}, &m);
     if (!(ok ? rc == 0 : (rc == strk_groups::kInvalid && strstr(m.text, needle)))) {
         fprintf(stderr, "FAILED plain %s: rc %d, message '%s'\n", what, rc, m.text);
         ++g_failed;
