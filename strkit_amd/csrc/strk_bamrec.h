@@ -33,7 +33,7 @@ struct Rec {
     const uint8_t* qual;
 };
 STRK_FE_HD bool parse_rec(const uint8_t* buf, int64_t n_bytes, int64_t off, Rec* r, int64_t* next) {
-    if (off + 4 > n_bytes) return false;
+    if (off < 0 || off > n_bytes - 4) return false;   // (an offset in front of the stream, or one so large that off + 4 wraps)
     const int32_t block = rd_i32(buf + off);
     if (block < 32 || off + 4 + block > n_bytes) return false;
     const uint8_t* p = buf + off + 4;

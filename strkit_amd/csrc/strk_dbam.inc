@@ -670,6 +670,10 @@ int strk_dbam_extract(strk_dbam* d, int32_t n_items, const int64_t* rec_off, con
     *d_seqs = nullptr;
     if (n_items == 0) { if (seq_off) seq_off[0] = 0; return 0; }
     if (!rec_off || !coords || !status || !nfl || !ntr || !nfr || !seq_off || !name_len) return fail(STRK_E_INVALID, "NULL argument");
+    // before any launch: every offset leaves room for a record's fixed part inside the stream (the kernels' parser checks the rest)
+    for (int32_t it = 0; it < n_items; ++it)
+        if (rec_off[it] < 0 || rec_off[it] > d->n_data - 36)
+            return fail(STRK_E_INVALID, "item %d: record offset %lld outside the stream", it, (long long)rec_off[it]);
     HIP_TRY(hipSetDevice(d->device));
     const size_t n = (size_t)n_items;
     int rc;
@@ -734,8 +738,19 @@ int strk_dbam_extract(strk_dbam* d, int32_t n_items, const int64_t* rec_off, con
 // Read names of n records (strk_bam_names' contract, out_off [n + 1] is an INPUT here: the running sum of the name lengths
 // strk_dbam_extract reported); fills out[0 .. out_off[n]).
 int strk_dbam_names(strk_dbam* d, int64_t n, const int64_t* rec_off, const int64_t* out_off, uint8_t* out) {
-    if (!d || n < 0 || (n > 0 && (!rec_off || !out_off || !out))) return fail(STRK_E_INVALID, "bad argument");
-    if (n == 0 || out_off[n] == 0) return 0;
+    if (!d || n < 0 || n > INT32_MAX || (n > 0 && (!rec_off || !out_off || !out))) return fail(STRK_E_INVALID, "bad argument");
+    if (n == 0) return 0;
+    // before any launch (k_dbam_names parses nothing): the name slices ascend from 0 and every one lies inside the stream
+    if (out_off[0] != 0) return fail(STRK_E_INVALID, "item 0: out_off must ascend from 0");
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t len = out_off[i + 1] - out_off[i];
+        if (len < 0) return fail(STRK_E_INVALID, "item %lld: out_off must ascend from 0", (long long)i);
+        if (rec_off[i] < 0 || rec_off[i] > d->n_data - 36)
+            return fail(STRK_E_INVALID, "item %lld: record offset %lld outside the stream", (long long)i, (long long)rec_off[i]);
+        if (len > d->n_data - 36 - rec_off[i])
+            return fail(STRK_E_INVALID, "item %lld: a name of %lld bytes runs past the stream", (long long)i, (long long)len);
+    }
+    if (out_off[n] == 0) return 0;
     HIP_TRY(hipSetDevice(d->device));
     int rc;
     if ((rc = d->w_a.ensure((size_t)n * 8)) || (rc = d->w_d.ensure((size_t)(n + 1) * 8)) || (rc = d->w_c.ensure((size_t)out_off[n] + 16))) return rc;

@@ -196,7 +196,7 @@ def write_bam(path: str, contigs: list[tuple[str, int]], records: list[dict]) ->
     """records: dicts with name, flag, contig, pos, mapq, cigar [(len, op letter)], seq, qual (array or None);
     written in the given order (sort by (contig, pos) for a coordinate-sorted file)."""
     text = "@HD\tVN:1.6\tSO:coordinate\n" + "".join(f"@SQ\tSN:{n}\tLN:{ln}\n" for n, ln in contigs)
-    tid = {n: i for i, (n, _) in enumerate(contigs)}
+    tid = {"*": -1, **{n: i for i, (n, _) in enumerate(contigs)}}   # contig "*": an unmapped record (pos -1, flag 4, no CIGAR)
     buf = bytearray(b"BAM\x01" + struct.pack("<i", len(text)) + text.encode() + struct.pack("<i", len(contigs)))
     for n, ln in contigs:
         buf += struct.pack("<i", len(n) + 1) + n.encode() + b"\0" + struct.pack("<i", ln)

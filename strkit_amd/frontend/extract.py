@@ -67,7 +67,7 @@ class CigarIndex:
         lens = (segment.cigar >> 4).astype(np.int64)
         q0 = np.concatenate(([0], np.cumsum(lens * _CONSUMES_QUERY[ops])[:-1]))
         r0 = segment.start + np.concatenate(([0], np.cumsum(lens * _CONSUMES_REF[ops])[:-1]))
-        al = _ALIGNED[ops]
+        al = _ALIGNED[ops] & (lens > 0)      # a zero-length run holds no pair: it is neither the first nor the last aligned base
         self.q0, self.r0, self.ln = q0[al], r0[al], lens[al]
         self.k0 = np.concatenate(([0], np.cumsum(self.ln)[:-1])) if self.ln.size else np.zeros(0, np.int64)
         self.n_pairs = int(self.ln.sum())

@@ -102,6 +102,20 @@ def _span(r: dict) -> tuple[int, int]:
     return r["pos"], r["pos"] + sum(ln for ln, op in r["cigar"] if op in "MDN=X")
 
 
+# hand vectors: every position around the alignment is a candidate, so that the first / last aligned base, the first / last
+# base of every operation, D, N, the neighbours of I, odd and even read positions, lo - 1, lo, hi - 1 and hi are all there
+HAND_CIGARS = [
+    [(100, "S"), (300, "M"), (2, "D"), (300, "M"), (100, "S")],
+    [(99, "S"), (300, "M"), (2, "D"), (300, "M"), (99, "S")],
+    [(100, "S"), (280, "="), (3, "I"), (5, "X"), (4, "N"), (290, "M"), (99, "S")],
+    [(5, "H"), (100, "S"), (600, "M")],                       # the clip is not the first operation: no take-in
+    [(3, "D"), (10, "M"), (2, "I"), (7, "M"), (5, "N"), (1, "M"), (4, "D")],   # D before the first and after the last aligned pair
+    [(10, "M")], [(10, "S")], [(4, "D")], [],
+    [(100, "S"), (200, "M"), (100, "S")],                     # the two take-ins cross: lo > hi
+    [(0, "M"), (12, "M"), (0, "D"), (0, "I"), (9, "M")],
+]
+
+
 @functools.lru_cache(maxsize=None)
 def corpus() -> dict:
     """records (in file order), item_locus, cand_off, cand_pos, alt, want_tags and the rule's hp / ps / cells."""
@@ -113,19 +127,7 @@ def corpus() -> dict:
         hi = max(_span(r)[1] for r in recs) + margin
         return np.arange(lo, hi, dtype=np.int64)
 
-    # hand vectors: every position around the alignment is a candidate, so that the first / last aligned base, the first / last
-    # base of every operation, D, N, the neighbours of I, odd and even read positions, lo - 1, lo, hi - 1 and hi are all there
-    hand = [
-        [(100, "S"), (300, "M"), (2, "D"), (300, "M"), (100, "S")],
-        [(99, "S"), (300, "M"), (2, "D"), (300, "M"), (99, "S")],
-        [(100, "S"), (280, "="), (3, "I"), (5, "X"), (4, "N"), (290, "M"), (99, "S")],
-        [(5, "H"), (100, "S"), (600, "M")],                       # the clip is not the first operation: no take-in
-        [(3, "D"), (10, "M"), (2, "I"), (7, "M"), (5, "N"), (1, "M"), (4, "D")],   # D before the first and after the last aligned pair
-        [(10, "M")], [(10, "S")], [(4, "D")], [],
-        [(100, "S"), (200, "M"), (100, "S")],                     # the two take-ins cross: lo > hi
-        [(0, "M"), (12, "M"), (0, "D"), (0, "I"), (9, "M")],
-    ]
-    for k, cig in enumerate(hand):
+    for k, cig in enumerate(HAND_CIGARS):
         recs = [_record(rng, f"hand{k}", 1000 + k, cig, int_tag(b"HP", "C", 1) + int_tag(b"PS", "i", 1000 + k))]
         recs.append(_record(rng, f"hand{k}nq", 1001 + k, cig, b"", qual=None))
         loci.append((recs, dense(recs)))

@@ -1,0 +1,137 @@
+"""CPU: the conditions the front-end corpus (tests/frontend_cases.py) has to meet for tests/test_gpu_frontend_cases.py to test
+what it says it tests, and the host library (NativeBam, strk_extract_reads, strk_bam_names) against the rule on that corpus:
+H / N / P operations, records without qualities, CG-tag CIGARs, unmapped records and the non-default thresholds."""
+import numpy as np
+import pytest
+
+import frontend_cases as fc
+from strkit_amd import _lib
+from strkit_amd.frontend import NativeBam, extract_reads
+from strkit_amd.frontend.extract import get_aligned_pairs, get_read_coords_from_cigar, get_read_coords_from_matched_pairs
+
+DEFAULT = fc.PARAMS[0]
+
+
+@pytest.fixture(scope="module")
+def nb():
+    return NativeBam(fc.corpus_file()["path"])
+
+
+def test_corpus_has_the_kinds_of_records_it_is_meant_to_have():
+    c, f = fc.corpus(), fc.corpus_file()
+    segs, fields = f["bam"].segments, f["fields"]
+    assert f["bam"].references == [n for n, _ in fc.CONTIGS]
+    assert sorted(set(fields["tid"].tolist())) == [-1, 0, 2, 3]                    # three contigs with records, one without, unmapped
+    key = [(t if t >= 0 else 1 << 30, p) for t, p in zip(fields["tid"].tolist(), fields["pos"].tolist())]
+    assert key == sorted(key)                                                      # coordinate-sorted, the unmapped records last
+    un = c["unmapped"]
+    assert un.tolist() == list(range(len(segs) - len(un), len(segs))) and len(un) >= 5
+    assert all(segs[i].flag == 4 and segs[i].start == -1 and segs[i].cigar.size == 0 and segs[i].contig == "*" for i in un)
+    ops = "".join(fc._OPS[o] for i in c["hand"] for o in (segs[i].cigar & 15).tolist())
+    assert set("MIDNSHP=X") <= set(ops) and any((segs[i].cigar >> 4 == 0).any() for i in c["hand"])
+    assert {0, 1, 63, 64, 65, 200} <= {int(s.cigar.size) for s in segs}
+    assert len(c["cg"]) >= 20 and all(len(c["records"][i]["cigar"]) == 2 or c["records"][i].get("long_cigar") for i in c["cg"])
+    assert {True, False} == {segs[i].tags.startswith(b"CGBI") for i in c["cg"]}    # the tag in front of and behind other tags
+    assert {0, 1} == set((fields["l_seq"] & 1).tolist()) and {1, 2, 255} <= set(fields["l_name"].tolist())
+    assert {0, 16, 256, 2048, 4} <= set(fields["flag"].tolist())
+    assert len(segs) > 2000 and len(f["layout"][0]) > 8
+    # the spans interleave: most records start before an earlier one of their contig has ended
+    mapped = fields["tid"] >= 0
+    run_end = np.maximum.accumulate(np.where(mapped, fields["end"].astype(np.int64) + fields["tid"].astype(np.int64) * (1 << 32), 0))
+    start = fields["pos"].astype(np.int64) + fields["tid"].astype(np.int64) * (1 << 32)
+    assert int((start[1:][mapped[1:]] < run_end[:-1][mapped[1:]]).sum()) > 0.8 * int(mapped.sum())
+
+
+def test_corpus_items_meet_the_coverage_conditions():
+    c, f = fc.corpus(), fc.corpus_file()
+    segs = f["bam"].segments
+    e = fc.expected(DEFAULT, False)
+    st = e["status"]
+    share = np.bincount(st, minlength=3) / st.size
+    assert (share >= 0.10).all() and int((st == 0).sum()) >= 1000, share
+    ok = st == 0
+    n = e["nfl"] + e["ntr"] + e["nfr"]
+    assert len({(int(a) & 1, int(k) & 7) for a, k in zip(e["cut_a"][ok], n[ok])}) == 16
+    tracts = b"".join(e["seqs"][int(e["seq_off"][i]) + int(e["nfl"][i]):int(e["seq_off"][i]) + int(e["nfl"][i]) + int(e["ntr"][i])].tobytes()
+                      for i in np.nonzero(ok)[0])
+    assert set(tracts.decode()) >= set(fc.ALL_CODES + "X")
+    assert int((ok & np.isin(c["item_rec"], c["no_qual"])).sum()) >= 50
+    kinds = {"D": 0, "N": 0, "I": 0, "clamp": 0}
+    for it in np.nonzero(ok)[0]:
+        for k in fc.boundary_kinds(segs[int(c["item_rec"][it])], c["coords"][it]):
+            kinds[k] += 1
+    assert min(kinds.values()) >= 10, kinds
+    assert int((ok & (e["ntr"] == 0)).sum()) >= 10                                  # empty tracts
+    end = f["fields"]["end"][c["item_rec"]]
+    rfc = c["coords"][:, 3]
+    assert (st[rfc == end - 1] == 0).sum() >= 10 and (rfc == end).sum() >= 10 and (rfc == end + 1).sum() >= 10
+    assert (st[rfc >= end] == 1).all()                                              # call_locus.py:907-909
+    assert len(set(c["item_rec"][np.isin(c["item_rec"], c["cg"])].tolist())) >= 20
+    # the substitute alignments: some extracted, some not; the set without alt_start too
+    alt_items = np.array(sorted(c["alt"]))
+    ea = fc.expected(DEFAULT, True)
+    assert (np.bincount(ea["status"][alt_items], minlength=3) >= 10).all()
+    assert not np.array_equal(ea["status"], st) and (np.bincount(fc.expected_alt0(DEFAULT)["status"], minlength=3) >= 5).all()
+    # the other thresholds change what comes out
+    assert (fc.expected(fc.PARAMS[2], False)["status"] != 2).all() and b"X" not in fc.expected(fc.PARAMS[3], False)["seqs"].tobytes()
+    assert int((fc.expected(fc.PARAMS[3], False)["status"] == 2).sum()) > int((st == 2).sum())
+
+
+def test_the_run_index_of_the_rule_equals_the_pair_list_on_every_item():
+    """get_read_coords_from_cigar (what the expectations use) against get_read_coords_from_matched_pairs on the expanded pairs:
+    zero-length M runs at either end of an alignment, D before the first and behind the last pair included."""
+    c, segs = fc.corpus(), fc.corpus_file()["bam"].segments
+    pairs = {}
+    for it in range(len(c["item_rec"])):
+        i = int(c["item_rec"][it])
+        if i not in pairs:
+            pairs[i] = get_aligned_pairs(segs[i])
+        c4 = [int(x) for x in c["coords"][it]]
+        assert get_read_coords_from_cigar(*c4, segs[i]) == get_read_coords_from_matched_pairs(*c4, *pairs[i]), (segs[i].name, c4)
+
+
+def test_host_records_equal_read_bam(nb):
+    c, f = fc.corpus(), fc.corpus_file()
+    segs, fields = f["bam"].segments, f["fields"]
+    assert nb.n_records == len(segs) and nb.references == f["bam"].references
+    for k in ("rec_off", "tid", "pos", "end", "flag", "l_seq", "clip_l", "clip_r"):
+        assert np.array_equal(getattr(nb, k), fields[k]), k
+    assert nb.names(np.arange(nb.n_records)) == [s.name for s in segs]
+    assert nb.names(c["names"]) == ["", "x", "n" * 254]
+    for i in np.concatenate((c["hand"], c["cg"], c["no_qual"][:60], c["unmapped"])).tolist():
+        fc.same_segment(nb.segment(i), segs[i])
+    for contig in ("chrA", "chrB", "chrEmpty", "nowhere"):
+        for lo, hi in ((0, 10 ** 6), (1000, 1100), (20000, 20400), (5003, 5004)):
+            assert [nb.name(i) for i in nb.fetch_indices(contig, lo, hi)] == [s.name for s in f["bam"].fetch(contig, lo, hi)]
+
+
+@pytest.mark.parametrize("param", fc.PARAMS)
+@pytest.mark.parametrize("with_alt", [False, True])
+def test_host_extraction_equals_the_rule(nb, param, with_alt):
+    c = fc.corpus()
+    want = fc.expected(param, with_alt)
+    got = extract_reads(nb, c["item_rec"], c["coords"], *param, alt=c["alt"] if with_alt else None)
+    fc.same_extraction(got, got["seqs"], want)
+
+
+def test_host_extraction_without_alt_start(nb):
+    c = fc.corpus()
+    for param in fc.PARAMS:
+        got, seqs = fc.raw_extract(nb, c["alt0_rec"], c["alt0_coords"], c["alt0"], param, alt_start=False)
+        fc.same_extraction(got, seqs, fc.expected_alt0(param))
+
+
+def test_host_refusals(nb):
+    """An offset in front of the stream, at its end and inside its last bytes is refused by the parser every host entry point
+    goes through, with the item's number."""
+    L = _lib.load()
+    c = fc.corpus()
+    for bad in (-1, -(1 << 40), nb.data.size, nb.data.size - 3, (1 << 63) - 2):
+        rec = c["item_rec"][:3].copy()
+        got, _ = fc.raw_extract(nb, rec, c["coords"][:3], None, DEFAULT, rec_off=np.array([nb.rec_off[rec[0]], bad, nb.rec_off[rec[2]]], np.int64),
+                                check=False)
+        assert got["rc"] == _lib.STRK_E_INVALID and b"item 1" in L.strk_last_error(), bad
+        off = np.zeros(3, np.int64)
+        rc = L.strk_bam_names(nb.data.ctypes.data, nb.data.size, 2, _lib.ptr(np.array([nb.rec_off[0], bad], np.int64)), None, 0, _lib.ptr(off))
+        assert rc == _lib.STRK_E_INVALID, bad
+    assert nb.names(np.array([0])) == [fc.corpus_file()["bam"].segments[0].name]
