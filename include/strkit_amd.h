@@ -664,6 +664,61 @@ int strk_dbam_methyl(strk_dbam* d, int32_t n_items, const int64_t* rec_off, cons
 /* the size constants of k_dbam_methyl as built: bases per lane and pass, bases per pass, MM bytes per pass, ordinals per window */
 void strk_methyl_constants(int32_t* out4);
 
+/* ---- Mendelian inheritance and the de novo test of a child / mother / father trio ------------------------------
+ * Stands where `strkit mi` builds one MILocusData per trio locus (strkit/mi/result.py:100-175): respects_mi (:352-389,
+ * decimal=False) and de_novo_test (:391-501), with scipy.stats.chi2_contingency(correction=False) and
+ * scipy.stats.mannwhitneyu(use_continuity=False, method="auto") as its statistics.
+ *
+ * Locus l owns six groups of reads in the order child 0, child 1, mother 0, mother 1, father 0, father 1: group g is
+ * cn[grp_off[6l + g] .. grp_off[6l + g + 1]) (copy numbers >= 0, at most 65 535 per group, grp_off[6 n_loci] <= n_cn).
+ * gt[6l ..] = the six called copy numbers, ci95 / ci99 [12l ..] = their intervals (lo, hi), ci99 NULL: none (that kind is -1).
+ * seq_id / seq_len [6l ..] = the caller's small integer ids (equal ids = equal strings) and lengths of the six allele sequences;
+ * both NULL, or a negative id in a locus, = no sequences (the three sequence kinds are -1).
+ * out_respects[7l ..] = strict, pm1, ci_95, ci_99, seq, sl, sl_pm1 as 1, 0 or -1 (None).
+ * With params->test != STRK_MI_TEST_NONE: out_status = STRK_MI_TESTED, _OVERLAP (the child's reads are one value and so are a
+ * configuration's parents' under a WMW test, :416), _EMPTY_PARENT (:419) or _EMPTY_CHILD (this project's own: the reference
+ * fails there); out_p = the largest of the four configurations' p-values (first largest; NaN unless tested), out_config = its
+ * configuration 0..3 = (mother's allele, father's allele) in (0,0) (0,1) (1,0) (1,1), -1 unless tested; out_mutation_from =
+ * STRK_MI_FROM_*.  With test == STRK_MI_TEST_NONE grp_off and cn may be NULL and only out_respects is written.
+ * Every input is checked before any work: STRK_E_INVALID names the entry point and the locus.
+ * strk_mi_trio: kernels k_mi_small (one wave per locus, loci of at most 256 reads) and k_mi_large (one workgroup per locus); the
+ * call goes through in pieces of at most piece_loci loci (0: the default) whose workspace fits ws_budget bytes (0: the default);
+ * the result does not depend on either.  stats: kernel_ms, n_dp_launches, n_fallback = loci on k_mi_large, n_sub_batches = pieces.
+ * strk_mi_trio_host: the same rule on the host's cores, no device; piece_loci = the loci a thread takes at a time; it runs on
+ * at most OMP_NUM_THREADS threads where that is set, at most 16 where it is not. */
+#define STRK_MI_TEST_NONE 0
+#define STRK_MI_TEST_X2 1
+#define STRK_MI_TEST_WMW 2
+#define STRK_MI_TEST_WMW_GT 3
+#define STRK_MI_TESTED 0
+#define STRK_MI_OVERLAP 1
+#define STRK_MI_EMPTY_PARENT 2
+#define STRK_MI_EMPTY_CHILD 3
+#define STRK_MI_FROM_NONE 0
+#define STRK_MI_FROM_UNKNOWN 1 /* "?" */
+#define STRK_MI_FROM_MAT 2
+#define STRK_MI_FROM_PAT 3
+#define STRK_MI_FROM_BOTH 4
+typedef struct strk_mi_params {
+    int32_t test;        /* STRK_MI_TEST_* */
+    int32_t piece_loci;  /* 0: the default */
+    double sig_level;    /* in (0, 1) */
+    double widen;        /* >= 0: the parents' intervals grow by this share of each bound */
+    int64_t ws_budget;   /* workspace bytes of one piece; 0: the default */
+    int32_t force_large; /* must be 0 outside tests; non-zero: every locus goes to k_mi_large (same results, slower) */
+    int32_t pad;
+} strk_mi_params;
+int strk_mi_trio(strk_ctx* ctx, int32_t n_loci, const int64_t* grp_off /*[6n+1]*/, const int32_t* cn, int64_t n_cn,
+                 const int32_t* gt /*[6n]*/, const int32_t* ci95 /*[12n]*/, const int32_t* ci99 /*[12n] or NULL*/,
+                 const int32_t* seq_id /*[6n] or NULL*/, const int32_t* seq_len /*[6n] or NULL*/, const strk_mi_params* params,
+                 int8_t* out_respects /*[7n]*/, double* out_p /*[n]*/, int32_t* out_config, int32_t* out_mutation_from,
+                 int32_t* out_status, strk_stats* stats);
+int strk_mi_trio_host(int32_t n_loci, const int64_t* grp_off, const int32_t* cn, int64_t n_cn, const int32_t* gt, const int32_t* ci95,
+                      const int32_t* ci99, const int32_t* seq_id, const int32_t* seq_len, const strk_mi_params* params,
+                      int8_t* out_respects, double* out_p, int32_t* out_config, int32_t* out_mutation_from, int32_t* out_status);
+/* the size constants of the kernels as built: reads of k_mi_small's largest locus, loci per workgroup, reads per group */
+void strk_mi_constants(int32_t* out3);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,9 @@
 subset of `strkit call` (strkit/entry.py:20-342) that the device backend covers: per-read copy numbers per locus and, with
 `--call-alleles`, a genotype per locus (`--consensus`: with the sequence of every allele, which a VCF with alleles needs;
 `--consensus-method poa`: by partial-order alignment where the reads of an allele differ);
-`--count-kmers`: the motif-sized k-mers of every tract, per read and per allele."""
+`--count-kmers`: the motif-sized k-mers of every tract, per read and per allele.
+`python -m strkit_amd mi <child> <mother> <father> [--caller strkit-json|strkit-vcf] [--test [x2|wmw|wmw-gt]]` — `strkit mi` over
+the files `call` writes (strkit_amd/mi.py)."""
 from __future__ import annotations
 
 import argparse
@@ -62,12 +64,59 @@ def build_parser() -> argparse.ArgumentParser:
     c.add_argument("--rc-method", choices=("repalign",), default="repalign")
     c.add_argument("--max-rcn-iters", type=int, default=50)
     c.add_argument("--min-read-align-score", type=float, default=0.1)
+    # `strkit mi` (strkit/entry.py: the mi sub-parser) for this project's own call files
+    m = sub.add_parser("mi", help="Mendelian inheritance and the de novo test of a child / mother / father trio (GPU)")
+    m.add_argument("child_calls", metavar="child-calls")
+    m.add_argument("mother_calls", metavar="mother-calls")
+    m.add_argument("father_calls", metavar="father-calls")
+    m.add_argument("--caller", choices=("strkit-json", "strkit-vcf"), default="strkit-json", help="the format of the three call files")
+    m.add_argument("--widen", type=float, default=0.0, help="share of each bound by which the parents' 95 %% intervals grow")
+    m.add_argument("--contig", action="append", default=None, help="only this contig (may be given more than once)")
+    m.add_argument("--json", default=None, metavar="PATH", help="write the report as JSON (stdout: to standard output)")
+    m.add_argument("--no-tsv", action="store_true", help="do not print the table of output loci")
+    m.add_argument("--mismatch-out-mi", choices=("strict", "pm1", "ci_95", "ci_99", "seq", "sl", "sl_pm1"), default="pm1",
+                   help="without --test: the kind of inheritance whose failures are listed")
+    m.add_argument("--hist", action="store_true", help="print the inheritance rates per bin of locus length")
+    m.add_argument("--bin-width", type=int, default=10)
+    m.add_argument("--test", nargs="?", default="none", const="x2", choices=("none", "x2", "wmw", "wmw-gt"),
+                   help="de novo test per locus on the read-level copy numbers (the flag alone: x2)")
+    m.add_argument("--sig-level", type=float, default=0.05)
+    m.add_argument("--mt-corr", default="none",
+                   choices=("none", "bonferroni", "sidak", "holm-sidak", "holm", "simes-hochberg", "fdr_bh", "fdr_by", "fdr_tsbh", "fdr_tsbky"),
+                   help="correction for multiple testing (the two-stage methods fdr_tsbh and fdr_tsbky are refused)")
+    m.add_argument("--only-phased", action="store_true", help="strkit-vcf: only loci where all three members carry a phase set")
+    m.add_argument("--seed", type=int, default=None, help="seeds the split of a one-peak locus's reads into two groups (strkit-json)")
     return ap
+
+
+def main_mi(ap: argparse.ArgumentParser, a) -> int:
+    from . import mi
+    if not 0.0 < a.sig_level < 1.0:
+        ap.error("--sig-level must be inside (0, 1)")
+    if a.widen < 0 or a.bin_width < 1:
+        ap.error("--widen must be >= 0 and --bin-width >= 1")
+    if a.mt_corr in ("fdr_tsbh", "fdr_tsbky"):
+        ap.error(f"--mt-corr {a.mt_corr}: the two-stage methods fdr_tsbh and fdr_tsbky are not supported")
+    trio, out, res = mi.run_mi(a.child_calls, a.mother_calls, a.father_calls, caller=a.caller, widen=a.widen, contigs=a.contig,
+                               test=a.test, sig_level=a.sig_level, mt_corr=a.mt_corr, mismatch_out_mi=a.mismatch_out_mi,
+                               only_phased=a.only_phased, seed=mi.DEFAULT_SEED if a.seed is None else a.seed, bin_width=a.bin_width)
+    if res is None:
+        return 1
+    if not a.no_tsv:
+        sys.stdout.write(mi.locus_tsv(trio, out, res))
+    sys.stdout.write(mi.summary_text(res, a.widen) + "\n")
+    if a.hist:
+        sys.stdout.write(mi.histogram_text(res, a.bin_width) + "\n")
+    if a.json:
+        mi.write_report_json(trio, out, res, a.json)
+    return 0
 
 
 def main(argv=None) -> int:
     ap = build_parser()
     a = ap.parse_args(argv)
+    if a.cmd == "mi":
+        return main_mi(ap, a)
     if a.consensus and not a.call_alleles:
         ap.error("--consensus needs --call-alleles")
     if a.max_mdn_poa_length < 0:

@@ -17,6 +17,9 @@ STRK_NARROW_NONE, STRK_NARROW_DECREMENT, STRK_NARROW_HALVE, STRK_NARROW_AFTER_SE
 STRK_I16_CELL_MAY_SATURATE, STRK_I16_SCORE_SATURATES = 1, 2
 STRK_E_EMPTY = -61
 STRK_E_INVALID, STRK_E_NOMEM, STRK_E_DEVICE, STRK_E_NODEV = -22, -12, -5, -19
+STRK_MI_TEST_NONE, STRK_MI_TEST_X2, STRK_MI_TEST_WMW, STRK_MI_TEST_WMW_GT = range(4)
+STRK_MI_TESTED, STRK_MI_OVERLAP, STRK_MI_EMPTY_PARENT, STRK_MI_EMPTY_CHILD = range(4)
+STRK_MI_FROM_NONE, STRK_MI_FROM_UNKNOWN, STRK_MI_FROM_MAT, STRK_MI_FROM_PAT, STRK_MI_FROM_BOTH = range(5)
 (STRK_METHYL_OK, STRK_METHYL_NOT_SPANNING, STRK_METHYL_NO_TAGS, STRK_METHYL_CLIPPED, STRK_METHYL_MALFORMED,
  STRK_METHYL_NO_SITES) = range(6)
 
@@ -50,6 +53,12 @@ class StrkPhaseParams(C.Structure):
                 ("ws_budget", C.c_int64)]
 
 
+class MiParams(C.Structure):
+    """strk_mi_params.  force_large is for tests: every locus goes through k_mi_large."""
+    _fields_ = [("test", C.c_int32), ("piece_loci", C.c_int32), ("sig_level", C.c_double), ("widen", C.c_double),
+                ("ws_budget", C.c_int64), ("force_large", C.c_int32), ("pad", C.c_int32)]
+
+
 class StrkStats(C.Structure):
     _fields_ = [("dp_cells", C.c_int64), ("n_fallback", C.c_int32), ("n_miss_reads", C.c_int32),
                 ("n_miss_rounds", C.c_int32), ("kernel_ms", C.c_float), ("dp_kernel_ms", C.c_float),
@@ -78,7 +87,8 @@ EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk
            "strk_count_kmers", "strk_count_kmers_dseqs", "strk_count_kmers_ws",
            "strk_consensus", "strk_consensus_dseqs", "strk_consensus_ws",
            "strk_phase_cells", "strk_useful_snvs", "strk_dbam_phase_cells", "strk_dbam_download_cells", "strk_dbam_useful_snvs",
-           "strk_methyl", "strk_dbam_methyl", "strk_methyl_constants")
+           "strk_methyl", "strk_dbam_methyl", "strk_methyl_constants",
+           "strk_mi_trio", "strk_mi_trio_host", "strk_mi_constants")
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -251,6 +261,14 @@ def load(build: bool = True):
         L.strk_dbam_methyl.argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] * 2 + [C.c_void_p] * 4
         L.strk_methyl_constants.restype = None
         L.strk_methyl_constants.argtypes = [_i32p]
+        L.strk_mi_trio.restype = C.c_int
+        L.strk_mi_trio.argtypes = ([C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(MiParams)]
+                                   + [C.c_void_p] * 5 + [C.POINTER(StrkStats)])
+        L.strk_mi_trio_host.restype = C.c_int
+        L.strk_mi_trio_host.argtypes = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.POINTER(MiParams)]
+                                        + [C.c_void_p] * 5)
+        L.strk_mi_constants.restype = None
+        L.strk_mi_constants.argtypes = [_i32p]
         L.strk_device_mem.restype = C.c_int
         L.strk_device_mem.argtypes = [C.c_int, _i64p, _i64p]
         L.strk_realign_i16_flags.restype = C.c_int

@@ -26,6 +26,8 @@
 #include "strk_phase_check.h"
 #include "strk_phase_inputs.h"
 #include "strk_methyl.h"
+#include "strk_mi_check.h"
+#include "strk_mi.h"
 
 #include <algorithm>
 #include <array>
@@ -169,6 +171,8 @@ struct strk_ctx {
     // pass on some of its groups while its own arrays are still in use
     GroupStage po_in;
     DevBuf po_res, po_pool, po_poolof, po_list, po_ws, po_out, po_outoff;
+    // trio inheritance (strk_mi_trio): what goes up, the workspaces, what comes down
+    DevBuf mi_in, mi_ws, mi_out;
     HostCounters h_counters;        // pinned: counters + cells + scratch_used
     // a chain of events along one call: start | after k_hash + k_plan | after k_dp_band | after k_dp_band_wide | after the
     // first k_replay pass | after k_dp_all / k_dp_ref | after k_dp_long | after k_dp_generic | end (after k_replay and the
@@ -1290,3 +1294,4 @@ int strk_realign_i16_flags(int32_t n_pairs, const int64_t* s1_off, const int64_t
 #include "strk_dbam.inc"
 #include "strk_phase_inputs.inc"
 #include "strk_methyl.inc"
+#include "strk_host_mi.inc"
