@@ -53,6 +53,9 @@ def build_parser() -> argparse.ArgumentParser:
     c.add_argument("--use-hp", action="store_true", help="group reads by their HP / PS tags where a locus has enough tagged reads (needs --call-alleles)")
     c.add_argument("--incorporate-snvs", "--snv", "-v", dest="incorporate_snvs", default=None, metavar="PATH",
                    help="VCF (plain or gzip) of candidate SNVs: reads are grouped by the bases they carry at them (needs --call-alleles)")
+    c.add_argument("--snv-phase-sets", action="store_true",
+                   help="--incorporate-snvs: loci that share heterozygous SNVs get one phase set (PS, '|' genotypes), and the "
+                        "called SNVs are written to the VCF as records of their own")
     c.add_argument("--snv-min-base-qual", type=int, default=20)
     c.add_argument("--significant-clip-threshold", type=int, default=100)
     c.add_argument("--use-methyl", "-m", action="store_true",
@@ -125,6 +128,8 @@ def main(argv=None) -> int:
         ap.error(f"--count-kmers {a.count_kmers} needs --call-alleles")
     if (a.use_hp or a.incorporate_snvs) and not a.call_alleles:
         ap.error("--use-hp / --incorporate-snvs need --call-alleles")
+    if a.snv_phase_sets and not a.incorporate_snvs:
+        ap.error("--snv-phase-sets needs --incorporate-snvs")
     if a.ploidy is not None:
         if not a.call_alleles:
             ap.error("--ploidy needs --call-alleles")
@@ -158,6 +163,7 @@ def main(argv=None) -> int:
                               significant_clip_threshold=a.significant_clip_threshold) if a.use_hp or a.incorporate_snvs else {}),
                       **(dict(use_methyl=True, methyl_threshold=a.methyl_threshold) if a.use_methyl else {}),
                       **(dict(ploidy=a.ploidy) if a.ploidy is not None else {}),
+                      **(dict(snv_phase_sets=True) if a.snv_phase_sets else {}),
                       **(dict(call_alleles=True, consensus=a.consensus or bool(a.vcf), seed=a.seed, n_alleles=a.n_alleles)
                          if a.call_alleles else {}))
     if world > 1:

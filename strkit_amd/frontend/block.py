@@ -54,17 +54,18 @@ def _count(batch: LocusBatch, opts: CallOptions, ctx, tm=None):
     return res, filter_reads(batch, res, opts.min_read_align_score)
 
 
-def _genotype_tail(loci, n_kept, cn, ws, slices, opts: CallOptions, ctx, tm, phase=None):
+def _genotype_tail(loci, n_kept, cn, ws, slices, opts: CallOptions, ctx, tm, phase=None, sets=None):
     """The genotype tail of both block paths -> (al, cons, kmers), None for what is off: allele calls of the live `loci` over
     their kept reads (locus l owns the next n_kept[l] entries of `cn` / `ws`) and, with `consensus` or `count_kmers`, allele
     sequences and k-mer counts.  `slices()` is asked only then, and once: (tract_start, tract_len, anchor_start, anchor_len) of
     every kept read inside one buffer, and that buffer as the keywords of genotype.block_consensus (`seqs`, or `d_seqs` ...).
     `phase()` (with a switch of PhasedCallOptions on: call_blocks then hands its PhaseRun to the block paths): the block's phase_block.BlockPhase; the calls are then the phased ones,
-    and the consensus and k-mer stages take their read peaks unchanged."""
+    and the consensus and k-mer stages take their read peaks unchanged.  `sets` (snv_phase_sets): the run's phase_sets.PhaseSets;
+    the SNV calls are then fitted into phase sets, peaks turned over where need be, before those stages."""
     want_kmers = opts.count_kmers != "none"
     al = cons = kmers = None
     if opts.call_alleles:
-        al = (call_block_alleles_phased(loci, n_kept, cn, ws, opts, ctx, tm, phase()) if phase is not None
+        al = (call_block_alleles_phased(loci, n_kept, cn, ws, opts, ctx, tm, phase(), sets) if phase is not None
               else call_block_alleles(loci, n_kept, cn, ws, opts, ctx, tm))
     if (opts.consensus or want_kmers) and len(cn):      # (no kept read: nothing to cut, and both stages would return nothing)
         t_start, t_len, a_start, a_len, where = slices()
@@ -178,7 +179,7 @@ def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data
                                   np.array([r["w"] for x in recs_of for r in x], np.float64), slices, opts, ctx, tm,
                                   phase=(lambda: python_block_phase(phase_run, opts, [p[0] for p in prepared],
                                                                     [[(e[0], e[1] is not None) for e in p[2]] for p in prepared], kept_of, tm))
-                                  if phase_run is not None else None)
+                                  if phase_run is not None else None, sets=getattr(phase_run, "sets", None))
     first = 0
     for li, row in enumerate(results[-len(prepared):]):
         if al is not None:
@@ -308,7 +309,8 @@ def _block_device_stage(live, bam, opts: CallOptions, ctx, tm, phase_run=None) -
             [l for l, _ in live], np.bincount(read_locus[kept], minlength=len(live)), st.cn[kept], st.ws,
             lambda: extract_raw_slices(st, bam, coords, VCF_ANCHOR_SIZE, opts.min_avg_phred, tm), opts, ctx, tm,
             phase=(lambda: native_block_phase(phase_run, opts, [l for l, _ in live], bam, rec, item_locus.astype(np.int32), alt,
-                                              ok_items[kept], read_locus[kept], st.cn[kept], tm)) if phase_run is not None else None)
+                                              ok_items[kept], read_locus[kept], st.cn[kept], tm)) if phase_run is not None else None,
+            sets=getattr(phase_run, "sets", None))
     return st
 
 

@@ -21,14 +21,14 @@ from .fasta import Fasta
 from .gather import _distributed, call_blocks_sharded, deal_locus_blocks
 from .loci import Locus, load_loci, resolve_contig
 from .native import DeviceBam, IndexedBam, NativeBam
-from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, MethylCallOptions, PhasedCallOptions, PloidyCallOptions, PoaCallOptions,
+from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, MethylCallOptions, PhasedCallOptions, PhaseSetCallOptions, PloidyCallOptions, PoaCallOptions,
                       allele_counts, phased, report_parameters, with_keywords)
 from .phase_block import PhaseRun
 from .reader import open_path
 from .refside import get_loci_with_ref_data, get_locus_with_ref_data, ref_side_of_blocks
 
 # (what moved to the other modules is still offered here under the names it had)
-__all__ = ["CallOptions", "PoaCallOptions", "PhasedCallOptions", "MethylCallOptions", "PloidyCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
+__all__ = ["CallOptions", "PoaCallOptions", "PhasedCallOptions", "MethylCallOptions", "PloidyCallOptions", "PhaseSetCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
 
 
 def ploidy_blocks(blocks, opts):
@@ -213,6 +213,7 @@ def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = Non
     opts.validate()
     blocks, _ = ploidy_blocks(blocks, opts)
     phase_run = PhaseRun(opts) if phased(opts) else None     # the candidate SNVs and the renumbering of the phase sets: one per run
+    sets = phase_run.sets if phase_run is not None else None      # (snv_phase_sets: phase sets across loci, phase_sets.py)
     ctx = ctx or _lib.default_context()
     run_block = _call_block_native if isinstance(bam, (NativeBam, IndexedBam, DeviceBam)) else _call_block_python
     results: list[dict] = []
@@ -227,12 +228,12 @@ def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = Non
             ref_data = ([ref_cache[id(l)] for l in block] if all(id(l) in ref_cache for l in block)
                         else get_loci_with_ref_data(block, ref, opts.respect_ref, ctx))
             tm["ref_side_s"] += time.perf_counter() - t_a
-            ids = phase_run.remap.snapshot() if phase_run is not None else None
+            ids = phase_run.snapshot() if phase_run is not None else None
             # (without a switch of PhasedCallOptions the block paths are called as they always were)
             rows, n = run_block(block, records, opts, ctx, tm, ref_data, **({"phase_run": phase_run} if phase_run is not None else {}))
         except _lib.StrkError as e:
             if ids is not None:     # the phase sets a failed block has numbered are numbered again by its re-run, from where it began
-                phase_run.remap.restore(ids)
+                phase_run.restore(ids)
             if len(block) > 1:
                 for locus in block:
                     safe([locus], records)
@@ -247,14 +248,25 @@ def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = Non
         feed = _PrefetchFeed(blocks, bam, tm)
     elif isinstance(bam, DeviceBam) and bam.streamed:
         feed = _span_feed(blocks, bam, tm)
+    elif sets is not None:          # (a hand-made block that mixes contigs is split, as the two feeds above split it)
+        feed = ((b, bam) for block in blocks for b in _one_contig_blocks(block))
     else:
         feed = ((block, bam) for block in blocks)       # a reader that holds every record
     with closing(feed):             # a feed is a generator or has a close() of its own (the prefetcher's pool)
         if ref_cache is None:       # reference side of ALL loci first (unless the caller has it already)
             ref_cache = ref_side_of_blocks(blocks, ref, opts, ctx, tm)
         with _collector_paused():
+            # snv_phase_sets: all three feeds hand the blocks on in the order of `blocks`, the catalog's (PhaseSets.enter
+            # refuses any other); when the contig changes, and at the end, the finished contig's rows get their fix-up
+            contig, first_row = None, 0
             for block, records in feed:
+                if sets is not None and block[0].contig != contig:
+                    sets.finish_contig(results[first_row:])
+                    contig, first_row = block[0].contig, len(results)
                 safe(block, records)
+            if sets is not None:
+                sets.finish_contig(results[first_row:])
+                tm["phase_sets_s"] = sets.seconds
     results.sort(key=lambda r: r["locus_index"])
     return results, n_depth, tm
 

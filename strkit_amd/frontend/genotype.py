@@ -58,12 +58,14 @@ def call_block_alleles(loci, n_kept: np.ndarray, cns: np.ndarray, ws: np.ndarray
     return out
 
 
-def call_block_alleles_phased(loci, n_kept: np.ndarray, cns: np.ndarray, ws: np.ndarray, opts, ctx, tm, phase) -> dict:
+def call_block_alleles_phased(loci, n_kept: np.ndarray, cns: np.ndarray, ws: np.ndarray, opts, ctx, tm, phase, sets=None) -> dict:
     """call_block_alleles with the reads grouped by haplotags or SNVs where that applies: the same
     normalisation of the weights, the same seeds, ONE call_alleles_phased_batch(..., fallback=True).  `phase`: the block's
     phase_block.BlockPhase (hp / ps per kept read when use_hp, the useful SNVs' cells when snv_vcf).  Returns what
     call_block_alleles returns plus method, reason, ps, the SNV outputs, `phase`, and `snv_base` / `cell_off` (the cells as the
-    call took them and the cells in front of every locus)."""
+    call took them and the cells in front of every locus).  `sets` (snv_phase_sets): the run's phase_sets.PhaseSets; the SNV
+    calls are then fitted into phase sets across loci (`snv_ps` [L], -1 = none; peaks turned over where the set asks for it),
+    and the loci that lose every SNV to the filter take the plain call."""
     from ..phasing import PhaseParams, call_alleles_phased_batch
     t_a = time.perf_counter()
     n_loci = len(loci)
@@ -117,6 +119,20 @@ def call_block_alleles_phased(loci, n_kept: np.ndarray, cns: np.ndarray, ws: np.
     if used.snv_off is not None:
         out["snv_base"] = used.snv_base
         out["cell_off"] = np.concatenate(([0], np.cumsum(n_sel * np.diff(used.snv_off)))).astype(np.int64)
+        if sets is not None:
+            # snv_phase_sets: the rule of phase_sets.py over the block's SNV calls, here, before the consensus, k-mer and
+            # methylation stages read the peaks; the loci it demotes take the plain call, ONE call over all of them, with
+            # the arguments of call_alleles_phased_batch's fallback
+            from .phase_block import snv_id
+            from .phase_sets import demote, resolve_block
+            rest = resolve_block(sets, loci, out, phase, lambda l, s: snv_id(phase, l, s, loci[l].contig))
+            if rest.size:
+                reads = np.flatnonzero(np.isin(owner, rest))
+                sub, sub_st = call_alleles_batch(np.concatenate(([0], np.cumsum(n_kept[rest]))).astype(np.int32), np.asarray(cns, np.int32)[reads],
+                                                 w[reads] / sums[owner[reads]], np.minimum(nal[rest], 2), seeds[rest],
+                                                 opts.allele_params or AlleleParams(), ctx, with_stats=True)
+                demote(out, rest, sub, reads)
+                st["kernel_ms"] += sub_st["kernel_ms"]
     tm["alleles_s"] = tm.get("alleles_s", 0.0) + time.perf_counter() - t_a
     tm["alleles_device_s"] = tm.get("alleles_device_s", 0.0) + st["kernel_ms"] / 1e3
     return out

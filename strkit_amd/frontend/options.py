@@ -154,6 +154,23 @@ class PloidyCallOptions(MethylCallOptions):
 PLOIDY_OPTION_NAMES = ("ploidy",)
 
 
+@dataclass
+class PhaseSetCallOptions(PloidyCallOptions):
+    """PloidyCallOptions plus phase sets across loci for SNV calls (frontend/phase_sets.py).  `snv_phase_sets`: a
+    locus called by its SNVs joins the phase set of the loci before it that share a heterozygous site with it (its two peaks
+    turned over where their order disagrees), or opens a new one; its row and its reads get `ps`, and the VCF gets the SNVs as
+    records of their own.  Needs `snv_vcf`.  A type of its own for the reason PoaCallOptions gives."""
+    snv_phase_sets: bool = False
+
+    def validate(self) -> None:
+        super().validate()
+        if self.snv_phase_sets and not self.snv_vcf:
+            raise ValueError("snv_phase_sets=True requires snv_vcf: the phase sets are those of SNV calls")
+
+
+PHASE_SET_OPTION_NAMES = ("snv_phase_sets",)
+
+
 def allele_counts(opts):
     """What genotype.n_alleles_of takes for a run: its ploidy configuration where one is set, else its n_alleles."""
     ploidy = getattr(opts, "ploidy", None)
@@ -171,8 +188,11 @@ def phased(opts) -> bool:
 def with_keywords(opts: CallOptions | None, **option_keywords) -> CallOptions:
     """`opts` (or the defaults) with the options given by name replaced: dataclasses.replace, after widening a plain
     CallOptions to PoaCallOptions when one of POA_OPTION_NAMES is among them, to PhasedCallOptions for PHASE_OPTION_NAMES, to
-    MethylCallOptions for METHYL_OPTION_NAMES, and to PloidyCallOptions for PLOIDY_OPTION_NAMES.  An unknown name is a TypeError."""
+    MethylCallOptions for METHYL_OPTION_NAMES, to PloidyCallOptions for PLOIDY_OPTION_NAMES, and to PhaseSetCallOptions for
+    PHASE_SET_OPTION_NAMES.  An unknown name is a TypeError."""
     opts = opts or CallOptions()
+    if not isinstance(opts, PhaseSetCallOptions) and any(k in option_keywords for k in PHASE_SET_OPTION_NAMES):
+        opts = PhaseSetCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, PloidyCallOptions) and any(k in option_keywords for k in PLOIDY_OPTION_NAMES):
         opts = PloidyCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, MethylCallOptions) and any(k in option_keywords for k in METHYL_OPTION_NAMES):
@@ -205,4 +225,5 @@ def report_parameters(opts: CallOptions, processes: int) -> dict:
             **({"significant_clip_threshold": opts.significant_clip_threshold} if phased(opts) else {}),
             **({"use_methyl": True} if getattr(opts, "use_methyl", False) else {}),
             **({"methyl_threshold": opts.methyl_threshold} if getattr(opts, "use_methyl", False) and opts.methyl_threshold != 127 else {}),
-            **({"ploidy": opts.ploidy} if getattr(opts, "ploidy", None) is not None else {})}
+            **({"ploidy": opts.ploidy} if getattr(opts, "ploidy", None) is not None else {}),
+            **({"snv_phase_sets": True} if getattr(opts, "snv_phase_sets", False) else {})}

@@ -159,7 +159,8 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
               date: str | None = None) -> int:
     """Writes the loci of a report as VCF 4.2 text; returns the number of records.  `ref` (a Fasta) supplies the contig
     lengths of the header.  Loci without reference data have no anchor and are skipped, as the reference does
-    (output/vcf.py:184-186).  `n_alleles` (one number, or a dict per contig): the report's own when not given, else 2."""
+    (output/vcf.py:184-186).  `n_alleles` (one number, or a dict per contig): the report's own when not given, else 2.  A
+    report of a run with snv_phase_sets also gets the called SNVs of its rows as `VT=snv` records, sorted in by position."""
     if n_alleles is None:
         params = report.get("parameters") or {}
         n_alleles = params.get("n_alleles", 2)
@@ -190,6 +191,10 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
     lines += [f'##INFO=<ID={i},Number={n},Type={t},Description="{d}">' for i, n, t, d in _INFOS]
     lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + sample)
     n_rec = 0
+    # snv_phase_sets: the only switch that changes what is written for a row's SNVs
+    snv_records = bool((report.get("parameters") or {}).get("snv_phase_sets"))
+    records: list[tuple] = []
+    snvs_written: set = set()
     for row in sorted(report["results"], key=lambda r: (r["contig"], r.get("start_adj", r["start"]))):
         if "ref_start_anchor" not in row or "ref_seq" not in row:
             continue
@@ -243,8 +248,29 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
                 n_peaks = None      # a call whose reads carry no peak: one group over all kept reads, as rows without a call
             keys += ["MCRL", "SLR"]
             vals += [",".join(mcrl_field(reads, n_peaks)), ",".join(slr_field(reads, n_peaks))]
-        lines.append("\t".join((row["contig"], str(start0 + 1), row["locus_id"], ref_allele, alt, ".", ".", info, ":".join(keys), ":".join(vals))))
+        records.append((row["contig"], start0 + 1, 0, "\t".join((row["contig"], str(start0 + 1), row["locus_id"], ref_allele, alt, ".", ".", info,
+                                                                  ":".join(keys), ":".join(vals)))))
         n_rec += 1
+        if not snv_records or not call:
+            continue
+        # the row's called SNVs as records of their own (output/vcf.py:359-392), each once per contig, by the first row that holds it
+        ps = row.get("ps")
+        for snv in row.get("snvs") or []:
+            if (row["contig"], snv["id"]) in snvs_written:
+                continue
+            snvs_written.add((row["contig"], snv["id"]))
+            snv_alleles = (snv["ref"], *sorted({b for b in snv["call"] if b != snv["ref"]}))
+            if len(snv_alleles) < 2:
+                continue
+            keys = ["GT", "DP", "AD"] + (["PS"] if ps is not None else [])
+            vals = [("|" if ps is not None else "/").join(str(snv_alleles.index(b)) for b in snv["call"]), str(sum(snv["rcs"])),
+                    ",".join(map(str, snv["rcs"]))] + ([str(ps)] if ps is not None else [])      # (AD in call order, as there)
+            records.append((row["contig"], snv["pos"] + 1, 1, "\t".join((row["contig"], str(snv["pos"] + 1), snv["id"], snv_alleles[0],
+                                                                          ",".join(snv_alleles[1:]), ".", ".", "VT=snv", ":".join(keys), ":".join(vals)))))
+            n_rec += 1
+    if snv_records:      # SNV records among the STR records by position; at one position the STR record comes first
+        records.sort(key=lambda r: r[:3])
+    lines += [r[3] for r in records]
     with open(path, "w") as fh:
         fh.write("\n".join(lines) + "\n")
     return n_rec

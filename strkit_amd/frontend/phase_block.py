@@ -14,6 +14,7 @@ from ..phasing import ASSIGN_HP, ASSIGN_NAMES, ASSIGN_NONE, ASSIGN_SNV, ASSIGN_S
 from . import phase_inputs as pi
 from .genotype import n_alleles_of
 from .options import allele_counts
+from .phase_sets import PhaseSets
 from .snv_vcf import read_snv_vcf
 
 MAX_CELLS = (512 << 20) // 2      # cells (a base and a quality byte each) of one phase_cells call: DESIGN.md §9's 512 MB
@@ -22,11 +23,25 @@ __all__ = ["PhaseRun", "BlockPhase", "native_block_phase", "python_block_phase",
 
 
 class PhaseRun:
-    """What one run keeps across its blocks: the candidate SNVs (read once) and the renumbering of the phase sets."""
+    """What one run keeps across its blocks: the candidate SNVs (read once), the renumbering of the phase sets and, with
+    snv_phase_sets, the phase sets of the SNV calls (`sets`, a phase_sets.PhaseSets; the renumbering then counts with it)."""
 
     def __init__(self, opts):
         self.snvs = read_snv_vcf(opts.snv_vcf) if opts.snv_vcf else None
-        self.remap = pi.PhaseSetRemap()
+        self.sets = PhaseSets() if getattr(opts, "snv_phase_sets", False) else None
+        self.remap = pi.PhaseSetRemap(self.sets)
+        if self.sets is not None:
+            self.sets.remap = self.remap
+
+    def snapshot(self):
+        """What a block may change; restore() puts it back (a block that failed is run again locus by locus)."""
+        return self.remap.snapshot() if self.sets is None else self.sets.snapshot()
+
+    def restore(self, snap) -> None:
+        if self.sets is None:
+            self.remap.restore(snap)
+        else:
+            self.sets.restore(snap)
 
 
 @dataclass
@@ -175,7 +190,7 @@ def python_block_phase(run: PhaseRun, opts, loci, entries_of, kept_of, tm) -> Bl
 def phase_row(row: dict, al: dict, li: int, recs: list[dict], locus) -> None:
     """After genotype.genotype_row: the fields of a phased call on the row of locus `li` and on its read records.  Per tagged
     read `hp` / `ps`; for an `hp` call assign_method and the locus `ps`; for an SNV call assign_method, `snvs` (the called SNVs)
-    and per read `snvu`, its bases at them."""
+    and per read `snvu`, its bases at them and, with snv_phase_sets, `ps` on the row and on its reads with a peak."""
     bp: BlockPhase = al["phase"]
     a = int(al["read_off"][li])
     if bp.hp is not None:
@@ -195,10 +210,23 @@ def phase_row(row: dict, al: dict, li: int, recs: list[dict], locus) -> None:
         snvs = []
         for s in called:
             k = int(bp.snv_rec[s])
-            snvs.append({"id": c.ids[k] or f"{locus.contig}_{int(c.pos[k]) + 1}", "ref": c.ref[k], "pos": int(c.pos[k]),
+            snvs.append({"id": snv_id(bp, li, s, locus.contig), "ref": c.ref[k], "pos": int(c.pos[k]),
                          "call": [chr(int(b)) for b in al["snv_call"][s]], "rcs": [int(x) for x in al["snv_rcs"][s]]})
         row["snvs"] = snvs
         n_s = s1 - s0
         cell0 = int(al["cell_off"][li])
         for k, r in enumerate(recs):
             r["snvu"] = [chr(int(al["snv_base"][cell0 + k * n_s + (s - s0)])) for s in called]
+        # snv_phase_sets (phase_sets.resolve_block): the locus's phase set on the row and on every read with a peak, in the
+        # place of the one its tag gave it (call_locus.py:423-438)
+        if "snv_ps" in al and int(al["snv_ps"][li]) != -1:
+            row["ps"] = int(al["snv_ps"][li])
+            for r in recs:
+                if r.get("p") is not None and r["p"] >= 0:
+                    r["ps"] = row["ps"]
+
+
+def snv_id(bp: BlockPhase, li: int, s: int, contig: str) -> str:
+    """The id of useful SNV `s` of locus `li` of the block: its record's, else contig_position (snvs.py:148)."""
+    c, k = bp.contigs[li], int(bp.snv_rec[s])
+    return c.ids[k] or f"{contig}_{int(c.pos[k]) + 1}"

@@ -189,21 +189,30 @@ def snv_step_allowed(n_alleles: int, n_realigned_kept: int, have_rare_realigns: 
 
 class PhaseSetRemap:
     """Original PS values renumbered 1, 2, ... in order of first appearance (block order, locus order, read order); one object
-    per run (the reference's counter starts at 1, call_sample.py:379).  Untagged (-1) stays -1."""
+    per run (the reference's counter starts at 1, call_sample.py:379).  Untagged (-1) stays -1.  With a `counter` (an object
+    with take(): phase_sets.PhaseSets, which numbers the SNV calls' sets from the same sequence) a new value takes its number
+    from there, and clear() forgets the values of a finished contig."""
 
-    def __init__(self):
+    def __init__(self, counter=None):
         self._ids: dict[int, int] = {}
+        self._counter = counter
 
     def __call__(self, ps: np.ndarray, hp: np.ndarray | None = None) -> np.ndarray:
         ps = np.asarray(ps, np.int32)
         out = np.full(ps.shape, -1, np.int32)
         tagged = (ps != -1) if hp is None else (np.asarray(hp) != -1) | (ps != -1)
         for i in np.nonzero(tagged.ravel())[0]:
-            out.ravel()[i] = self._ids.setdefault(int(ps.ravel()[i]), len(self._ids) + 1)
+            key = int(ps.ravel()[i])
+            if key not in self._ids:
+                self._ids[key] = len(self._ids) + 1 if self._counter is None else self._counter.take()
+            out.ravel()[i] = self._ids[key]
         return out
 
     def __len__(self) -> int:
         return len(self._ids)
+
+    def clear(self) -> None:
+        self._ids.clear()
 
     def snapshot(self) -> dict:
         """The ids handed out so far; restore() puts them back (a block that failed is run again and numbers its phase sets anew)."""
