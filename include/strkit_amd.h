@@ -261,6 +261,10 @@ int strk_ref_repeat_count_batch(strk_ctx* ctx, int32_t n_loci, const int32_t* st
  * D consumes s2), written to cigar[cigar_off[p] ..] with out_n_cigar[p] runs; it starts at s2 position 0
  * (free leading s2 bases are one D run) and ends at out_end_ref.  2*|s1| + 4 runs always suffice.
  * gap_pref: which gap kind wins an exact score tie after the diagonal (0: I before D, the default; 1: D before I).
+ * Accepted: 0 <= extend <= open <= 4096, 1 <= |s1| <= 2^20, 1 <= |s2| <= 2^24 and, per pair,
+ * 2*open + (|s1| - 2)*extend < 2^24 (what the kernel's 28-bit scores hold: strk_realign.h at kRealignNeg).  Every accepted
+ * pair is exact; anything else is STRK_E_INVALID before any launch, with the pair named in strk_last_error().  A CIGAR range
+ * too small for its pair's runs is STRK_E_INVALID as well, found after the launch: nothing is written outside the pairs' ranges.
  * stats (optional): kernel_ms, dp_cells, exact_bytes = trace bytes written. */
 int strk_realign(strk_ctx* ctx, int32_t n_pairs, const uint8_t* s1, const int64_t* s1_off, const uint8_t* s2,
                  const int64_t* s2_off, int32_t open, int32_t extend, int32_t gap_pref, int32_t* out_score,

@@ -34,7 +34,25 @@ namespace strk {
 constexpr int kRealignMaxCL = 32;
 constexpr int kRealignPadSym = 17;     // pad column: scores 0 against every row symbol
 constexpr int kRealignRowStride = 32;  // bytes per row-symbol row of the LDS score table
+// kRealignNeg is "no gap yet" for the two gap states: -2^24 in score units (values are 16 * score + tag).  What it can
+// hold, with i the 0-based s1 position, o = open, e = ext, all in score units:
+//   - Row -1 is bnd(i) = -(o + i*e); left of column 0, H is 0 on every row.  So on every row H(i) >= E(i) >= -(o + i*e)
+//     (one gap from the left edge), and F(i) >= H(i) of the row before - o >= -(2*o + i*e).  Nothing legitimate lies below
+//     -(2*o + (n1 - 1)*e), and nothing that a real row computes lies below that less one more e: no int32 wraps while
+//     16 * (2*o + n1*e) < 2^31.
+//   - The sentinel meets a real value in two places only.  E, at the left edge of every row: (Neg - 16*e) | flag against
+//     0 - 16*o + tag, which the real value wins for every o <= 4096.  F, on row 0 of every column (Gd starts at Neg in every
+//     tile): (Neg + tagGd - 16*e) | kFlagGdExt against bnd(i) - 16*o + tagGd.  Both sides less tagGd are multiples of 16 but
+//     for the flag, so the opening wins, strictly as the oracle has it, iff 16 * (2*o + i*e) <= 2^28 + 16*e - 16, that is
+//     iff 2*o + (i - 1)*e < 2^24.  From row 1 on Gd holds that real value and every comparison is between real values.
+//   - i = n1 - 1 is the column that asks most: a pair is exact iff 2*open + (n1 - 2)*ext < 2^24, which also keeps every
+//     value above -2^29.  Where it fails, the sentinel's "extended gap" stands in for row 0's F from that column on: equal to
+//     the real value at the first such column (same scores), above it by ext per column after that, and once it is above
+//     that column's real H (about open further out) the scores are wrong: open = ext = 4096 against a one-base read is last
+//     accepted at n1 = 4095, still right in score up to 4098 and wrong from 4099 on (tests/test_realign_cases.py).
+// strk_realign_plan::plan refuses a pair beyond that bound (kGapCostLimit), so every accepted pair is exact.
 constexpr int kRealignNeg = -(1 << 28);
+static_assert(strk_realign_plan::kGapCostLimit * 16 == -(int64_t)kRealignNeg, "the planner's bound is derived from kRealignNeg");
 constexpr int kRealignStrip = 1024;    // row symbols staged in LDS per wave
 constexpr int kTagDiag = 8;            // bits 3:2 = 2
 constexpr int kTagMask = 12;

@@ -34,6 +34,11 @@ namespace strk_realign_plan {
 
 constexpr int kNoMem = -12;   // = STRK_E_NOMEM of include/strkit_amd.h (strk_api.hip asserts it)
 
+// What the kernel's number format holds (derived next to kRealignNeg in strk_realign.h, which asserts that the two agree):
+// a pair is exact if and only if 2 * open + (n1 - 2) * extend < kGapCostLimit.
+constexpr int64_t kGapCostLimit = (int64_t)1 << 24;
+inline int64_t gap_cost_reach(int64_t open, int64_t ext, int64_t n1) { return 2 * open + (n1 - 2) * ext; }
+
 // Pairs [p0, p1) of the call, run together: as many pairs in caller order as fit the trace budget, and always at least one.
 struct Chunk {
     int p0, p1;
@@ -71,6 +76,9 @@ inline int plan(int32_t n_pairs, const int64_t* s1_off, const int64_t* s2_off, c
         if (n1 < 1 || n2 < 1) return why->invalid("pair %d: empty sequence", p);
         if (n1 > (1 << 20) || n2 > (1 << 24))
             return why->invalid("pair %d: sequence too long (%lld x %lld)", p, (long long)n1, (long long)n2);
+        if (gap_cost_reach(open, ext, n1) >= kGapCostLimit)
+            return why->invalid("pair %d: gap costs beyond the number format (2*open + (n1 - 2)*extend = %lld, must be below %lld)", p,
+                                (long long)gap_cost_reach(open, ext, n1), (long long)kGapCostLimit);
         if (cap < 0) return why->invalid("pair %d: negative CIGAR capacity", p);
         strk::RealignPair& r = all[p];
         r.s1_off = s1_off[p] - s1_off[0];

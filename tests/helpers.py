@@ -165,18 +165,27 @@ def cigar_tuples(cig):
     return [(int(x) >> 4, "MIDNSHP=X"[int(x) & 15]) for x in cig]
 
 
+_RESCORE = None   # (score matrix, byte -> symbol), from the oracle, once
+
+
 def rescore_cigar(ref, read, cig, open_=7, ext=0):
     """Score of the alignment a CIGAR describes (s1 = ref window, s2 = read; leading D run is free)."""
-    M = oracle.matrix()
+    global _RESCORE
+    if _RESCORE is None:
+        _RESCORE = (oracle.matrix().astype(np.int64), np.array([oracle.lib().strk_o_encode(b) for b in range(256)], np.int64))
+    M, enc = _RESCORE
+    as_sym = lambda s: enc[np.frombuffer(s.encode("latin-1") if isinstance(s, str) else bytes(s), np.uint8)]   # noqa: E731
+    a, b = as_sym(ref), as_sym(read)
     i = j = 0
     score = 0
     first = True
     for ln, op in cigar_tuples(cig):
         if op in "=X":
-            for _ in range(ln):
-                score += int(M[oracle.encode(ref[i]), oracle.encode(read[j])])
-                i += 1
-                j += 1
+            if i + ln > len(a) or j + ln > len(b):
+                raise IndexError("the CIGAR runs past a sequence")
+            score += int(M[a[i:i + ln], b[j:j + ln]].sum())
+            i += ln
+            j += ln
         elif op == "I":
             score -= open_ + (ln - 1) * ext
             i += ln

@@ -772,7 +772,9 @@ def test_allele_call_checkers_accept_and_refuse_what_they_should(tmp_path):
 def test_realign_planner_accepts_refuses_and_lays_out_what_it_should(tmp_path):
     """Host build of tools/realign_asan.cpp (no HIP in strk_realign_plan.h): strk_realign's input check over every refusal, by
     its message, and the invariants of the plan (chunks, order, trace / edge / CIGAR ranges) over random valid calls and trace
-    budgets from 1 MiB up, arrays of exactly their length; the program counts its own failures and exits 0 without one."""
+    budgets from 1 MiB up, arrays of exactly their length; the gap-cost bound 2*open + (n1 - 2)*extend < 2^24 at the last
+    (open, extend, n1) taken and the first refused along each of the three, and at n1 = 2^20; the program counts its own
+    failures and exits 0 without one."""
     import shutil
     import subprocess
     if shutil.which("g++") is None:

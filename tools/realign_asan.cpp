@@ -137,6 +137,8 @@ int main() {
         Call c(n1, n2, cap, it % 3 == 0 ? 0 : (int64_t)(rng() % 100000));
         c.open = (int32_t)(rng() % 4097);
         c.ext = (int32_t)(rng() % (unsigned)(c.open + 1));
+        for (int64_t len : n1)   // a valid call: every pair's gap costs inside the number format
+            while (RP::gap_cost_reach(c.open, c.ext, len) >= RP::kGapCostLimit) c.ext /= 2;
         c.gap_pref = (int32_t)(rng() % 2);
         for (size_t budget : budgets) {
             RP::Plan plan;
@@ -188,6 +190,38 @@ int main() {
         if (c.plan((size_t)1 << 20, &plan, &why) != 0) failed("2^20 x 2^17 was refused");
         else check_plan(c, (size_t)1 << 20, plan, &chunks);
         ++calls;
+    }
+    {   // the gap-cost bound 2*open + (n1 - 2)*extend < 2^24: the last (open, extend, n1) taken and the first refused, along each
+        // of the three; the n1 = 2^20 corner; the pair is named, and the bound is looked at before the capacity
+        struct { int32_t open, ext; int64_t n1; bool ok; long long reach; } const cases[] = {
+            {4096, 4096, 4095, true, 0}, {4096, 4096, 4096, false, 16777216}, {4096, 4096, 4097, false, 16781312},
+            {4096, 4095, 4096, true, 0}, {4096, 4095, 4097, false, 16777217},
+            {4096, 4000, 4194, true, 0}, {4096, 4001, 4194, false, 16780384},
+            {3071, 2048, 8191, true, 0}, {3072, 2048, 8191, false, 16777216},
+            {4096, 1, 16769026, false, 16777216},   // (n1 beyond 2^20 is refused as too long first)
+            {4096, 15, 1 << 20, true, 0}, {16, 16, 1 << 20, false, 16777216}, {4096, 4096, 1 << 20, false, 4294967296ll},
+            {4096, 4096, 1, true, 0}, {4096, 4096, 2, true, 0}, {7, 0, 1 << 20, true, 0},
+        };
+        for (const auto& k : cases) {
+            Call c({10, k.n1}, {20, 1}, {24, -1});
+            c.open = k.open; c.ext = k.ext;
+            RP::Plan plan;
+            strk_groups::Message why;
+            const int rc = c.plan((size_t)1 << 20, &plan, &why);
+            char text[256];
+            if (k.n1 > (1 << 20)) snprintf(text, sizeof text, "pair 1: sequence too long (%lld x 1)", (long long)k.n1);
+            else if (k.ok) snprintf(text, sizeof text, "pair 1: negative CIGAR capacity");
+            else snprintf(text, sizeof text, "pair 1: gap costs beyond the number format (2*open + (n1 - 2)*extend = %lld, must be below 16777216)", k.reach);
+            refused(rc, why, strk_groups::kInvalid, text, "gap-cost bound");
+            if (k.ok != (RP::gap_cost_reach(k.open, k.ext, k.n1) < RP::kGapCostLimit)) failed("gap_cost_reach", k.open, k.ext);
+            if (k.ok) {   // and with a capacity it is planned
+                Call g({10, k.n1}, {20, 1}, {24, 0});
+                g.open = k.open; g.ext = k.ext;
+                if (g.plan((size_t)1 << 20, &plan, &why) != 0) failed("a pair inside the gap-cost bound was refused", k.open, k.ext);
+                else check_plan(g, (size_t)1 << 20, plan, &chunks);
+                ++calls;
+            }
+        }
     }
     printf("realign_asan: %ld valid calls, %ld chunks, %d refusals, %d failed\n", calls, chunks, g_refusals, g_failed);
     return g_failed ? 1 : 0;
