@@ -668,6 +668,42 @@ int strk_dbam_methyl(strk_dbam* d, int32_t n_items, const int64_t* rec_off, cons
 /* the size constants of k_dbam_methyl as built: bases per lane and pass, bases per pass, MM bytes per pass, ordinals per window */
 void strk_methyl_constants(int32_t* out4);
 
+/* ---- Which of the records fetched for a locus are used: one record per read name, skip flags, the cap -----------
+ * Stands where the reference builds a locus's segments (block_segments.get_segments_for_locus of strkit_rust_ext, not in its
+ * tree; call sites strkit/call/call_locus.py:1044-1057,1277-1285; --skip-supplementary / --skip-secondary; chimeric_in_region,
+ * types.py:35-37): the rule is this project's own statement (frontend/select.py is the readable one).
+ *
+ * Locus l owns items item_off[l] .. item_off[l + 1] (item_off ascends from 0), item i is the record at rec_off[i] of the stream:
+ * the overlapping mapped records in coordinate order, equal positions in file order.  A read name is the l_read_name - 1 bytes
+ * behind the fixed part of the record (none when l_read_name is 0); names are equal when lengths and all bytes are.
+ * rules (0 .. 7): 1 = skip supplementary, 2 = skip secondary, 4 = one record per name.  Per locus:
+ *   1. status of a name = OR over all items of that name at the locus of (flag & 0x800 ? 2 : 1), whatever becomes of them;
+ *   2. an item is flag-skipped with reason 1 when rules & 1 and flag & 0x800, else with reason 2 when rules & 2 and flag & 0x100;
+ *   3. with rules & 4 an item that is not flag-skipped is a duplicate (reason 3) when an earlier item of its name at the locus is
+ *      not flag-skipped (a flag-skipped first occurrence shadows nothing);
+ *   4. of the items without a reason the first max_reads (>= 1) are kept (reason 0), the others get reason 4.
+ * out_reason / out_status: per item (status = its name's); out_n_kept: per locus.  A kept read is chimeric in the region when
+ * its status is 3.  rules == 0 is the plain cap.  The same read at two loci is two questions.
+ * STRK_E_INVALID before any work: item_off not ascending from 0, max_reads < 1, rules outside 0 .. 7, a rec_off outside the
+ * stream; a record the parser refuses is STRK_E_INVALID with the item named, and is never read past. */
+#define STRK_SELECT_SKIP_SUPPLEMENTARY 1
+#define STRK_SELECT_SKIP_SECONDARY 2
+#define STRK_SELECT_UNIQUE 4
+#define STRK_SELECT_KEPT 0
+#define STRK_SELECT_SUPPLEMENTARY 1
+#define STRK_SELECT_SECONDARY 2
+#define STRK_SELECT_DUPLICATE 3
+#define STRK_SELECT_OVER_CAP 4
+int strk_select_reads(const uint8_t* buf, int64_t n_bytes, int32_t n_loci, const int64_t* item_off, const int64_t* rec_off,
+                      int32_t rules, int32_t max_reads, uint8_t* out_reason, uint8_t* out_status, int32_t* out_n_kept);
+/* The same over the file resident on the device (kernels k_select_small: one workgroup per locus, the name table in LDS, and
+ * k_select_large for loci beyond its class: the table in the object's workspace). */
+int strk_dbam_select_reads(strk_dbam* d, int32_t n_loci, const int64_t* item_off, const int64_t* rec_off, int32_t rules,
+                           int32_t max_reads, uint8_t* out_reason, uint8_t* out_status, int32_t* out_n_kept);
+/* the size constants of the kernels as built: items of a locus k_select_small takes, its table's slots, threads per workgroup,
+ * bytes per step of the name compare */
+void strk_select_constants(int32_t* out4);
+
 /* ---- Mendelian inheritance and the de novo test of a child / mother / father trio ------------------------------
  * Stands where `strkit mi` builds one MILocusData per trio locus (strkit/mi/result.py:100-175): respects_mi (:352-389,
  * decimal=False) and de_novo_test (:391-501), with scipy.stats.chi2_contingency(correction=False) and

@@ -61,6 +61,14 @@ def build_parser() -> argparse.ArgumentParser:
     c.add_argument("--use-methyl", "-m", action="store_true",
                    help="5-methyl CpG calls from the reads' MM / ML tags (GPU): m / mc per read, am / amc per called allele")
     c.add_argument("--methyl-threshold", type=int, default=127, help="--use-methyl: a site counts as methylated above this ML value (0 .. 255)")
+    c.add_argument("--skip-supplementary", "--skip-supp", dest="skip_supplementary", action="store_true",
+                   help="leave out supplementary alignment records (flag 0x800)")
+    c.add_argument("--skip-secondary", "--skip-sec", dest="skip_secondary", action="store_true",
+                   help="leave out secondary alignment records (flag 0x100)")
+    c.add_argument("--unique-reads", action="store_true",
+                   help="use a read name once per locus, by its first record that is not skipped (GPU with the device front end); "
+                        "with one of these three switches a kept read that has a supplementary and another record over the locus "
+                        "is marked chimeric_in_region, and --max-reads caps the records that are left")
     c.add_argument("--sample-id", default=None)
     c.add_argument("--processes", type=int, default=1)
     c.add_argument("--seed", type=int, default=None)
@@ -164,6 +172,7 @@ def main(argv=None) -> int:
                       **(dict(use_methyl=True, methyl_threshold=a.methyl_threshold) if a.use_methyl else {}),
                       **(dict(ploidy=a.ploidy) if a.ploidy is not None else {}),
                       **(dict(snv_phase_sets=True) if a.snv_phase_sets else {}),
+                      **{k: True for k in ("skip_supplementary", "skip_secondary", "unique_reads") if getattr(a, k)},
                       **(dict(call_alleles=True, consensus=a.consensus or bool(a.vcf), seed=a.seed, n_alleles=a.n_alleles)
                          if a.call_alleles else {}))
     if world > 1:

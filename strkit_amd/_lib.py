@@ -22,6 +22,8 @@ STRK_MI_TESTED, STRK_MI_OVERLAP, STRK_MI_EMPTY_PARENT, STRK_MI_EMPTY_CHILD = ran
 STRK_MI_FROM_NONE, STRK_MI_FROM_UNKNOWN, STRK_MI_FROM_MAT, STRK_MI_FROM_PAT, STRK_MI_FROM_BOTH = range(5)
 (STRK_METHYL_OK, STRK_METHYL_NOT_SPANNING, STRK_METHYL_NO_TAGS, STRK_METHYL_CLIPPED, STRK_METHYL_MALFORMED,
  STRK_METHYL_NO_SITES) = range(6)
+STRK_SELECT_SKIP_SUPPLEMENTARY, STRK_SELECT_SKIP_SECONDARY, STRK_SELECT_UNIQUE = 1, 2, 4
+STRK_SELECT_KEPT, STRK_SELECT_SUPPLEMENTARY, STRK_SELECT_SECONDARY, STRK_SELECT_DUPLICATE, STRK_SELECT_OVER_CAP = range(5)
 
 _u8p = C.POINTER(C.c_uint8)
 _i32p = C.POINTER(C.c_int32)
@@ -88,7 +90,8 @@ EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk
            "strk_consensus", "strk_consensus_dseqs", "strk_consensus_ws",
            "strk_phase_cells", "strk_useful_snvs", "strk_dbam_phase_cells", "strk_dbam_download_cells", "strk_dbam_useful_snvs",
            "strk_methyl", "strk_dbam_methyl", "strk_methyl_constants",
-           "strk_mi_trio", "strk_mi_trio_host", "strk_mi_constants")
+           "strk_mi_trio", "strk_mi_trio_host", "strk_mi_constants",
+           "strk_select_reads", "strk_dbam_select_reads", "strk_select_constants")
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -269,6 +272,12 @@ def load(build: bool = True):
                                         + [C.c_void_p] * 5)
         L.strk_mi_constants.restype = None
         L.strk_mi_constants.argtypes = [_i32p]
+        L.strk_select_reads.restype = C.c_int
+        L.strk_select_reads.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 3
+        L.strk_dbam_select_reads.restype = C.c_int
+        L.strk_dbam_select_reads.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 3
+        L.strk_select_constants.restype = None
+        L.strk_select_constants.argtypes = [_i32p]
         L.strk_device_mem.restype = C.c_int
         L.strk_device_mem.argtypes = [C.c_int, _i64p, _i64p]
         L.strk_realign_i16_flags.restype = C.c_int

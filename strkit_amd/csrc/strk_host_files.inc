@@ -144,6 +144,46 @@ int strk_extract_reads(const uint8_t* buf, int64_t n_bytes, int32_t n_items, con
     return 0;
 }
 
+// Which of the records fetched for each locus are used (the rule, the check and the host twin: strk_select.h).  Every record is
+// parsed before the rule runs; threads take runs of sixteen loci.
+int strk_select_reads(const uint8_t* buf, int64_t n_bytes, int32_t n_loci, const int64_t* item_off, const int64_t* rec_off, int32_t rules,
+                      int32_t max_reads, uint8_t* out_reason, uint8_t* out_status, int32_t* out_n_kept) {
+    const strk_sel::Input in{n_bytes, n_loci, item_off, rec_off, rules, max_reads};
+    strk_groups::Message msg;
+    if (strk_sel::check_input(in, &msg)) return fail(STRK_E_INVALID, "strk_select_reads: %s", msg.text);
+    if (n_loci == 0) return 0;
+    const int64_t n_items = item_off[n_loci];
+    if (!out_n_kept || (n_items > 0 && (!buf || !out_reason || !out_status))) return fail(STRK_E_INVALID, "strk_select_reads: NULL argument");
+    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)host_cpus(), 32, n_items / 4096}));
+    auto run = [&](auto&& body) {
+        std::vector<std::thread> th;
+        for (int t = 1; t < nt; ++t) th.emplace_back(body);
+        body();
+        for (auto& x : th) x.join();
+    };
+    std::atomic<int64_t> bad{INT64_MAX}, next_item{0};
+    run([&]() {
+        for (;;) {
+            const int64_t i0 = next_item.fetch_add(4096);
+            if (i0 >= n_items) return;
+            const int64_t b = strk_sel::host_first_bad(buf, in, i0, std::min(n_items, i0 + 4096));
+            int64_t cur = bad.load();
+            while (b >= 0 && b < cur && !bad.compare_exchange_weak(cur, b)) {}
+        }
+    });
+    if (bad.load() != INT64_MAX) return fail(STRK_E_INVALID, "strk_select_reads: item %lld: malformed BAM record", (long long)bad.load());
+    std::atomic<int64_t> next_locus{0};
+    run([&]() {
+        strk_sel::HostTable table;
+        for (;;) {
+            const int64_t l0 = next_locus.fetch_add(16);
+            if (l0 >= n_loci) return;
+            for (int32_t l = (int32_t)l0; l < std::min<int64_t>(n_loci, l0 + 16); ++l) strk_sel::host_locus(buf, in, l, table, out_reason, out_status, out_n_kept);
+        }
+    });
+    return 0;
+}
+
 // Inflates `blocks` of `comp` into `out` on up to n_threads threads (<= 0: the CPUs of this process; 32 at most) that take
 // sixteen blocks at a time; false when a block is corrupt.  thread_per_16: at most one thread per sixteen blocks (a range of a
 // few blocks is not worth starting threads for).

@@ -21,6 +21,7 @@ from .native import extract_raw_slices, extract_reads, realign_cigar_to_read_ali
 from .options import VCF_ANCHOR_SIZE, CallOptions
 from .output import block_read_weights, read_weights
 from .phase_block import native_block_phase, phase_row, python_block_phase
+from .select import CHIMERIC, NO_CAP, rules_of, select_reads, select_segments
 
 
 def _locus_dict(locus: Locus) -> dict:
@@ -83,6 +84,9 @@ def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data
     flank_size = opts.flank_size
     want_raw = opts.consensus or opts.count_kmers != "none"
     use_methyl = getattr(opts, "use_methyl", False)
+    rules = rules_of(opts)            # read selection (select.py); 0: the first max_reads records, as ever
+    chimeric: list[set[int]] = []     # per prepared locus: id() of its kept segments that are chimeric in ITS region (the same
+                                      # segment object serves every locus it overlaps: the mark is the locus's, not the segment's)
     results: list[dict] = []
     prepared = []                     # (locus, ref data, [[segment, the pairs of its new alignment or None] ...])
     realign_jobs = []                 # (locus, ref data, entry) of the soft-clipped reads
@@ -90,7 +94,15 @@ def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data
         if rd is None:
             results.append(_locus_dict(locus))    # SkipLocus: locus fields + empty call (call_locus.py:1032-1036)
             continue
-        segs = bam.fetch(locus.contig, locus.left_flank_coord, locus.right_flank_coord)[:opts.max_reads]
+        segs = bam.fetch(locus.contig, locus.left_flank_coord, locus.right_flank_coord)
+        if rules:
+            t_a = time.perf_counter()
+            segs, seg_status = select_segments(segs, rules, opts.max_reads)
+            chimeric.append({id(seg) for seg, st_ in zip(segs, seg_status) if st_ == CHIMERIC})
+            tm["select_s"] = tm.get("select_s", 0.0) + time.perf_counter() - t_a
+        else:
+            segs = segs[:opts.max_reads]
+            chimeric.append(set())
         entries = [[seg, None] for seg in segs]
         if opts.realign:
             realign_jobs += [(locus, rd, e) for e in entries if e[0].soft_clip_overlaps_locus(locus)]
@@ -151,7 +163,8 @@ def _call_block_python(block, bam: BamFile, opts: CallOptions, ctx, tm, ref_data
             name, strand, realigned, sl, seg, rc = meta[li][r - r0]
             sc = float(flt["sc"][r])
             reads[name] = {"s": strand, "cn": int(res["cn"][r]), "w": float(ws[r - r0]),
-                           "sc": None if np.isnan(sc) else sc, "sl": sl, **({"realn": True} if realigned else {})}
+                           "sc": None if np.isnan(sc) else sc, "sl": sl, **({"realn": True} if realigned else {}),
+                           **({"chimeric_in_region": True} if id(seg) in chimeric[li] else {})}
             if use_methyl:     # the rule itself (methyl.py) on the tract extraction cut
                 a, b, c, d = rc.left_flank_start, rc.left_flank_end, rc.right_flank_start, rc.right_flank_end
                 q = (b, c) if 0 <= a <= b <= c <= d and c <= seg.length else (None, None)
@@ -215,6 +228,7 @@ class BlockState:
     cons: dict | None = None
     kmers: dict | None = None
     methyl: dict | None = None    # status / known / mc per kept read (use_methyl)
+    chimeric: np.ndarray | None = None     # per kept read: chimeric in the region (read selection on)
 
 
 def _call_block_native(block, bam, opts: CallOptions, ctx, tm, ref_data, phase_run=None):
@@ -238,12 +252,20 @@ def _block_device_stage(live, bam, opts: CallOptions, ctx, tm, phase_run=None) -
     rfc = np.array([l.right_flank_coord for l, _ in live], np.int64)
     lca = np.array([rd["left_coord_adj"] for _, rd in live], np.int64)
     rca = np.array([rd["right_coord_adj"] for _, rd in live], np.int64)
+    rules = rules_of(opts)                   # read selection (select.py): the fetch is then made without a cap
+    fetch_cap = NO_CAP if rules else opts.max_reads
     if len({l.contig for l, _ in live}) == 1:
-        rec, counts = bam.fetch_many(live[0][0].contig, lfc, rfc, opts.max_reads)
+        rec, counts = bam.fetch_many(live[0][0].contig, lfc, rfc, fetch_cap)
     else:                                    # a hand-made block that mixes contigs
-        parts = [bam.fetch_indices(l.contig, int(a), int(b))[:opts.max_reads] for (l, _), a, b in zip(live, lfc, rfc)]
+        parts = [bam.fetch_indices(l.contig, int(a), int(b))[:fetch_cap] for (l, _), a, b in zip(live, lfc, rfc)]
         rec = np.concatenate(parts) if parts else np.zeros(0, np.int64)
         counts = np.array([len(x) for x in parts], np.int64)
+    item_status = None
+    if rules:                                # from here on nothing sees a record that is left out
+        t_s = time.perf_counter()
+        rec, counts, item_status = select_reads(bam, rec, counts, rules, opts.max_reads)
+        tm["select_s"] = tm.get("select_s", 0.0) + time.perf_counter() - t_s
+        t_a += time.perf_counter() - t_s     # (not extract_s's)
     item_locus = np.repeat(np.arange(len(live)), counts)
     coords = np.stack((lfc, lca, rca, rfc), axis=1)[item_locus]
     tm["extract_s"] += time.perf_counter() - t_a
@@ -294,6 +316,8 @@ def _block_device_stage(live, bam, opts: CallOptions, ctx, tm, phase_run=None) -
                     minus=(bam.flag[kept_rec] & 16) != 0, cn=res["cn"], sc=flt["sc"], ntr=batch.ntr, alt=alt,
                     weigh=lambda: block_read_weights(counts, item_locus, lens_all, read_locus[kept],
                                                      batch.nfl[kept].astype(np.int64) + batch.ntr[kept] + batch.nfr[kept]))
+    if item_status is not None:
+        st.chimeric = item_status[ok_items[kept]] == CHIMERIC
     tm["names_s"] = tm.get("names_s", 0.0) + time.perf_counter() - t_a
     if getattr(opts, "use_methyl", False):     # one library call over the kept items: the records are read where they lie
         t_a = time.perf_counter()
@@ -331,6 +355,9 @@ def _block_report_stage(st: BlockState, opts: CallOptions, tm):
         for k, it in enumerate(st.ok_items[kept].tolist()):
             if it in alt:
                 recs[k]["realn"] = True
+    if st.chimeric is not None:
+        for k in np.nonzero(st.chimeric)[0].tolist():
+            recs[k]["chimeric_in_region"] = True
     if st.methyl is not None:
         for r, s_, k_, m_ in zip(recs, st.methyl["status"].tolist(), st.methyl["known"].tolist(), st.methyl["mc"].tolist()):
             r["m"], r["mc"] = record_values(s_, k_, m_)

@@ -21,14 +21,14 @@ from .fasta import Fasta
 from .gather import _distributed, call_blocks_sharded, deal_locus_blocks
 from .loci import Locus, load_loci, resolve_contig
 from .native import DeviceBam, IndexedBam, NativeBam
-from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, MethylCallOptions, PhasedCallOptions, PhaseSetCallOptions, PloidyCallOptions, PoaCallOptions,
+from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, MethylCallOptions, PhasedCallOptions, PhaseSetCallOptions, PloidyCallOptions, PoaCallOptions, ReadSelectionCallOptions,
                       allele_counts, phased, report_parameters, with_keywords)
 from .phase_block import PhaseRun
 from .reader import open_path
 from .refside import get_loci_with_ref_data, get_locus_with_ref_data, ref_side_of_blocks
 
 # (what moved to the other modules is still offered here under the names it had)
-__all__ = ["CallOptions", "PoaCallOptions", "PhasedCallOptions", "MethylCallOptions", "PloidyCallOptions", "PhaseSetCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
+__all__ = ["CallOptions", "PoaCallOptions", "PhasedCallOptions", "MethylCallOptions", "PloidyCallOptions", "PhaseSetCallOptions", "ReadSelectionCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
 
 
 def ploidy_blocks(blocks, opts):

@@ -55,7 +55,7 @@ _NAME_BYTES = 64          # fixed width of the read-name field of a gathered per
 def _encode_rows(rows: list[dict], errors: list[dict]):
     """Per-locus rows -> fixed-size records: loci int64[n, 6] = (locus_index, status, ref_cn, start_adj, end_adj, n reads)
     with status 0 called / 1 skipped (no reference data) / 2 failed; reads int64[m, 6] = (locus_index, cn, sl, flags,
-    sc as float64 bits, w as float64 bits) with flags bit 0 reverse strand, bit 1 realigned, bit 2 sc is None;
+    sc as float64 bits, w as float64 bits) with flags bit 0 reverse strand, bit 1 realigned, bit 2 sc is None, bit 3 chimeric in the region;
     names uint8[m, W]."""
     n_reads = sum(len(r.get("reads") or {}) for r in rows)
     width = max([_NAME_BYTES] + [len(nm.encode()) for r in rows for nm in (r.get("reads") or {})])
@@ -71,7 +71,7 @@ def _encode_rows(rows: list[dict], errors: list[dict]):
             b = nm.encode()
             names[k, :len(b)] = np.frombuffer(b, np.uint8)
             sc = x.get("sc")
-            reads[k] = (r["locus_index"], x["cn"], x.get("sl", 0), (x["s"] == "-") | (2 if x.get("realn") else 0) | (4 if sc is None else 0),
+            reads[k] = (r["locus_index"], x["cn"], x.get("sl", 0), (x["s"] == "-") | (2 if x.get("realn") else 0) | (4 if sc is None else 0) | (8 if x.get("chimeric_in_region") else 0),
                         np.float64(0.0 if sc is None else sc).view(np.int64), np.float64(x["w"]).view(np.int64))
             k += 1
     for i, e in enumerate(errors):
@@ -101,7 +101,7 @@ def _decode_rows(loci_by_index: dict, ref: Fasta, respect_ref: bool, loci_t: np.
             nm = names_t[k].tobytes().rstrip(b"\0").decode()
             reads[nm] = {"s": "-" if flags & 1 else "+", "cn": cn, "w": float(np.int64(w_bits).view(np.float64)),
                          "sc": None if flags & 4 else float(np.int64(sc_bits).view(np.float64)), "sl": sl,
-                         **({"realn": True} if flags & 2 else {})}
+                         **({"realn": True} if flags & 2 else {}), **({"chimeric_in_region": True} if flags & 8 else {})}
         rd = {"ref_cn": ref_cn, "left_coord_adj": s_adj, "right_coord_adj": e_adj,
               "ref_seq": ref.fetch(locus.contig, s_adj, e_adj),
               "ref_left_flank_seq": ref.fetch(locus.contig, max(0, s_adj - VCF_ANCHOR_SIZE), s_adj)}

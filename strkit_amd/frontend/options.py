@@ -171,6 +171,28 @@ class PhaseSetCallOptions(PloidyCallOptions):
 PHASE_SET_OPTION_NAMES = ("snv_phase_sets",)
 
 
+@dataclass
+class ReadSelectionCallOptions(PhaseSetCallOptions):
+    """PhaseSetCallOptions plus which of the records fetched for a locus are used (frontend/select.py).
+    `skip_supplementary` / `skip_secondary`: records with flag 0x800 / 0x100 are left out (`strkit call --skip-supplementary /
+    --skip-secondary`).  `unique_reads`: a read name is used once per locus, by its first record that is not left out (the
+    reference always does this; here it is a switch, off by default, so that every earlier report keeps its bytes).  With one of
+    them on, a kept read that has a supplementary and a non-supplementary record over the locus gets `chimeric_in_region`, and
+    `max_reads` caps the records that are left, not the records fetched.  A type of its own for the reason PoaCallOptions gives."""
+    skip_supplementary: bool = False
+    skip_secondary: bool = False
+    unique_reads: bool = False
+
+    def validate(self) -> None:
+        super().validate()
+        for name in READ_SELECTION_OPTION_NAMES:
+            if not isinstance(getattr(self, name), bool):
+                raise ValueError(f"{name} must be True or False: got {getattr(self, name)!r}")
+
+
+READ_SELECTION_OPTION_NAMES = ("skip_supplementary", "skip_secondary", "unique_reads")
+
+
 def allele_counts(opts):
     """What genotype.n_alleles_of takes for a run: its ploidy configuration where one is set, else its n_alleles."""
     ploidy = getattr(opts, "ploidy", None)
@@ -188,9 +210,11 @@ def phased(opts) -> bool:
 def with_keywords(opts: CallOptions | None, **option_keywords) -> CallOptions:
     """`opts` (or the defaults) with the options given by name replaced: dataclasses.replace, after widening a plain
     CallOptions to PoaCallOptions when one of POA_OPTION_NAMES is among them, to PhasedCallOptions for PHASE_OPTION_NAMES, to
-    MethylCallOptions for METHYL_OPTION_NAMES, to PloidyCallOptions for PLOIDY_OPTION_NAMES, and to PhaseSetCallOptions for
-    PHASE_SET_OPTION_NAMES.  An unknown name is a TypeError."""
+    MethylCallOptions for METHYL_OPTION_NAMES, to PloidyCallOptions for PLOIDY_OPTION_NAMES, to PhaseSetCallOptions for
+    PHASE_SET_OPTION_NAMES, and to ReadSelectionCallOptions for READ_SELECTION_OPTION_NAMES.  An unknown name is a TypeError."""
     opts = opts or CallOptions()
+    if not isinstance(opts, ReadSelectionCallOptions) and any(k in option_keywords for k in READ_SELECTION_OPTION_NAMES):
+        opts = ReadSelectionCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, PhaseSetCallOptions) and any(k in option_keywords for k in PHASE_SET_OPTION_NAMES):
         opts = PhaseSetCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, PloidyCallOptions) and any(k in option_keywords for k in PLOIDY_OPTION_NAMES):
@@ -226,4 +250,5 @@ def report_parameters(opts: CallOptions, processes: int) -> dict:
             **({"use_methyl": True} if getattr(opts, "use_methyl", False) else {}),
             **({"methyl_threshold": opts.methyl_threshold} if getattr(opts, "use_methyl", False) and opts.methyl_threshold != 127 else {}),
             **({"ploidy": opts.ploidy} if getattr(opts, "ploidy", None) is not None else {}),
-            **({"snv_phase_sets": True} if getattr(opts, "snv_phase_sets", False) else {})}
+            **({"snv_phase_sets": True} if getattr(opts, "snv_phase_sets", False) else {}),
+            **{name: True for name in READ_SELECTION_OPTION_NAMES if getattr(opts, name, False)}}

@@ -24,6 +24,12 @@ oracle against it (`-m "not gpu"`) and the HIP library against it (`-m gpu`), an
 it, which combinations of the open switches (end-gap flags x tie rule x search-range schedule) do.  Without the file those
 tests skip; parity stays "unpinned" until it exists.  Nothing of STRkit's source is read or copied by this script: it only
 imports the installed package and records what its functions return.
+
+Not made here: read selection (one record per read name, the skip flags, chimeric_in_region).  What would
+pin it is `block_segments.get_segments_for_locus(locus)` of strkit_rust_ext's block reader (the call of
+strkit/call/call_locus.py:1048, the block made at call_sample.py:86-87) on an alignment file such as the one
+strkit_amd/frontend/synth_chimeric.py writes, with and without --skip-supplementary / --skip-secondary: the names of the
+segments it returns per locus, in order, and which of them it marks chimeric.
 """
 from __future__ import annotations
 
