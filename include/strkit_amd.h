@@ -171,6 +171,16 @@ int32_t strk_plan_scope(int32_t n_reads);
  * read indices into out_reads (host memory); returns the length of the list (>= 0) or an error.  For tests of the list
  * order; valid until the next call on ctx. */
 int strk_band_list(strk_ctx* ctx, int32_t band_class, int32_t* out_reads, int32_t cap);
+/* Test support for the exact scoring path.  strk_classify: the list the planning kernel gives an item of these lengths, candidate
+ * window [lo, lo + n) and mode: 0..16 the fast classes, 17 the column-tiled kernel, 18 the generic kernel (the device's own
+ * function, compiled for the host).  strk_score_constants: up to `cap` of {kTableMax, kFastFlankMax, kMotifMax, kRowSlack,
+ * kNumClasses, kLongTile, kLongMaxTiles, kLongFlankMax, kStairMinG, the 17 class capacities, the 17 lanes-per-read values}.
+ * strk_class_counts: the lengths of those 19 lists in ctx's last finished scoring call, from the counters that call downloaded
+ * (an item the fast or the tiled kernel hands over to the generic one is counted in both lists); up to `cap` of them into out,
+ * returns 19 (0 while a submitted call is pending; all lists empty before the first call) or an error. */
+int32_t strk_classify(int32_t nfl, int32_t ntr, int32_t nfr, int32_t m, int32_t lo, int32_t n, int32_t force_generic, int32_t ref_mode);
+void strk_score_constants(int32_t* out, int32_t cap);
+int strk_class_counts(strk_ctx* ctx, int32_t* out, int32_t cap);
 /* Forget what the library has learnt about the current sample (the default candidate-window level per motif-length bucket,
  * process-wide): call it when a process moves on to ANOTHER sample (the reference runs one sample per process,
  * call_sample.py:265).  Per-context state (band probation, grid history) goes with strk_destroy. */

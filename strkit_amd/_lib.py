@@ -91,7 +91,8 @@ EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk
            "strk_phase_cells", "strk_useful_snvs", "strk_dbam_phase_cells", "strk_dbam_download_cells", "strk_dbam_useful_snvs",
            "strk_methyl", "strk_dbam_methyl", "strk_methyl_constants",
            "strk_mi_trio", "strk_mi_trio_host", "strk_mi_constants",
-           "strk_select_reads", "strk_dbam_select_reads", "strk_select_constants")
+           "strk_select_reads", "strk_dbam_select_reads", "strk_select_constants",
+           "strk_classify", "strk_score_constants", "strk_class_counts")
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -136,6 +137,12 @@ def load(build: bool = True):
         L.strk_plan_scope.argtypes = [C.c_int32]
         L.strk_band_list.restype = C.c_int
         L.strk_band_list.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32]
+        L.strk_classify.restype = C.c_int32
+        L.strk_classify.argtypes = [C.c_int32] * 8
+        L.strk_score_constants.restype = None
+        L.strk_score_constants.argtypes = [_i32p, C.c_int32]
+        L.strk_class_counts.restype = C.c_int
+        L.strk_class_counts.argtypes = [C.c_void_p, _i32p, C.c_int32]
         L.strk_adaptive_reset.restype = None
         L.strk_adaptive_reset.argtypes = []
         L.strk_repeat_count.restype = C.c_int

@@ -14,7 +14,8 @@ from . import _lib
 from .repeat_count_params import RepeatCountParams, default_read_rc_params
 from .synth import LocusBatch
 
-__all__ = ["count_loci", "score_table", "score_ref_table", "make_params", "batch_struct", "calc_adj_score", "filter_reads"]
+__all__ = ["count_loci", "score_table", "score_ref_table", "make_params", "batch_struct", "calc_adj_score", "filter_reads",
+           "score_constants", "classify", "class_counts"]
 
 
 def make_params(rc_params: RepeatCountParams | None = None, feedback: bool = True, window: int = 0,
@@ -119,6 +120,36 @@ def score_ref_table(b: LocusBatch, lo, n, force_generic: bool = False, ctx: _lib
                                                 _ptr(sc), _ptr(eq), C.byref(st)))
     del keep
     return [(sc[off[r]:off[r + 1]], eq[off[r]:off[r + 1]]) for r in range(b.n_reads)]
+
+
+def score_constants() -> dict:
+    """The size constants of the exact scoring kernels as built (strk_score_constants): the names of strk_kernels.h, with
+    `caps` and `lanes` the capacity and the lanes per read of each fast class."""
+    out = np.zeros(9 + 2 * 64, np.int32)
+    _lib.load().strk_score_constants(out.ctypes.data_as(_lib._i32p), out.size)
+    names = ("kTableMax", "kFastFlankMax", "kMotifMax", "kRowSlack", "kNumClasses", "kLongTile", "kLongMaxTiles", "kLongFlankMax",
+             "kStairMinG")
+    c = {k: int(v) for k, v in zip(names, out)}
+    nc = c["kNumClasses"]
+    c["caps"] = [int(v) for v in out[9:9 + nc]]
+    c["lanes"] = [int(v) for v in out[9 + nc:9 + 2 * nc]]
+    return c
+
+
+def classify(nfl: int, ntr: int, nfr: int, m: int, lo: int, n: int, force_generic: bool = False, ref_mode: bool = False) -> int:
+    """The list the planning kernel gives such an item (strk_classify): 0 .. kNumClasses - 1 the fast classes, then the
+    column-tiled kernel, then the generic kernel."""
+    return int(_lib.load().strk_classify(nfl, ntr, nfr, m, lo, n, int(force_generic), int(ref_mode)))
+
+
+def class_counts(ctx: _lib.Context | None = None) -> np.ndarray:
+    """Lengths of the class lists (fast classes, tiled, generic) of the context's last scoring call (strk_class_counts)."""
+    ctx = ctx or _lib.default_context()
+    out = np.zeros(64, np.int32)
+    k = _lib.load().strk_class_counts(ctx.handle, out.ctypes.data_as(_lib._i32p), out.size)
+    if k < 0:
+        raise _lib.StrkError(k, "strk_class_counts")
+    return out[:k].copy()
 
 
 # ---- what the caller does with the four integers (strkit/call/call_locus.py:1172,1222-1252,1279-1283) ----------

@@ -873,6 +873,7 @@ int score_table_impl(strk_ctx* ctx, const strk_batch* batch, const int32_t* lo, 
         if (hipEventElapsedTime(&ms, ctx->ev[kEvPre], ctx->ev[kEvExact]) == hipSuccess) stats->dp_kernel_ms = ms;
         stats->n_dp_launches = 2;
         stats->n_fallback = ctx->h_counters.cnt(kCntClass0 + kGenericClass);
+        stats->n_long_reads = ctx->h_counters.cnt(kCntClass0 + kLongClass);
         stats->dp_cells = (int64_t)ctx->h_counters.cells();
     }
     return 0;
@@ -918,6 +919,21 @@ int strk_band_list(strk_ctx* c, int32_t band_class, int32_t* out_reads, int32_t 
         if (hipMemcpy2D(out_reads, sizeof(int32_t), src, 2 * sizeof(int32_t), sizeof(int32_t), (size_t)k, hipMemcpyDeviceToHost) != hipSuccess) return STRK_E_DEVICE;
     }
     return n;
+}
+
+int32_t strk_classify(int32_t nfl, int32_t ntr, int32_t nfr, int32_t m, int32_t lo, int32_t n, int32_t force_generic, int32_t ref_mode) {
+    return classify(nfl, ntr, nfr, m, lo, n, force_generic, ref_mode);
+}
+void strk_score_constants(int32_t* out, int32_t cap) {
+    int32_t v[9 + 2 * kNumClasses] = {kTableMax, kFastFlankMax, kMotifMax, kRowSlack, kNumClasses, kLongTile, kLongMaxTiles, kLongFlankMax, kStairMinG};
+    for (int k = 0; k < kNumClasses; ++k) { v[9 + k] = class_cap(k); v[9 + kNumClasses + k] = class_G(k); }
+    for (int k = 0; k < cap && k < 9 + 2 * kNumClasses; ++k) out[k] = v[k];
+}
+int strk_class_counts(strk_ctx* c, int32_t* out, int32_t cap) {
+    if (!c || cap < 0 || (cap > 0 && !out)) return STRK_E_INVALID;
+    if (!c->h_counters.mem.p || c->pending) return 0;
+    for (int k = 0; k < cap && k < kNumClasses + 2; ++k) out[k] = c->h_counters.cnt(kCntClass0 + k);
+    return kNumClasses + 2;
 }
 
 void strk_adaptive_reset(void) { g_window.reset(); }
@@ -974,6 +990,7 @@ int strk_init(int device, strk_ctx** out) {
     hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(strk::c_mat), t.mat, sizeof t.mat);
     if (e == hipSuccess) e = hipMemcpyToSymbol(HIP_SYMBOL(strk::c_enc), t.enc, sizeof t.enc);
     if (e == hipSuccess) e = c->h_counters.mem.alloc(kCountersBytes);
+    if (e == hipSuccess) memset(c->h_counters.mem.p, 0, kCountersBytes);   // (strk_class_counts before the first call: all lists empty)
     for (int i = 0; i < kNumEvents && e == hipSuccess; ++i) e = hipEventCreate(&c->ev[i].h);
     if (e != hipSuccess) {
         strk_destroy(c);

@@ -159,7 +159,7 @@ constexpr int kErrLongSlot = 16;  // a window too long for a k_dp_long scratch s
 // ---------------------------------------------------------------------------------------------
 // Plan: per read -> locus id, candidate window, table slot, kernel class.
 // ---------------------------------------------------------------------------------------------
-__device__ inline int classify(int nfl, int ntr, int nfr, int m, int lo, int n, int force_generic, int ref_mode) {
+__host__ __device__ inline int classify(int nfl, int ntr, int nfr, int m, int lo, int n, int force_generic, int ref_mode) {
     const long long ndb = (long long)nfl + ntr + nfr;
     const long long rows = (long long)nfl + (long long)(lo + n - 1) * m;
     if (force_generic || nfl < 1 || (nfr < 1 && !ref_mode) || n > kTableMax || m > kMotifMax) return kGenericClass;
