@@ -678,6 +678,37 @@ int strk_dbam_methyl(strk_dbam* d, int32_t n_items, const int64_t* rec_off, cons
 /* the size constants of k_dbam_methyl as built: bases per lane and pass, bases per pass, MM bytes per pass, ordinals per window */
 void strk_methyl_constants(int32_t* out4);
 
+/* ---- Candidate SNVs out of VCF text ----------------------------------------------------------------------------
+ * Stands where the reference asks its tabix-indexed SNV catalog for the candidates of one block of loci
+ * (STRkitVCFReader.get_candidate_snvs of strkit_rust_ext, not in its tree; call site strkit/call/call_sample.py:124).  The rule
+ * is frontend/snv_vcf.py::read_snv_vcf's, restated for a byte parser:
+ *   lines end at '\n' (trailing '\r's are stripped; a lone '\r' ends nothing); lines that begin with '#' or have fewer than
+ *   five tab-separated fields are skipped; a record counts when, after ASCII upper-casing, REF is one byte of ACGTN and ALT,
+ *   split at ',', is non-empty with every piece one byte of ACGTN.  Only on such a line POS is read: 1 to 18 decimal digits,
+ *   otherwise the call fails with STRK_E_INVALID and names the line's byte offset.  A record is reported when its CHROM field
+ *   equals `contig` byte for byte and beg <= POS - 1 < end; of several such records at one position the first in the text
+ *   stays; a reported position below the one before it (or below prev_pos) fails: not coordinate-sorted.
+ * The text is buf[start, n_bytes), `start` a line start.  final != 0: the text ends its file, so that a last line without
+ * '\n' is complete; otherwise it is left for the next piece: *end_off = the offset just past the last complete line.
+ * prev_pos = the last position the previous piece reported (-1: none), contig_seen != 0: a record of the contig was seen before.
+ * Outputs in text order: pos (0-based), ref (upper case), id_off [n + 1] into ids (the ID column; empty where it is ".").
+ * *id_bytes = the ID bytes of all records; ids == NULL: none are written (size query).  *past = 1 when a record of the contig at
+ * or beyond `end`, or one of another contig after one of this contig, was seen.  Returns the number of records n; the arrays
+ * (capacity cap) are filled when n <= cap.  STRK_E_NOMEM when ids is given and ids_cap < *id_bytes. */
+int64_t strk_vcf_snvs(const uint8_t* buf, int64_t n_bytes, int64_t start, const char* contig, int64_t beg, int64_t end, int32_t final,
+                      int64_t prev_pos, int32_t contig_seen, int64_t cap, int64_t* pos, uint8_t* ref, int64_t* id_off, uint8_t* ids,
+                      int64_t ids_cap, int64_t* id_bytes, int64_t* end_off, int32_t* past);
+/* The same over the stream of a strk_dbam object (a BGZF-compressed VCF inflated by strk_dbam_inflate*), `start` an offset into
+ * it, checked against the stream's size before any launch.  Kernels: k_vcf_count, k_vcf_scan, k_vcf_starts (the lines),
+ * k_vcf_parse (one lane per line), k_vcf_compact (the kept lines and their ID bytes); one record per position and sortedness are
+ * applied on the host to what comes back.  tile_bytes: the text bytes one wave walks in the line passes, a multiple of 256
+ * (0: the default); no output depends on it. */
+int64_t strk_dbam_vcf_snvs(strk_dbam* d, int64_t start, const char* contig, int64_t beg, int64_t end, int32_t final, int64_t prev_pos,
+                           int32_t contig_seen, int32_t tile_bytes, int64_t cap, int64_t* pos, uint8_t* ref, int64_t* id_off,
+                           uint8_t* ids, int64_t ids_cap, int64_t* id_bytes, int64_t* end_off, int32_t* past);
+/* the size constants of the kernels as built: default tile bytes, bytes per step, lines per wave */
+void strk_vcf_constants(int32_t* out3);
+
 /* ---- Which of the records fetched for a locus are used: one record per read name, skip flags, the cap -----------
  * Stands where the reference builds a locus's segments (block_segments.get_segments_for_locus of strkit_rust_ext, not in its
  * tree; call sites strkit/call/call_locus.py:1044-1057,1277-1285; --skip-supplementary / --skip-secondary; chimeric_in_region,

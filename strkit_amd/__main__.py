@@ -52,7 +52,8 @@ def build_parser() -> argparse.ArgumentParser:
     # component), --processes sizes the locus blocks as the reference does (loci.py:193)
     c.add_argument("--use-hp", action="store_true", help="group reads by their HP / PS tags where a locus has enough tagged reads (needs --call-alleles)")
     c.add_argument("--incorporate-snvs", "--snv", "-v", dest="incorporate_snvs", default=None, metavar="PATH",
-                   help="VCF (plain or gzip) of candidate SNVs: reads are grouped by the bases they carry at them (needs --call-alleles)")
+                   help="VCF (plain or gzip; BGZF with a PATH.tbi next to it is read region by region) of candidate SNVs: reads are grouped by "
+                        "the bases they carry at them (needs --call-alleles)")
     c.add_argument("--snv-phase-sets", action="store_true",
                    help="--incorporate-snvs: loci that share heterozygous SNVs get one phase set (PS, '|' genotypes), and the "
                         "called SNVs are written to the VCF as records of their own")

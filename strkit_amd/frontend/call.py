@@ -155,6 +155,15 @@ def _collector_paused():
             gc.enable()
 
 
+@contextmanager
+def _phase_run_closed(phase_run, tm):
+    try:
+        yield
+    finally:
+        if phase_run is not None:
+            phase_run.close(tm)
+
+
 def _one_contig_blocks(block):
     """A block as the loader builds it stays on one contig (loci.py:277-280); a hand-made one is split."""
     return [list(run) for _, run in itertools.groupby(block, key=lambda locus: locus.contig)]
@@ -212,7 +221,8 @@ def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = Non
     opts = opts or CallOptions()
     opts.validate()
     blocks, _ = ploidy_blocks(blocks, opts)
-    phase_run = PhaseRun(opts) if phased(opts) else None     # the candidate SNVs and the renumbering of the phase sets: one per run
+    # the candidate SNVs and the renumbering of the phase sets: one per run (an indexed SNV file is read where the alignments are)
+    phase_run = PhaseRun(opts, device=getattr(bam, "device", 0) if isinstance(bam, DeviceBam) else None) if phased(opts) else None
     sets = phase_run.sets if phase_run is not None else None      # (snv_phase_sets: phase sets across loci, phase_sets.py)
     ctx = ctx or _lib.default_context()
     run_block = _call_block_native if isinstance(bam, (NativeBam, IndexedBam, DeviceBam)) else _call_block_python
@@ -252,7 +262,8 @@ def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = Non
         feed = ((b, bam) for block in blocks for b in _one_contig_blocks(block))
     else:
         feed = ((block, bam) for block in blocks)       # a reader that holds every record
-    with closing(feed):             # a feed is a generator or has a close() of its own (the prefetcher's pool)
+    # a feed is a generator or has a close() of its own (the prefetcher's pool); the phase run gives its SNV reader back
+    with closing(feed), _phase_run_closed(phase_run, tm):
         if ref_cache is None:       # reference side of ALL loci first (unless the caller has it already)
             ref_cache = ref_side_of_blocks(blocks, ref, opts, ctx, tm)
         with _collector_paused():

@@ -365,6 +365,7 @@ class DeviceBam(_Records):
 
     def __init__(self, path: str, index: str | None = None, device: int = 0, span_bytes: int | None = None):
         self.path = path
+        self.device = int(device)
         L = _lib.load()
         h = C.c_void_p()
         _lib.check(L.strk_dbam_open(int(device), C.byref(h)))

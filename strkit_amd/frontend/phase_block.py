@@ -15,7 +15,7 @@ from . import phase_inputs as pi
 from .genotype import n_alleles_of
 from .options import allele_counts
 from .phase_sets import PhaseSets
-from .snv_vcf import read_snv_vcf
+from .snv_vcf import IndexedSnvVcf, open_snv_candidates
 
 MAX_CELLS = (512 << 20) // 2      # cells (a base and a quality byte each) of one phase_cells call: DESIGN.md §9's 512 MB
 
@@ -23,15 +23,29 @@ __all__ = ["PhaseRun", "BlockPhase", "native_block_phase", "python_block_phase",
 
 
 class PhaseRun:
-    """What one run keeps across its blocks: the candidate SNVs (read once), the renumbering of the phase sets and, with
-    snv_phase_sets, the phase sets of the SNV calls (`sets`, a phase_sets.PhaseSets; the renumbering then counts with it)."""
+    """What one run keeps across its blocks: the candidate SNVs (a file with a tabix index: opened, then asked block by block,
+    on the device when `device` is given, as the alignment file's reader is; any other file: read once), the renumbering of the
+    phase sets and, with snv_phase_sets, the phase sets of the SNV calls (`sets`, a phase_sets.PhaseSets; the renumbering then
+    counts with it)."""
 
-    def __init__(self, opts):
-        self.snvs = read_snv_vcf(opts.snv_vcf) if opts.snv_vcf else None
+    def __init__(self, opts, device: int | None = None):
+        t0 = time.perf_counter()
+        self.snvs = (open_snv_candidates(opts.snv_vcf, "host" if device is None else "device", device or 0) if opts.snv_vcf else None)
+        self.open_s = time.perf_counter() - t0
         self.sets = PhaseSets() if getattr(opts, "snv_phase_sets", False) else None
         self.remap = pi.PhaseSetRemap(self.sets)
         if self.sets is not None:
             self.sets.remap = self.remap
+
+    def close(self, tm: dict | None = None) -> None:
+        """Gives the indexed reader's device object back; its stage times (only it has any) go into `tm`."""
+        if isinstance(self.snvs, IndexedSnvVcf):
+            if tm is not None:
+                tm["snv_candidates_s"] = self.open_s + self.snvs.seconds
+                tm["snv_vcf_compressed_mb"] = round(self.snvs.compressed_bytes / 1e6, 4)
+                if self.snvs.front_end == "device":
+                    tm["snv_vcf_device_s"] = self.snvs.kernel_s()
+            self.snvs.close()
 
     def snapshot(self):
         """What a block may change; restore() puts it back (a block that failed is run again locus by locus)."""
@@ -73,8 +87,16 @@ class BlockPhase:
 def _candidates(run: PhaseRun, loci, spans):
     """Per locus the indices of its candidates among its contig's records -> (contig records per locus, index arrays, cand_off, cand_pos)."""
     contigs, idx = [], []
+    # one query per contig of the block, over [min lo, max hi) of its loci with reads (the reference's per-block query,
+    # call_sample.py:124); a file read whole answers with the whole contig
+    of_contig: dict = {}
+    if run.snvs is not None:
+        for name in dict.fromkeys(locus.contig for locus in loci):
+            with_reads = [(lo, hi) for locus, (lo, hi) in zip(loci, spans) if locus.contig == name and hi > lo]
+            of_contig[name] = (run.snvs.window(name, min(lo for lo, _ in with_reads), max(hi for _, hi in with_reads))
+                               if with_reads else None)
     for locus, (lo, hi) in zip(loci, spans):
-        c = run.snvs.contig(locus.contig) if run.snvs is not None else None
+        c = of_contig.get(locus.contig)
         contigs.append(c)
         idx.append(pi.locus_candidates(c.pos, lo, hi, locus.left_flank_coord, locus.right_flank_coord)
                    if c is not None and hi > lo else np.zeros(0, np.int64))

@@ -25,6 +25,9 @@ it, which combinations of the open switches (end-gap flags x tie rule x search-r
 tests skip; parity stays "unpinned" until it exists.  Nothing of STRkit's source is read or copied by this script: it only
 imports the installed package and records what its functions return.
 
+Not made here either: a real tabix index.  On a machine with htslib, `bgzip -c snvs.vcf > snvs.vcf.gz && tabix -p vcf
+snvs.vcf.gz` on a small sorted VCF gives a `snvs.vcf.gz` + `snvs.vcf.gz.tbi` pair for tests/golden/ that pins `frontend/tabix.py` against htslib.
+
 Not made here: read selection (one record per read name, the skip flags, chimeric_in_region).  What would
 pin it is `block_segments.get_segments_for_locus(locus)` of strkit_rust_ext's block reader (the call of
 strkit/call/call_locus.py:1048, the block made at call_sample.py:86-87) on an alignment file such as the one
