@@ -709,6 +709,43 @@ int64_t strk_dbam_vcf_snvs(strk_dbam* d, int64_t start, const char* contig, int6
 /* the size constants of the kernels as built: default tile bytes, bytes per step, lines per wave */
 void strk_vcf_constants(int32_t* out3);
 
+/* ---- Locus annotations out of GFF3 / GTF text -----------------------------------------------------------------
+ * Stands where the reference asks its tabix-indexed annotation file for the features of every locus (strkit/call/loci.py:158-166,
+ * 209-214, 250-253, through pysam's asGFF3 / asGTF, which are not in its tree).  The rule is frontend/annotations.py's:
+ *   lines end at '\n' (trailing '\r's are stripped); empty lines and lines that begin with '#' are skipped; every other line
+ *   must have nine tab-separated fields, start (field 4) and end (field 5) of 1 to 18 decimal digits with 1 <= start <= end,
+ *   otherwise the call fails with STRK_E_INVALID and names the line's byte offset.  A feature is a line whose field 1 equals
+ *   `contig` byte for byte; f_beg = start - 1, f_end = end; its f_beg must not lie below the one before it (or below prev_beg;
+ *   -1: none): STRK_E_INVALID, not coordinate-sorted.  Feature and locus [s, e) overlap iff f_beg < e and f_end > s.
+ *   The id of a feature comes from field 9: gtf == 0: split at ';', leading spaces dropped, key = the bytes before the first '=',
+ *   value = the rest; gtf != 0: split at every ';' outside double quotes, spaces around a piece dropped, key = the bytes before
+ *   the first space, value = the rest without the spaces around it and without one pair of double quotes.  The last piece of a
+ *   key wins, a key matches as a whole.  kind 0: the value of `ID`; kind 1: no `ID`, field 3 is one of 5UTR, 3UTR, CDS,
+ *   start_codon, stop_codon and there is an `exon_id`: its value; kind 2: neither (the caller writes type:contig-f_beg-f_end).
+ * The text is buf[start, n_bytes), `start` a line start; final, *end_off as in strk_vcf_snvs.  l_start / l_end: the n_loci loci
+ * of the contig (callers pass them sorted by start; the pairs come in the order given).  Outputs: the (locus, feature) pairs in
+ * locus order and, per locus, file order (pair_feat indexes the hit features); per distinct hit feature, in file order, f_beg,
+ * f_end, f_kind and f_text_off [2 n + 1]: feature k's type bytes are text[f_text_off[2k] .. f_text_off[2k + 1]), its id bytes
+ * (none for kind 2) text[f_text_off[2k + 1] .. f_text_off[2k + 2]).  sizes[0..2] = pairs, hit features, text bytes, always;
+ * sizes[3] = the f_beg of the contig's last feature in the text (prev_beg when it has none).  The arrays are filled when all three
+ * sizes fit their capacities.  *past = 1 when a feature of another contig follows one of this contig (or prev_beg >= 0).
+ * Returns the number of pairs. */
+int64_t strk_gff_overlaps(const uint8_t* buf, int64_t n_bytes, int64_t start, const char* contig, int32_t gtf, int32_t final, int64_t prev_beg,
+                          int32_t n_loci, const int64_t* l_start, const int64_t* l_end, int64_t pair_cap, int32_t* pair_locus, int32_t* pair_feat,
+                          int64_t feat_cap, int64_t* f_beg, int64_t* f_end, int32_t* f_kind, int64_t* f_text_off, int64_t text_cap, uint8_t* text,
+                          int64_t* sizes, int64_t* end_off, int32_t* past);
+/* The same over the stream of a strk_dbam object, `start` an offset into it, checked before any launch.  Kernels: k_vcf_count,
+ * k_vcf_scan, k_vcf_starts (the lines), k_gff_coords (one lane per line), k_gff_gather, k_gff_classes (features partitioned by
+ * length class), k_gff_join (one wave per locus: two binary searches per class, then ballots over the candidates; count and fill
+ * pass), k_gff_hits, k_gff_order, k_gff_ids (one wave per hit feature), k_gff_text (compaction).  tile_bytes as in
+ * strk_dbam_vcf_snvs. */
+int64_t strk_dbam_gff_overlaps(strk_dbam* d, int64_t start, const char* contig, int32_t gtf, int32_t final, int64_t prev_beg, int32_t tile_bytes,
+                               int32_t n_loci, const int64_t* l_start, const int64_t* l_end, int64_t pair_cap, int32_t* pair_locus, int32_t* pair_feat,
+                               int64_t feat_cap, int64_t* f_beg, int64_t* f_end, int32_t* f_kind, int64_t* f_text_off, int64_t text_cap, uint8_t* text,
+                               int64_t* sizes, int64_t* end_off, int32_t* past);
+/* the size constants of the kernels as built: length classes, attribute bytes per step of k_gff_ids, lines per wave */
+void strk_gff_constants(int32_t* out3);
+
 /* ---- Which of the records fetched for a locus are used: one record per read name, skip flags, the cap -----------
  * Stands where the reference builds a locus's segments (block_segments.get_segments_for_locus of strkit_rust_ext, not in its
  * tree; call sites strkit/call/call_locus.py:1044-1057,1277-1285; --skip-supplementary / --skip-secondary; chimeric_in_region,

@@ -3,6 +3,7 @@ subset of `strkit call` (strkit/entry.py:20-342) that the device backend covers:
 `--call-alleles`, a genotype per locus (`--consensus`: with the sequence of every allele, which a VCF with alleles needs;
 `--consensus-method poa`: by partial-order alignment where the reads of an allele differ);
 `--count-kmers`: the motif-sized k-mers of every tract, per read and per allele.
+`--gff genes.gff3.gz`: the ids of the genome features every locus overlaps (`annotations`, `ANNOT` in the VCF).
 `python -m strkit_amd mi <child> <mother> <father> [--caller strkit-json|strkit-vcf] [--test [x2|wmw|wmw-gt]]` — `strkit mi` over
 the files `call` writes (strkit_amd/mi.py)."""
 from __future__ import annotations
@@ -70,6 +71,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="use a read name once per locus, by its first record that is not skipped (GPU with the device front end); "
                         "with one of these three switches a kept read that has a supplementary and another record over the locus "
                         "is marked chimeric_in_region, and --max-reads caps the records that are left")
+    c.add_argument("--gff", "--annotation-file", dest="annotation_file", default=None, metavar="PATH",
+                   help="BGZF-compressed GFF3 / GTF file (a GTF when .gtf occurs in PATH) with a PATH.tbi next to it: every locus lists the "
+                        "ids of the features it overlaps (annotations in the JSON report, ANNOT in the VCF); each contig's part of the "
+                        "file is read once, where --front-end says (GPU or host cores)")
     c.add_argument("--sample-id", default=None)
     c.add_argument("--processes", type=int, default=1)
     c.add_argument("--seed", type=int, default=None)
@@ -152,6 +157,8 @@ def main(argv=None) -> int:
     if not 0 <= a.methyl_threshold <= 255:
         ap.error("--methyl-threshold must be in 0 .. 255")
     import os
+    if a.annotation_file and not (os.path.isfile(a.annotation_file) and os.path.isfile(a.annotation_file + ".tbi")):
+        ap.error(f"--gff {a.annotation_file}: the file and its tabix index ({a.annotation_file}.tbi) must exist")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:   # python -m torch.distributed.run --nproc-per-node N -m strkit_amd call ...: one rank per GPU
         import torch
@@ -174,6 +181,7 @@ def main(argv=None) -> int:
                       **(dict(ploidy=a.ploidy) if a.ploidy is not None else {}),
                       **(dict(snv_phase_sets=True) if a.snv_phase_sets else {}),
                       **{k: True for k in ("skip_supplementary", "skip_secondary", "unique_reads") if getattr(a, k)},
+                      **(dict(annotation_file=a.annotation_file) if a.annotation_file else {}),
                       **(dict(call_alleles=True, consensus=a.consensus or bool(a.vcf), seed=a.seed, n_alleles=a.n_alleles)
                          if a.call_alleles else {}))
     if world > 1:

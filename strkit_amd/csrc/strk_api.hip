@@ -27,6 +27,7 @@
 #include "strk_phase_inputs.h"
 #include "strk_methyl.h"
 #include "strk_vcf.h"
+#include "strk_gff.h"
 #include "strk_select.h"
 #include "strk_mi_check.h"
 #include "strk_mi.h"
@@ -1314,5 +1315,6 @@ int strk_realign_i16_flags(int32_t n_pairs, const int64_t* s1_off, const int64_t
 #include "strk_phase_inputs.inc"
 #include "strk_methyl.inc"
 #include "strk_vcf.inc"
+#include "strk_gff.inc"
 #include "strk_select.inc"
 #include "strk_host_mi.inc"

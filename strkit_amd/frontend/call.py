@@ -21,14 +21,14 @@ from .fasta import Fasta
 from .gather import _distributed, call_blocks_sharded, deal_locus_blocks
 from .loci import Locus, load_loci, resolve_contig
 from .native import DeviceBam, IndexedBam, NativeBam
-from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, CallOptions, MethylCallOptions, PhasedCallOptions, PhaseSetCallOptions, PloidyCallOptions, PoaCallOptions, ReadSelectionCallOptions,
+from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, AnnotationCallOptions, CallOptions, MethylCallOptions, PhasedCallOptions, PhaseSetCallOptions, PloidyCallOptions, PoaCallOptions, ReadSelectionCallOptions,
                       allele_counts, phased, report_parameters, with_keywords)
 from .phase_block import PhaseRun
 from .reader import open_path
 from .refside import get_loci_with_ref_data, get_locus_with_ref_data, ref_side_of_blocks
 
 # (what moved to the other modules is still offered here under the names it had)
-__all__ = ["CallOptions", "PoaCallOptions", "PhasedCallOptions", "MethylCallOptions", "PloidyCallOptions", "PhaseSetCallOptions", "ReadSelectionCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
+__all__ = ["AnnotationCallOptions", "CallOptions", "PoaCallOptions", "PhasedCallOptions", "MethylCallOptions", "PloidyCallOptions", "PhaseSetCallOptions", "ReadSelectionCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
 
 
 def ploidy_blocks(blocks, opts):
@@ -117,6 +117,10 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, *, sample_
         if own_reader and isinstance(bam, DeviceBam):
             bam.close()             # gigabytes of device memory: not left to the garbage collector
     errors = tm.pop("errors", [])
+    if getattr(opts, "annotation_file", None):      # on the merged rows: the annotations depend on the catalog and the file only
+        from .annotations import annotate_rows
+        on_device = isinstance(bam, DeviceBam)
+        tm.update(annotate_rows(results, opts.annotation_file, "device" if on_device else "host", getattr(bam, "device", 0) if on_device else 0))
     tm["ref_side_s"] = tm.get("ref_side_s", 0.0) + tm_pre.get("ref_side_s", 0.0)
     tm["open_s"] = t_open
     if own_reader and isinstance(bam, DeviceBam):

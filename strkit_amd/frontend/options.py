@@ -193,6 +193,28 @@ class ReadSelectionCallOptions(PhaseSetCallOptions):
 READ_SELECTION_OPTION_NAMES = ("skip_supplementary", "skip_secondary", "unique_reads")
 
 
+@dataclass
+class AnnotationCallOptions(ReadSelectionCallOptions):
+    """ReadSelectionCallOptions plus locus annotations (frontend/annotations.py; `strkit call --gff /
+    --annotation-file`).  `annotation_file`: a BGZF-compressed, tabix-indexed GFF3 or GTF file (a GTF when ".gtf" occurs in the
+    path); every row of the report then lists, as `annotations`, the ids of the features its locus overlaps, and the VCF carries
+    them as ANNOT.  A type of its own for the reason PoaCallOptions gives."""
+    annotation_file: str | None = None
+
+    def validate(self) -> None:
+        super().validate()
+        if self.annotation_file is not None:
+            import os
+            if not isinstance(self.annotation_file, str) or not os.path.isfile(self.annotation_file):
+                raise ValueError(f"annotation_file {self.annotation_file!r} does not exist")
+            if not os.path.isfile(self.annotation_file + ".tbi"):
+                raise ValueError(f"annotation_file {self.annotation_file!r} has no tabix index next to it ({self.annotation_file}.tbi): "
+                                 f"bgzip the sorted file and run `tabix -p gff` on it")
+
+
+ANNOTATION_OPTION_NAMES = ("annotation_file",)
+
+
 def allele_counts(opts):
     """What genotype.n_alleles_of takes for a run: its ploidy configuration where one is set, else its n_alleles."""
     ploidy = getattr(opts, "ploidy", None)
@@ -211,8 +233,11 @@ def with_keywords(opts: CallOptions | None, **option_keywords) -> CallOptions:
     """`opts` (or the defaults) with the options given by name replaced: dataclasses.replace, after widening a plain
     CallOptions to PoaCallOptions when one of POA_OPTION_NAMES is among them, to PhasedCallOptions for PHASE_OPTION_NAMES, to
     MethylCallOptions for METHYL_OPTION_NAMES, to PloidyCallOptions for PLOIDY_OPTION_NAMES, to PhaseSetCallOptions for
-    PHASE_SET_OPTION_NAMES, and to ReadSelectionCallOptions for READ_SELECTION_OPTION_NAMES.  An unknown name is a TypeError."""
+    PHASE_SET_OPTION_NAMES, to ReadSelectionCallOptions for READ_SELECTION_OPTION_NAMES, and to AnnotationCallOptions for
+    ANNOTATION_OPTION_NAMES.  An unknown name is a TypeError."""
     opts = opts or CallOptions()
+    if not isinstance(opts, AnnotationCallOptions) and any(k in option_keywords for k in ANNOTATION_OPTION_NAMES):
+        opts = AnnotationCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, ReadSelectionCallOptions) and any(k in option_keywords for k in READ_SELECTION_OPTION_NAMES):
         opts = ReadSelectionCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, PhaseSetCallOptions) and any(k in option_keywords for k in PHASE_SET_OPTION_NAMES):
@@ -251,4 +276,5 @@ def report_parameters(opts: CallOptions, processes: int) -> dict:
             **({"methyl_threshold": opts.methyl_threshold} if getattr(opts, "use_methyl", False) and opts.methyl_threshold != 127 else {}),
             **({"ploidy": opts.ploidy} if getattr(opts, "ploidy", None) is not None else {}),
             **({"snv_phase_sets": True} if getattr(opts, "snv_phase_sets", False) else {}),
-            **{name: True for name in READ_SELECTION_OPTION_NAMES if getattr(opts, name, False)}}
+            **{name: True for name in READ_SELECTION_OPTION_NAMES if getattr(opts, name, False)},
+            **({"annotation_file": opts.annotation_file} if getattr(opts, "annotation_file", None) else {})}

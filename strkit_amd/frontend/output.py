@@ -123,6 +123,16 @@ _INFOS = (("VT", "1", "String", "Variant record type (str/snv)"),
           ("ANCH", "1", "Integer", "Five-prime anchor size"))
 
 
+_INFO_ANNOT = ("ANNOT", "1", "String", "Locus annotations (e.g., genomic regions)")      # output/vcf.py:148
+
+
+def _annot_value(ids) -> str:
+    """The ids joined by ',' as the reference joins them (output/vcf.py:275), each with the characters an INFO value cannot hold
+    percent-encoded (VCF 4.3 §1.2; '%' itself too, so that the encoding can be undone)."""
+    enc = {"%": "%25", " ": "%20", ";": "%3B", "=": "%3D", ",": "%2C"}
+    return ",".join("".join(enc.get(ch, ch) for ch in i) for i in ids)
+
+
 def _has_seqs(row: dict) -> bool:
     return bool(row.get("call")) and bool((row.get("peaks") or {}).get("seqs"))
 
@@ -188,7 +198,8 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
     if ref is not None:
         lines += [f"##contig=<ID={c},length={ref.get_reference_length(c)}>" for c in ref.references]
     lines += [f'##FORMAT=<ID={i},Number={n},Type={t},Description="{d}">' for i, n, t, d in formats]
-    lines += [f'##INFO=<ID={i},Number={n},Type={t},Description="{d}">' for i, n, t, d in _INFOS]
+    annot = bool((report.get("parameters") or {}).get("annotation_file"))      # (--gff: ANNOT exists only in such a report's VCF)
+    lines += [f'##INFO=<ID={i},Number={n},Type={t},Description="{d}">' for i, n, t, d in _INFOS + ((_INFO_ANNOT,) if annot else ())]
     lines.append("#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + sample)
     n_rec = 0
     # snv_phase_sets: the only switch that changes what is written for a row's SNVs
@@ -220,6 +231,8 @@ def write_vcf(report: dict, path: str, ref=None, sample_id: str | None = None, n
         if peaks:
             n_peaks = int(peaks["modal_n"])
         info = f"VT=str;MOTIF={row['motif']};REFMC={row['ref_cn']};BED_START={row['start']};BED_END={row['end']};ANCH={len(anchor)}"
+        if annot and row.get("annotations"):
+            info += ";ANNOT=" + _annot_value(row["annotations"])
         keys, vals = ["GT", "DP"], [gt, str(len(reads))]
         if row.get("assign_method"):
             keys.append("PM"); vals.append(str(row["assign_method"]))

@@ -42,10 +42,12 @@ def _voff(block_off: np.ndarray, block_bytes: int, u: int) -> int:
     return (int(block_off[u // block_bytes]) << 16) | (u % block_bytes)
 
 
-def write_tbi(path: str, text: bytes, block_off: np.ndarray, block_bytes: int = 0xFF00) -> None:
+def write_tbi(path: str, text: bytes, block_off: np.ndarray, block_bytes: int = 0xFF00, gff: bool = False) -> None:
     """The tabix index of the VCF `text` written by write_bgzf_vcf (coordinate-sorted within each contig, contigs in blocks).
     Every data line is a record of [POS - 1, POS - 1 + len(REF)); consecutive records of a bin share a chunk; linear windows no
-    record overlaps take the preceding window's entry, as htslib fills them."""
+    record overlaps take the preceding window's entry, as htslib fills them.  `gff`: the text is GFF3 / GTF instead: a data line is
+    a record of [start - 1, end) (columns 4 and 5), in the bin of that extent and in the linear index of every window it overlaps,
+    and the header says generic format 0 with columns 1 / 4 / 5 (`tabix -p gff`)."""
     names: list[bytes] = []
     bins: list[dict[int, list]] = []
     lin: list[dict[int, int]] = []
@@ -53,10 +55,11 @@ def write_tbi(path: str, text: bytes, block_off: np.ndarray, block_bytes: int = 
     for raw in text.split(b"\n"):
         a, u = u, u + len(raw) + 1
         f = raw.split(b"\t")
-        if not raw or raw[:1] == b"#" or len(f) < 4:
+        if not raw or raw[:1] == b"#" or len(f) < (5 if gff else 4):
             continue
         try:
-            pos0 = int(f[1]) - 1
+            pos0 = int(f[3 if gff else 1]) - 1
+            end_gff = int(f[4]) if gff else 0
         except ValueError:
             pos0 = -1
         if not 0 <= pos0 < (1 << 29):      # what the index cannot place is left out of it (the bins end at 2^29)
@@ -66,7 +69,7 @@ def write_tbi(path: str, text: bytes, block_off: np.ndarray, block_bytes: int = 
             bins.append({})
             lin.append({})
         t = names.index(f[0])
-        end0 = pos0 + max(1, len(f[3].rstrip(b"\r")))
+        end0 = min(max(end_gff, pos0 + 1), 1 << 29) if gff else pos0 + max(1, len(f[3].rstrip(b"\r")))
         v0, v1 = _voff(block_off, block_bytes, a), _voff(block_off, block_bytes, min(u, len(text)))
         ch = bins[t].setdefault(_reg2bin(pos0, end0), [])
         if ch and ch[-1][1] == v0:
@@ -77,7 +80,7 @@ def write_tbi(path: str, text: bytes, block_off: np.ndarray, block_bytes: int = 
             if w not in lin[t] or v0 < lin[t][w]:
                 lin[t][w] = v0
     nm = b"".join(n + b"\0" for n in names)
-    out = bytearray(b"TBI\x01" + struct.pack("<8i", len(names), 2, 1, 2, 0, ord("#"), 0, len(nm)) + nm)
+    out = bytearray(b"TBI\x01" + struct.pack("<8i", len(names), 0 if gff else 2, 1, 4 if gff else 2, 5 if gff else 0, ord("#"), 0, len(nm)) + nm)
     for t in range(len(names)):
         out += struct.pack("<i", len(bins[t]))
         for b in sorted(bins[t]):

@@ -1,4 +1,4 @@
-"""A tabix index (.tbi) of a BGZF-compressed VCF: which compressed bytes hold the records of a region.  Stands where the
+"""A tabix index (.tbi) of a BGZF-compressed VCF (or, with preset="gff", of a GFF3 / GTF file): which compressed bytes hold the records of a region.  Stands where the
 reference's reader hands a locus block to htslib's tabix access (call_sample.py:124); the layout is the one of the tabix
 specification (samtools.github.io/hts-specs/tabix.pdf), the binning scheme the one of `synth_large._reg2bin` and `write_bai`.
 Unpinned against htslib: the only writer on hand is `synth_snvs.write_tbi`, which comes from the same reading of the format.
@@ -33,8 +33,12 @@ def reg2bins(beg: int, end: int) -> list[int]:
 class TabixIndex:
     """`names`: the contigs in the index's order; per contig the bins with their chunks and the 16 kb linear index."""
 
-    def __init__(self, path: str, vcf_path: str | None = None):
-        self.path = path
+    def __init__(self, path: str, vcf_path: str | None = None, preset: str = "vcf"):
+        """`preset`: "vcf" (format 2, columns 1 / 2) or, by request only, "gff" (the generic format 0 with columns 1 / 4 / 5 and
+        the comment character '#': what `tabix -p gff` writes); an index of any other layout is refused."""
+        if preset not in ("vcf", "gff"):
+            raise ValueError(f"preset must be 'vcf' or 'gff', not {preset!r}")
+        self.path, self.preset = path, preset
         if vcf_path is not None and os.path.getmtime(path) + 1.0 < os.path.getmtime(vcf_path):
             warnings.warn(f"{path} is older than {vcf_path}: the index may be stale (re-index the file if records go missing)",
                           RuntimeWarning, stacklevel=3)
@@ -51,8 +55,12 @@ class TabixIndex:
             raise ValueError(f"{path}: truncated tabix index") from None
 
     def _parse(self, raw: bytes) -> None:
-        n_ref, fmt, col_seq, col_beg, _col_end, _meta, _skip, l_nm = struct.unpack_from("<8i", raw, 4)
-        if fmt != 2 or col_seq != 1 or col_beg != 2:
+        n_ref, fmt, col_seq, col_beg, col_end, meta, _skip, l_nm = struct.unpack_from("<8i", raw, 4)
+        if self.preset == "gff":
+            if fmt != 0 or (col_seq, col_beg, col_end) != (1, 4, 5) or meta != ord("#"):
+                raise ValueError(f"{self.path}: not the index of a GFF3 / GTF file (format {fmt}, columns {col_seq} / {col_beg} / {col_end}, "
+                                 f"comment character {meta}; expected 0, 1 / 4 / 5, {ord('#')})")
+        elif fmt != 2 or col_seq != 1 or col_beg != 2:
             raise ValueError(f"{self.path}: not the index of a VCF (format {fmt}, columns {col_seq} / {col_beg}; expected 2, 1 / 2)")
         if n_ref < 0 or l_nm < 0 or 36 + l_nm > len(raw):
             raise IndexError
@@ -87,6 +95,20 @@ class TabixIndex:
     def resolve(self, contig: str) -> str | None:
         """The contig as the file spells it (with or without "chr"), or None."""
         return resolve_contig(self.names, contig)
+
+    def contig_range(self, contig: str) -> tuple[int, int] | None:
+        """(virtual offset of the contig's first record, compressed offset of the last BGZF block that holds one of its records), from
+        the chunks of all its bins (a first record at virtual offset 0, which the linear index cannot tell from "none", is found
+        too), or None when the index knows of none."""
+        name = self.resolve(contig)
+        if name is None:
+            return None
+        chunks = [c for c in self.bins[self.names.index(name)].values() if len(c)]
+        if not chunks:
+            return None
+        both = np.concatenate(chunks)
+        start, stop = int(both[:, 0].min()), int(both[:, 1].max())
+        return (start, stop >> 16) if stop > start else None
 
     def block_range(self, contig: str, beg: int, end: int) -> tuple[int, int] | None:
         """(virtual offset to start reading at, compressed offset of the last BGZF block that has to be read) for the records of
