@@ -699,7 +699,7 @@ int64_t strk_vcf_snvs(const uint8_t* buf, int64_t n_bytes, int64_t start, const 
                       int64_t prev_pos, int32_t contig_seen, int64_t cap, int64_t* pos, uint8_t* ref, int64_t* id_off, uint8_t* ids,
                       int64_t ids_cap, int64_t* id_bytes, int64_t* end_off, int32_t* past);
 /* The same over the stream of a strk_dbam object (a BGZF-compressed VCF inflated by strk_dbam_inflate*), `start` an offset into
- * it, checked against the stream's size before any launch.  Kernels: k_vcf_count, k_vcf_scan, k_vcf_starts (the lines),
+ * it, checked against the stream's size before any launch.  Kernels: k_lines_count, k_lines_scan, k_lines_starts (the lines),
  * k_vcf_parse (one lane per line), k_vcf_compact (the kept lines and their ID bytes); one record per position and sortedness are
  * applied on the host to what comes back.  tile_bytes: the text bytes one wave walks in the line passes, a multiple of 256
  * (0: the default); no output depends on it. */
@@ -708,6 +708,15 @@ int64_t strk_dbam_vcf_snvs(strk_dbam* d, int64_t start, const char* contig, int6
                            uint8_t* ids, int64_t ids_cap, int64_t* id_bytes, int64_t* end_off, int32_t* past);
 /* the size constants of the kernels as built: default tile bytes, bytes per step, lines per wave */
 void strk_vcf_constants(int32_t* out3);
+/* The lines of the text in the stream of a strk_dbam object, from `start` on: what strk_dbam_vcf_snvs and
+ * strk_dbam_gff_overlaps begin with (k_lines_count, k_lines_scan, k_lines_starts).  A line start is `start` itself and the offset just past every '\n' in
+ * [start, the stream's size): *n_starts of them (the '\n's + 1), of which starts[0 .. min(cap, *n_starts)) are written.  Returns
+ * the number of lines a reader takes: one per '\n', and the bytes behind the last '\n' when final != 0 and there are any;
+ * *end_off = where the first line not taken begins (the stream's size when all were).  tile_bytes as in strk_dbam_vcf_snvs.
+ * STRK_E_INVALID, before any launch, for a tile_bytes that is no multiple of 256 and a start outside the stream; start == the
+ * stream's size: 0 lines, *end_off = start, *n_starts = 1, nothing launched. */
+int64_t strk_dbam_text_lines(strk_dbam* d, int64_t start, int32_t final, int32_t tile_bytes, int64_t cap, int64_t* starts,
+                             int64_t* end_off, int64_t* n_starts);
 
 /* ---- Locus annotations out of GFF3 / GTF text -----------------------------------------------------------------
  * Stands where the reference asks its tabix-indexed annotation file for the features of every locus (strkit/call/loci.py:158-166,
@@ -734,8 +743,8 @@ int64_t strk_gff_overlaps(const uint8_t* buf, int64_t n_bytes, int64_t start, co
                           int32_t n_loci, const int64_t* l_start, const int64_t* l_end, int64_t pair_cap, int32_t* pair_locus, int32_t* pair_feat,
                           int64_t feat_cap, int64_t* f_beg, int64_t* f_end, int32_t* f_kind, int64_t* f_text_off, int64_t text_cap, uint8_t* text,
                           int64_t* sizes, int64_t* end_off, int32_t* past);
-/* The same over the stream of a strk_dbam object, `start` an offset into it, checked before any launch.  Kernels: k_vcf_count,
- * k_vcf_scan, k_vcf_starts (the lines), k_gff_coords (one lane per line), k_gff_gather, k_gff_classes (features partitioned by
+/* The same over the stream of a strk_dbam object, `start` an offset into it, checked before any launch.  Kernels: k_lines_count,
+ * k_lines_scan, k_lines_starts (the lines), k_gff_coords (one lane per line), k_gff_gather, k_gff_classes (features partitioned by
  * length class), k_gff_join (one wave per locus: two binary searches per class, then ballots over the candidates; count and fill
  * pass), k_gff_hits, k_gff_order, k_gff_ids (one wave per hit feature), k_gff_text (compaction).  tile_bytes as in
  * strk_dbam_vcf_snvs. */

@@ -90,7 +90,7 @@ EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk
            "strk_consensus", "strk_consensus_dseqs", "strk_consensus_ws",
            "strk_phase_cells", "strk_useful_snvs", "strk_dbam_phase_cells", "strk_dbam_download_cells", "strk_dbam_useful_snvs",
            "strk_methyl", "strk_dbam_methyl", "strk_methyl_constants",
-           "strk_vcf_snvs", "strk_dbam_vcf_snvs", "strk_vcf_constants",
+           "strk_vcf_snvs", "strk_dbam_vcf_snvs", "strk_vcf_constants", "strk_dbam_text_lines",
            "strk_gff_overlaps", "strk_dbam_gff_overlaps", "strk_gff_constants",
            "strk_mi_trio", "strk_mi_trio_host", "strk_mi_constants",
            "strk_select_reads", "strk_dbam_select_reads", "strk_select_constants",
@@ -280,6 +280,8 @@ def load(build: bool = True):
         L.strk_dbam_vcf_snvs.argtypes = [C.c_void_p, C.c_int64, C.c_char_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32] + _vcf_tail
         L.strk_vcf_constants.restype = None
         L.strk_vcf_constants.argtypes = [_i32p]
+        L.strk_dbam_text_lines.restype = C.c_int64
+        L.strk_dbam_text_lines.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, _i64p, _i64p]
         _gff_tail = ([C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_void_p, C.c_void_p,
                      C.POINTER(C.c_int64), C.POINTER(C.c_int32)])
         L.strk_gff_overlaps.restype = C.c_int64

@@ -1312,6 +1312,7 @@ int strk_realign_i16_flags(int32_t n_pairs, const int64_t* s1_off, const int64_t
 }  // extern "C"
 
 #include "strk_dbam.inc"
+#include "strk_lines.inc"
 #include "strk_phase_inputs.inc"
 #include "strk_methyl.inc"
 #include "strk_vcf.inc"

@@ -237,8 +237,9 @@ struct strk_dbam {
     std::vector<int64_t> pc_cell_off_h;
     bool pc_valid = false;
     DevBuf me_in;   // strk_dbam_methyl (strk_methyl.inc): its inputs and outputs
-    DevBuf vc_tiles, vc_lines, vc_out;   // strk_dbam_vcf_snvs (strk_vcf.inc): per tile, per line, per kept line
-    DevBuf gf_tiles, gf_lines, gf_feat, gf_join, gf_pairs, gf_out, gf_text;   // strk_dbam_gff_overlaps (strk_gff.inc): per tile, line, feature, locus, pair; what is downloaded
+    DevBuf ln_tiles, ln_starts, ln_query;   // the lines of a text (strk_lines.inc): per tile, the line starts; a reader's status words and contig name
+    DevBuf vc_lines, vc_out;   // strk_dbam_vcf_snvs (strk_vcf.inc): per line, per kept line
+    DevBuf gf_lines, gf_feat, gf_join, gf_pairs, gf_out, gf_text;   // strk_dbam_gff_overlaps (strk_gff.inc): per line, feature, locus, pair; what is downloaded
     int64_t n_data = 0;    // bytes of `data` that are filled
     int64_t coff0 = 0;     // compressed offset of the inflated stretch
     PinnedBuf ring_mem;                     // strk_dbam_inflate_file: pinned pieces, their stream and events

@@ -1,8 +1,7 @@
 // strk_gff.h — the genome features of GFF3 / GTF text that overlap the loci of one contig, for host and device: the rule of one line
 // (parse_line), the key match of an attribute piece (match_key) and the id of a feature (find_id), the host walk with its join
 // (overlaps_host), the closing pass with its capacities (emit), and the kernels that do the same over a text resident in HBM.
-// strk_gff.inc has the buffers and the launches; the lines of the text are found by strk_vcf.h's k_vcf_count / k_vcf_scan /
-// k_vcf_starts.
+// strk_gff.inc has the buffers and the launches; the lines: strk_lines.h.
 //
 // Reference: strkit/call/loci.py:158-166 (get_feature_id), :209-214, :250-253 (one tabix fetch per locus through pysam's asGFF3 /
 // asGTF, which are not in the tree).  The rule is the one frontend/annotations.py states; tests/annot_cases.py pins
@@ -16,7 +15,7 @@
 #include <vector>
 
 #include "strk_bamrec.h"   // STRK_FE_HD
-#include "strk_vcf.h"      // the line split
+#include "strk_lines.h"
 
 namespace strk_gff {
 
@@ -175,20 +174,15 @@ inline int unsorted_line(Message* msg, int64_t off) {
     return -1;
 }
 
-// The host walk over t[start, n): lines by memchr, the fields by `par` (a parallel for over [0, n) in slices), order, the join by
+// The host walk over t[start, n): lines by strk_lines::split_host, the fields by `par` (a parallel for over [0, n) in slices), order, the join by
 // length classes (two binary searches per class and locus), ids of the hit features only.  Returns 0, or -1 with msg.
 template <class Par>
 int overlaps_host(const uint8_t* t, int64_t n, int64_t start, const char* contig, int32_t gtf, int32_t final, int64_t prev_beg, int32_t n_loci,
                   const int64_t* ls, const int64_t* le, Result* out, Message* msg, Par&& par) {
-    std::vector<int64_t> starts{start};
-    for (int64_t p = start; p < n;) {
-        const void* nl = memchr(t + p, '\n', (size_t)(n - p));
-        if (!nl) break;
-        p = (const uint8_t*)nl - t + 1;
-        starts.push_back(p);
-    }
-    const int32_t n_nl = (int32_t)starts.size() - 1, n_lines = n_nl + ((final && starts.back() < n) ? 1 : 0);
-    out->end_off = n_lines > n_nl ? n : starts.back();
+    const strk_lines::Lines l = strk_lines::split_host(t, n, start, final);
+    const std::vector<int64_t>& starts = l.starts;
+    const int32_t n_nl = l.n_nl, n_lines = l.n_lines;
+    out->end_off = l.end_off;
     const int32_t contig_len = (int32_t)strlen(contig);
     std::vector<Line> lines((size_t)n_lines);
     par(n_lines, [&](int32_t i0, int32_t i1) {
@@ -277,7 +271,7 @@ inline int64_t emit(const Result& r, int32_t n_loci, int64_t pair_cap, int32_t* 
 #if defined(__HIPCC__)
 
 // ---- the fields: one lane per line ------------------------------------------------------------------------------------------
-// Lines as in k_vcf_parse.  st: [0] the lowest offset of a line that breaks a rule, [1] the first line of the contig, [2] 1 + the
+// Lines as strk_lines.h numbers them.  st: [0] the lowest offset of a line that breaks a rule, [1] the first line of the contig, [2] 1 + the
 // last line of another contig, [3] the lowest offset of a line whose start descends (k_gff_gather).
 __global__ void __launch_bounds__(256) k_gff_coords(const uint8_t* data, int64_t n, const int64_t* starts, int32_t n_nl, int32_t n_lines,
                                                     const uint8_t* contig, int32_t contig_len, int64_t* l_beg, int64_t* l_end, int64_t* l_type_a,

@@ -1,6 +1,7 @@
 // strk_gff.inc — locus annotations from GFF3 / GTF text (part of strk_api.hip, after strk_vcf.inc): strk_gff_overlaps over a
 // decompressed host buffer and strk_dbam_gff_overlaps over the stream of a strk_dbam object.  The rule of a line and of an id, the
-// host walk, the closing pass and the kernels are strk_gff.h; here are the argument checks, the buffers and the launches.
+// host walk, the closing pass and the kernels are strk_gff.h, the lines strk_lines.h / strk_lines.inc; here are the argument checks,
+// the buffers and the launches.
 
 namespace {
 
@@ -8,10 +9,7 @@ int gff_check(const char* who, int64_t n_bytes, int64_t start, const char* conti
               int64_t pair_cap, const int32_t* pair_locus, const int32_t* pair_feat, int64_t feat_cap, const int64_t* f_beg, const int64_t* f_end,
               const int32_t* f_kind, const int64_t* f_text_off, int64_t text_cap, const uint8_t* text, const int64_t* sizes, const int64_t* end_off,
               const int32_t* past) {
-    if (!contig || !contig[0]) return fail(STRK_E_INVALID, "%s: no contig name", who);
-    if (!sizes || !end_off || !past) return fail(STRK_E_INVALID, "%s: NULL argument", who);
-    if (n_bytes < 0 || start < 0 || start > n_bytes) return fail(STRK_E_INVALID, "%s: start offset %lld outside the text of %lld bytes", who, (long long)start, (long long)n_bytes);
-    if (n_bytes - start >= ((int64_t)1 << 31)) return fail(STRK_E_INVALID, "%s: a piece of %lld bytes (at most 2^31 - 1)", who, (long long)(n_bytes - start));
+    if (const int rc = text_check(who, n_bytes, start, contig, sizes, end_off, past)) return rc;
     if (prev_beg < -1) return fail(STRK_E_INVALID, "%s: bad prev_beg", who);
     if (n_loci < 0 || (n_loci > 0 && (!ls || !le))) return fail(STRK_E_INVALID, "%s: bad loci", who);
     if (pair_cap < 0 || feat_cap < 0 || text_cap < 0 || (pair_cap > 0 && (!pair_locus || !pair_feat)) ||
@@ -56,70 +54,42 @@ int64_t strk_dbam_gff_overlaps(strk_dbam* d, int64_t start, const char* contig, 
     int rc = gff_check(who, d->n_data, start, contig, prev_beg, n_loci, l_start, l_end, pair_cap, pair_locus, pair_feat, feat_cap, f_beg, f_end, f_kind,
                        f_text_off, text_cap, text, sizes, end_off, past);
     if (rc) return rc;
-    if (tile_bytes == 0) tile_bytes = strk_vcf::kTileBytes;
-    if (tile_bytes < strk_vcf::kStepBytes || tile_bytes % strk_vcf::kStepBytes || tile_bytes > (1 << 20))
-        return fail(STRK_E_INVALID, "%s: tile_bytes must be a multiple of %d", who, strk_vcf::kStepBytes);
+    *end_off = start; *past = 0;
+    DevLines l;
+    if ((rc = dbam_lines(d, who, start, final, tile_bytes, &l))) return rc;
     const int64_t n = d->n_data;
     strk_gff::Result r;
     r.pair_off.assign((size_t)n_loci + 1, 0);
     r.text_off.push_back(0);
-    r.last_beg = prev_beg; r.end_off = start;
-    *end_off = start; *past = 0;
+    r.last_beg = prev_beg; r.end_off = l.end_off;
     const auto done = [&]() {
         *end_off = r.end_off; *past = r.past;
         return strk_gff::emit(r, n_loci, pair_cap, pair_locus, pair_feat, feat_cap, f_beg, f_end, f_kind, f_text_off, text_cap, text, sizes);
     };
     if (start == n) return done();   // nothing to read, nothing launched
-    HIP_TRY(hipSetDevice(d->device));
+    const int32_t n_nl = l.n_nl, n_lines = l.n_lines;
+    if (n_lines == 0) return done();
     const uint8_t* const data = d->data.as<uint8_t>();
+    const int64_t* const starts = l.starts;
     const int32_t contig_len = (int32_t)strlen(contig);
-    // ---- the lines (strk_vcf.h's kernels).  gf_tiles: counts | offsets | status words | the contig's name
-    const int64_t t0 = start & ~(int64_t)(strk_vcf::kStepBytes - 1);
-    const int32_t n_tiles = (int32_t)((n - t0 + tile_bytes - 1) / tile_bytes);
-    Carve ct;
-    const size_t o_cnt = ct.take((size_t)n_tiles * 4), o_off = ct.take(((size_t)n_tiles + 1) * 8), o_st = ct.take(32), o_name = ct.take((size_t)contig_len);
-    if ((rc = d->gf_tiles.ensure(ct.bytes))) return rc;
-    const unsigned long long st0[4] = {~0ull, ~0ull, 0ull, ~0ull};
-    HIP_TRY(hipMemcpy(d->gf_tiles.at<char>(o_st), st0, 32, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d->gf_tiles.at<char>(o_name), contig, (size_t)contig_len, hipMemcpyHostToDevice));
-    unsigned long long* const st = d->gf_tiles.at<unsigned long long>(o_st);
-    const dim3 tile_grid((unsigned)((n_tiles + 3) / 4));
-    d->tic();
-    hipLaunchKernelGGL(strk_vcf::k_vcf_count, tile_grid, dim3(256), 0, 0, data, n, start, tile_bytes, n_tiles, d->gf_tiles.at<int32_t>(o_cnt));
-    hipLaunchKernelGGL(strk_vcf::k_vcf_scan, dim3(1), dim3(256), 0, 0, d->gf_tiles.at<int32_t>(o_cnt), n_tiles, d->gf_tiles.at<int64_t>(o_off));
-    HIP_TRY(hipGetLastError());
-    d->toc();
-    int64_t n_nl64 = 0;
-    HIP_TRY(hipMemcpy(&n_nl64, d->gf_tiles.at<int64_t>(o_off) + n_tiles, 8, hipMemcpyDeviceToHost));
-    if (n_nl64 < 0 || n_nl64 > n - start) return fail(STRK_E_DEVICE, "%s: line count %lld out of range", who, (long long)n_nl64);
-    const int32_t n_nl = (int32_t)n_nl64;
-    // gf_lines: starts [n_nl + 1] | f_beg | f_end | type_a | attr_a | type_len | attr_len | status per line | features per wave, their offsets
+    unsigned long long* st = nullptr;
+    const uint8_t* name = nullptr;
+    if ((rc = dbam_query(d, {~0ull, ~0ull, 0ull, ~0ull}, contig, contig_len, &st, &name))) return rc;
+    // gf_lines: f_beg | f_end | type_a | attr_a | type_len | attr_len | status per line | features per wave, their offsets
     const size_t cap_lines = (size_t)n_nl + 1, n_lw = (cap_lines + 63) / 64;
     Carve cl;
-    const size_t o_starts = cl.take(cap_lines * 8), o_beg = cl.take(cap_lines * 8), o_end = cl.take(cap_lines * 8), o_ta = cl.take(cap_lines * 8),
-                 o_aa = cl.take(cap_lines * 8), o_tl = cl.take(cap_lines * 4), o_al = cl.take(cap_lines * 4), o_stat = cl.take(cap_lines),
-                 o_oc = cl.take(n_lw * 4), o_oo = cl.take((n_lw + 1) * 8);
+    const size_t o_beg = cl.take(cap_lines * 8), o_end = cl.take(cap_lines * 8), o_ta = cl.take(cap_lines * 8), o_aa = cl.take(cap_lines * 8),
+                 o_tl = cl.take(cap_lines * 4), o_al = cl.take(cap_lines * 4), o_stat = cl.take(cap_lines), o_oc = cl.take(n_lw * 4),
+                 o_oo = cl.take((n_lw + 1) * 8);
     if ((rc = d->gf_lines.ensure(cl.bytes))) return rc;
-    int64_t* const starts = d->gf_lines.at<int64_t>(o_starts);
-    d->tic();
-    hipLaunchKernelGGL(strk_vcf::k_vcf_starts, tile_grid, dim3(256), 0, 0, data, n, start, tile_bytes, n_tiles, d->gf_tiles.at<int64_t>(o_off),
-                       (int64_t)cap_lines, starts);
-    HIP_TRY(hipGetLastError());
-    d->toc();
-    int64_t last_start = 0;
-    HIP_TRY(hipMemcpy(&last_start, starts + n_nl, 8, hipMemcpyDeviceToHost));
-    if (last_start < start || last_start > n) return fail(STRK_E_DEVICE, "%s: line start %lld out of range", who, (long long)last_start);
-    const int32_t n_lines = n_nl + ((final && last_start < n) ? 1 : 0);
-    r.end_off = n_lines > n_nl ? n : last_start;
-    if (n_lines == 0) return done();
     // ---- the fields, the contig's features in file order
     const int32_t n_line_waves = (n_lines + 63) / 64;
-    const dim3 line_grid((unsigned)((n_lines + 255) / 256));
+    const dim3 line_grid = l.line_grid;
     d->tic();
-    hipLaunchKernelGGL(strk_gff::k_gff_coords, line_grid, dim3(256), 0, 0, data, n, starts, n_nl, n_lines, d->gf_tiles.at<uint8_t>(o_name), contig_len,
+    hipLaunchKernelGGL(strk_gff::k_gff_coords, line_grid, dim3(256), 0, 0, data, n, starts, n_nl, n_lines, name, contig_len,
                        d->gf_lines.at<int64_t>(o_beg), d->gf_lines.at<int64_t>(o_end), d->gf_lines.at<int64_t>(o_ta), d->gf_lines.at<int32_t>(o_tl),
                        d->gf_lines.at<int64_t>(o_aa), d->gf_lines.at<int32_t>(o_al), d->gf_lines.at<uint8_t>(o_stat), d->gf_lines.at<int32_t>(o_oc), st);
-    hipLaunchKernelGGL(strk_vcf::k_vcf_scan, dim3(1), dim3(256), 0, 0, d->gf_lines.at<int32_t>(o_oc), n_line_waves, d->gf_lines.at<int64_t>(o_oo));
+    hipLaunchKernelGGL(strk_lines::k_lines_scan, dim3(1), dim3(256), 0, 0, d->gf_lines.at<int32_t>(o_oc), n_line_waves, d->gf_lines.at<int64_t>(o_oo));
     HIP_TRY(hipGetLastError());
     d->toc();
     int64_t n_feat64 = 0;
@@ -147,7 +117,7 @@ int64_t strk_dbam_gff_overlaps(strk_dbam* d, int64_t start, const char* contig, 
                            d->gf_lines.at<int64_t>(o_end), d->gf_lines.at<int64_t>(o_oo), n_feat, fb, fe, f_line);
         hipLaunchKernelGGL(strk_gff::k_gff_classes, feat_grid, dim3(256), 0, 0, n_feat, fb, fe, f_line, starts, prev_beg, n_fw, d->gf_feat.at<int32_t>(o_cc),
                            (const int64_t*)nullptr, (int64_t*)nullptr, (int64_t*)nullptr, (int32_t*)nullptr, st);
-        hipLaunchKernelGGL(strk_vcf::k_vcf_scan, dim3(1), dim3(256), 0, 0, d->gf_feat.at<int32_t>(o_cc), (int32_t)n_slots, coff);
+        hipLaunchKernelGGL(strk_lines::k_lines_scan, dim3(1), dim3(256), 0, 0, d->gf_feat.at<int32_t>(o_cc), (int32_t)n_slots, coff);
         hipLaunchKernelGGL(strk_gff::k_gff_classes, feat_grid, dim3(256), 0, 0, n_feat, fb, fe, f_line, starts, prev_beg, n_fw, d->gf_feat.at<int32_t>(o_cc),
                            (const int64_t*)coff, d->gf_feat.at<int64_t>(o_pb), d->gf_feat.at<int64_t>(o_pe), d->gf_feat.at<int32_t>(o_po), st);
         HIP_TRY(hipGetLastError());
@@ -177,7 +147,7 @@ int64_t strk_dbam_gff_overlaps(strk_dbam* d, int64_t start, const char* contig, 
     hipLaunchKernelGGL(strk_gff::k_gff_join, locus_grid, dim3(256), 0, 0, n_loci, d->gf_join.at<int64_t>(o_ls), d->gf_join.at<int64_t>(o_le), n_feat, n_fw, coff,
                        d->gf_feat.at<int64_t>(o_pb), d->gf_feat.at<int64_t>(o_pe), d->gf_feat.at<int32_t>(o_po), d->gf_join.at<int32_t>(o_pc),
                        (const int64_t*)nullptr, (int64_t)0, (int32_t*)nullptr, (uint8_t*)nullptr);
-    hipLaunchKernelGGL(strk_vcf::k_vcf_scan, dim3(1), dim3(256), 0, 0, d->gf_join.at<int32_t>(o_pc), n_loci, pair_off);
+    hipLaunchKernelGGL(strk_lines::k_lines_scan, dim3(1), dim3(256), 0, 0, d->gf_join.at<int32_t>(o_pc), n_loci, pair_off);
     HIP_TRY(hipGetLastError());
     d->toc();
     int64_t n_pairs = 0;
@@ -192,7 +162,7 @@ int64_t strk_dbam_gff_overlaps(strk_dbam* d, int64_t start, const char* contig, 
                        (const int64_t*)pair_off, n_pairs, d->gf_pairs.as<int32_t>(), d->gf_feat.at<uint8_t>(o_flag));
     hipLaunchKernelGGL(strk_gff::k_gff_hits, feat_grid, dim3(256), 0, 0, n_feat, d->gf_feat.at<uint8_t>(o_flag), d->gf_feat.at<int32_t>(o_hc),
                        (const int64_t*)nullptr, 0, (int32_t*)nullptr, (int32_t*)nullptr);
-    hipLaunchKernelGGL(strk_vcf::k_vcf_scan, dim3(1), dim3(256), 0, 0, d->gf_feat.at<int32_t>(o_hc), n_fw, d->gf_feat.at<int64_t>(o_ho));
+    hipLaunchKernelGGL(strk_lines::k_lines_scan, dim3(1), dim3(256), 0, 0, d->gf_feat.at<int32_t>(o_hc), n_fw, d->gf_feat.at<int64_t>(o_ho));
     HIP_TRY(hipGetLastError());
     d->toc();
     int64_t n_hit64 = 0;
@@ -217,7 +187,7 @@ int64_t strk_dbam_gff_overlaps(strk_dbam* d, int64_t start, const char* contig, 
                        d->gf_lines.at<int32_t>(o_tl), d->gf_lines.at<int64_t>(o_aa), d->gf_lines.at<int32_t>(o_al), gtf ? 1 : 0, d->gf_out.at<int64_t>(q_hb),
                        d->gf_out.at<int64_t>(q_he), d->gf_out.at<int32_t>(q_hk), d->gf_out.at<int64_t>(q_ta), d->gf_out.at<int32_t>(q_tl),
                        d->gf_out.at<int64_t>(q_ia), d->gf_out.at<int32_t>(q_il), d->gf_out.at<int32_t>(q_ht));
-    hipLaunchKernelGGL(strk_vcf::k_vcf_scan, dim3(1), dim3(256), 0, 0, d->gf_out.at<int32_t>(q_ht), n_hit, d->gf_out.at<int64_t>(q_to));
+    hipLaunchKernelGGL(strk_lines::k_lines_scan, dim3(1), dim3(256), 0, 0, d->gf_out.at<int32_t>(q_ht), n_hit, d->gf_out.at<int64_t>(q_to));
     HIP_TRY(hipMemcpyAsync(d->gf_out.at<char>(q_po), pair_off, ((size_t)n_loci + 1) * 8, hipMemcpyDeviceToDevice, 0));
     HIP_TRY(hipGetLastError());
     d->toc();

@@ -1,6 +1,7 @@
-// strk_vcf.h — candidate SNVs out of VCF text, for host and device: the rule of one line (parse_line), what both entry points
-// do with the kept lines afterwards (finish: one record per position, sortedness, capacities), and the kernels that find the
-// lines of a text resident in HBM and parse them.  strk_vcf.inc has the threads, the buffers and the launches.
+// strk_vcf.h — candidate SNVs out of VCF text, for host and device: the rule of one line (parse_line), the host walk over the
+// lines in slices (snvs_host), what both entry points do with the kept lines afterwards (finish: one record per position,
+// sortedness, capacities), and the kernels that parse the lines of a text resident in HBM.  The lines themselves: strk_lines.h.
+// strk_vcf.inc has the buffers and the launches.
 //
 // Reference: the reader strkit_rust_ext wraps around htslib's tabix access (STRkitVCFReader.get_candidate_snvs, call site
 // strkit/call/call_sample.py:124) — not in the tree.  The rule is the one frontend/snv_vcf.py::read_snv_vcf states
@@ -10,14 +11,16 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <mutex>
+#include <utility>
 #include <vector>
 
 #include "strk_bamrec.h"   // STRK_FE_HD
+#include "strk_lines.h"
 
 namespace strk_vcf {
 
-constexpr int kTileBytes = 1024;    // text bytes one wave walks in the line-split passes (a multiple of kStepBytes)
-constexpr int kStepBytes = 256;     // one aligned 32-bit word per lane and step
 constexpr int kLinesPerWave = 64;   // parse / compaction: one lane per line
 
 // what a line is to the query
@@ -94,6 +97,69 @@ struct Kept {
     std::vector<uint8_t> ref, ids;
 };
 
+// What the host walk gives back, before finish() looks at the capacities.
+struct Walk {
+    Kept kept;
+    int64_t bad_off = -1;   // the first line with a malformed POS
+    int64_t end_off = 0;
+    int32_t past = 0;       // the contig's part of the file is over
+};
+
+// The host walk over t[start, n): lines by strk_lines::split_host, their fields by `par` (a parallel for over [0, n) in slices, in
+// any order, on any threads), then the slices merged in file order.
+template <class Par>
+void snvs_host(const uint8_t* t, int64_t n, int64_t start, const char* contig, int64_t beg, int64_t end, int32_t final, int32_t contig_seen,
+               Walk* out, Par&& par) {
+    const strk_lines::Lines l = strk_lines::split_host(t, n, start, final);
+    out->end_off = l.end_off;
+    const int32_t contig_len = (int32_t)strlen(contig);
+    struct Slice { Kept k; int64_t bad = -1, first_on = -1, last_other = -1; bool past = false; };
+    std::mutex mu;
+    std::vector<std::pair<int32_t, Slice>> slices;
+    par(l.n_lines, [&](int32_t i0, int32_t i1) {
+        Slice s;
+        s.k.id_off.push_back(0);
+        for (int32_t i = i0; i < i1; ++i) {
+            const int64_t a = l.starts[(size_t)i], e = i < l.n_nl ? l.starts[(size_t)i + 1] - 1 : n;
+            const Line r = parse_line(t, a, e, (const uint8_t*)contig, contig_len, beg, end);
+            switch (r.status) {
+            case kBadPos: if (s.bad < 0) s.bad = a; break;
+            case kOther: s.last_other = i; break;
+            case kPast: s.past = true; [[fallthrough]];
+            case kBefore: if (s.first_on < 0) s.first_on = i; break;
+            case kKeep:
+                if (s.first_on < 0) s.first_on = i;
+                s.k.pos.push_back(r.pos); s.k.line.push_back(a); s.k.ref.push_back(r.ref);
+                s.k.ids.insert(s.k.ids.end(), t + r.id_a, t + r.id_a + r.id_len);
+                s.k.id_off.push_back((int64_t)s.k.ids.size());
+                break;
+            default: break;
+            }
+        }
+        std::lock_guard<std::mutex> lk(mu);
+        slices.emplace_back(i0, std::move(s));
+    });
+    std::sort(slices.begin(), slices.end(), [](const auto& x, const auto& y) { return x.first < y.first; });
+    Kept& all = out->kept;
+    all.id_off.push_back(0);
+    int64_t bad = -1, first_on = contig_seen ? 0 : -1, last_other = -1;
+    bool any_past = false;
+    for (auto& [i0, s] : slices) {
+        if (bad < 0) bad = s.bad;
+        if (first_on < 0) first_on = s.first_on;
+        if (s.last_other >= 0) last_other = s.last_other;
+        any_past = any_past || s.past;
+        const int64_t id0 = (int64_t)all.ids.size();
+        all.pos.insert(all.pos.end(), s.k.pos.begin(), s.k.pos.end());
+        all.line.insert(all.line.end(), s.k.line.begin(), s.k.line.end());
+        all.ref.insert(all.ref.end(), s.k.ref.begin(), s.k.ref.end());
+        all.ids.insert(all.ids.end(), s.k.ids.begin(), s.k.ids.end());
+        for (size_t j = 1; j < s.k.id_off.size(); ++j) all.id_off.push_back(id0 + s.k.id_off[j]);
+    }
+    out->bad_off = bad;
+    out->past = (any_past || (first_on >= 0 && (contig_seen ? last_other >= 0 : last_other > first_on))) ? 1 : 0;
+}
+
 struct Message { char text[200]; };
 
 // One record per position (the first in the file stays), sortedness, the first malformed POS (bad_off >= 0: its line), the
@@ -143,82 +209,6 @@ inline int64_t finish(const Kept& k, int64_t bad_off, int64_t prev_pos, int64_t 
 }
 
 #if defined(__HIPCC__)
-
-// ---- line split: count, (scan), scatter ------------------------------------------------------------------------------------
-// Tile w = the tile_bytes text bytes from t0 + w * tile_bytes on (t0 = the start offset rounded down to kStepBytes, so that every
-// word load is aligned); one wave per tile, a lane reads one aligned word per step and the wave ballots each of its four bytes.
-// Only '\n' at offsets in [start, n) count.  A line start is the byte after a '\n'; starts[0] = start itself.
-__device__ inline uint32_t text_word(const uint8_t* data, int64_t n, int64_t p) {
-    return p < n ? *reinterpret_cast<const uint32_t*>(data + p) : 0u;   // (the stream's buffer is padded by 16 bytes)
-}
-
-__global__ void __launch_bounds__(256) k_vcf_count(const uint8_t* data, int64_t n, int64_t start, int32_t tile_bytes, int32_t n_tiles,
-                                                   int32_t* counts) {
-    const int32_t w = (int32_t)(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    if (w >= n_tiles) return;
-    const int64_t base = (start & ~(int64_t)(kStepBytes - 1)) + (int64_t)w * tile_bytes;
-    int32_t cnt = 0;
-    for (int32_t o = 0; o < tile_bytes; o += kStepBytes) {
-        const int64_t p = base + o + 4 * lane;
-        const uint32_t word = text_word(data, n, p);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const bool hit = ((word >> (8 * k)) & 0xffu) == '\n' && p + k >= start && p + k < n;
-            cnt += __popcll(__ballot(hit));
-        }
-    }
-    if (lane == 0) counts[w] = cnt;
-}
-
-// exclusive sums of n counts (one workgroup): off[i] = counts[0] + ... + counts[i - 1], off[n] = the total
-__global__ void __launch_bounds__(256) k_vcf_scan(const int32_t* counts, int32_t n, int64_t* off) {
-    __shared__ int64_t part[256];
-    const int32_t t = threadIdx.x, per = (n + 255) / 256;
-    const int32_t a = min(n, t * per), b = min(n, a + per);
-    int64_t s = 0;
-    for (int32_t i = a; i < b; ++i) s += counts[i];
-    part[t] = s;
-    __syncthreads();
-    if (t == 0) {
-        int64_t run = 0;
-        for (int i = 0; i < 256; ++i) { const int64_t x = part[i]; part[i] = run; run += x; }
-        off[n] = run;
-    }
-    __syncthreads();
-    int64_t run = part[t];
-    for (int32_t i = a; i < b; ++i) { off[i] = run; run += counts[i]; }
-}
-
-__global__ void __launch_bounds__(256) k_vcf_starts(const uint8_t* data, int64_t n, int64_t start, int32_t tile_bytes, int32_t n_tiles,
-                                                    const int64_t* tile_off, int64_t n_starts, int64_t* starts) {
-    const int32_t w = (int32_t)(blockIdx.x * 4 + (threadIdx.x >> 6)), lane = threadIdx.x & 63;
-    if (w >= n_tiles) return;
-    if (w == 0 && lane == 0) starts[0] = start;
-    const int64_t base = (start & ~(int64_t)(kStepBytes - 1)) + (int64_t)w * tile_bytes;
-    const unsigned long long lower = (1ull << lane) - 1ull;
-    int64_t run = 1 + tile_off[w];
-    for (int32_t o = 0; o < tile_bytes; o += kStepBytes) {
-        const int64_t p = base + o + 4 * lane;
-        const uint32_t word = text_word(data, n, p);
-        bool hit[4];
-        int32_t before = 0, total = 0;   // '\n's of the step in lower lanes (all four of their bytes); all of the step's
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            hit[k] = ((word >> (8 * k)) & 0xffu) == '\n' && p + k >= start && p + k < n;
-            const unsigned long long m = __ballot(hit[k]);
-            before += __popcll(m & lower);
-            total += __popcll(m);
-        }
-        int64_t at = run + before;
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (hit[k]) {
-                if (at < n_starts) starts[at] = p + k + 1;
-                ++at;
-            }
-        run += total;
-    }
-}
 
 // ---- parse: one lane per line ---------------------------------------------------------------------------------------------
 // Line i = [starts[i], starts[i + 1] - 1) for i < n_nl; line n_nl (only when n_lines == n_nl + 1: the text ends the file without

@@ -19,7 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from .loci import resolve_contig
-from .snv_vcf import IndexedSnvVcf, _bgzf_block_bytes
+from .tabix_text import TabixText
 
 __all__ = ["Feature", "Annotations", "AnnotationError", "parse_line", "attributes", "feature_id", "read_annotations", "annotate",
            "is_gtf", "IndexedAnnotations", "annotate_rows", "EXON_FEATURE_TYPES"]
@@ -153,63 +153,23 @@ def annotate(loci, source) -> list[list[str]]:
     return out
 
 
-class IndexedAnnotations:
-    """A BGZF-compressed GFF3 / GTF file with its tabix index: `contig_overlaps` walks the contig's byte range once, in pieces of
-    about `piece_bytes` decompressed bytes (a piece resumes at the block that holds the first line the piece before left
-    incomplete), and has the library join every piece against all of the contig's loci — on the device (front_end="device": a
+class IndexedAnnotations(TabixText):
+    """A BGZF-compressed GFF3 / GTF file with its tabix index: `contig_overlaps` walks the contig's byte range once, in pieces
+    (TabixText.walk), and has the library join every piece against all of the contig's loci — on the device (front_end="device": a
     strk_dbam object of its own holds the inflated piece in HBM; strk_dbam_gff_overlaps) or on the host cores
     (strk_bgzf_inflate_range + strk_gff_overlaps).  Counters as IndexedSnvVcf's."""
 
     def __init__(self, path: str, index: str | None = None, front_end: str = "host", device: int = 0, piece_bytes: int = 32 << 20,
                  tile_bytes: int = 0, gtf: bool | None = None):
-        from .tabix import TabixIndex
-        if front_end not in ("host", "device"):
-            raise ValueError(f"front_end must be 'host' or 'device', not {front_end!r}")
-        index = index or path + ".tbi"
+        super().__init__(path, index or path + ".tbi", front_end, device, piece_bytes, tile_bytes, "gff")
+        self.gtf = is_gtf(path) if gtf is None else bool(gtf)
+
+    def _precondition(self, path: str, index: str) -> None:
         with open(path, "rb") as fh:
             head = fh.read(18)
         if not (len(head) == 18 and head[:4] == b"\x1f\x8b\x08\x04" and head[12:14] == b"BC") or not os.path.exists(index):
             raise ValueError(f"{path}: an annotation file must be BGZF-compressed with a tabix index next to it ({index}); "
                              f"bgzip the sorted file and run `tabix -p gff` on it")
-        self.path, self.front_end, self.piece_bytes, self.tile_bytes = path, front_end, int(piece_bytes), int(tile_bytes)
-        self.gtf = is_gtf(path) if gtf is None else bool(gtf)
-        self.index = TabixIndex(index, path, preset="gff")
-        self.comp = np.memmap(path, np.uint8, "r")
-        self.compressed_bytes = 0        # compressed bytes inflated so far (a block inflated twice counts twice)
-        self.n_queries = 0
-        self.seconds = 0.0
-        self.text_bytes = 0              # decompressed bytes handed to the parser
-        self.kernel_ms = [0.0, 0.0]      # device: HIP-event time of the inflation kernel, of the line / join / id kernels
-        self._h = None
-        if front_end == "device":
-            from .. import _lib
-            h = C.c_void_p()
-            _lib.check(_lib.load().strk_dbam_open(int(device), C.byref(h)))
-            self._h = h
-
-    @property
-    def references(self) -> list[str]:
-        return list(self.index.names)
-
-    def kernel_s(self) -> float:
-        from .. import _lib
-        return float(_lib.load().strk_dbam_kernel_ms(self._h)) / 1e3 if self._h is not None else 0.0
-
-    def close(self) -> None:
-        if self._h is not None:
-            from .. import _lib
-            _lib.load().strk_dbam_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    # the blocks of a piece, and whether only empty blocks follow: IndexedSnvVcf's (they look at self.comp only)
-    _piece = IndexedSnvVcf._piece
-    _only_empty = IndexedSnvVcf._only_empty
 
     def _join(self, L, buf, n, start, name, final, prev, ls, le):
         """One library call over a piece, with the arrays grown to what it asks for -> (pair_locus, pair_feat, ids of the hit
@@ -266,49 +226,15 @@ class IndexedAnnotations:
         self.n_queries += 1
         order = np.argsort(starts, kind="stable")
         ls, le = np.ascontiguousarray(starts[order]), np.ascontiguousarray(ends[order])
-        voff, last = rng
-        coff, start = voff >> 16, voff & 0xFFFF
-        limit = min(self.comp.size, last + _bgzf_block_bytes(self.comp, last)[0]) if last < self.comp.size else self.comp.size
-        want, prev = self.piece_bytes, -1
-        buf = None
-        while coff < limit:
-            coffs, outs, nxt = self._piece(coff, limit, want)
-            n = outs[-1]
-            self.compressed_bytes += nxt - coff
-            got = C.c_int64(0)
-            if self._h is not None:
-                ms0 = L.strk_dbam_kernel_ms(self._h)
-                r = L.strk_dbam_inflate(self._h, self.comp.ctypes.data, nxt, coff, max(n, 1), C.byref(got))
-                ms1 = L.strk_dbam_kernel_ms(self._h)
-                self.kernel_ms[0] += ms1 - ms0
-            else:
-                if buf is None or buf.size < n + 16:
-                    buf = np.empty(n + 16, np.uint8)
-                r = L.strk_bgzf_inflate_range(self.comp.ctypes.data, nxt, coff, buf.ctypes.data, buf.size, C.byref(got), 0)
-            if r < 0:
-                _lib.check(int(r))
-            if int(r) != n or got.value != nxt:
-                raise ValueError(f"{self.path}: the blocks at byte {coff} inflate to {int(r)} bytes, their headers say {n}")
-            final = int(self._only_empty(nxt))
-            self.text_bytes += n - start
-            try:
-                pl, pf, ids, prev, end_off, past = self._join(L, buf, n, start, name.encode(), final, prev, ls, le)
-            except _lib.StrkError as e:
-                raise _lib.StrkError(e.code, f"{self.path} (text inflated from compressed byte {coff}): {e}") from None
-            if self._h is not None:
-                self.kernel_ms[1] += L.strk_dbam_kernel_ms(self._h) - ms1
+        prev = [-1]         # the last f_beg of the contig so far
+
+        def consume(buf, n, start, final):
+            pl, pf, ids, prev[0], end_off, past = self._join(L, buf, n, start, name.encode(), final, prev[0], ls, le)
             for l, j in zip(order[pl].tolist(), pf.tolist()):      # pieces come in file order, so do a locus's ids
                 out[l].append(ids[j])
-            if past or nxt >= limit:
-                break
-            if end_off >= n:                # the piece ended on a line end
-                coff, start, want = nxt, 0, self.piece_bytes
-                continue
-            b = int(np.searchsorted(outs[:-1], end_off, side="right")) - 1
-            if coffs[b] == coff and end_off - outs[b] == start:
-                want = max(2 * want, 2 * n)     # not one complete line in the piece: a longer one
-            else:
-                coff, start, want = coffs[b], end_off - outs[b], self.piece_bytes
+            return end_off, past
+
+        self.walk(rng, consume)
         self.seconds += time.perf_counter() - t0
         return out
 

@@ -8,13 +8,13 @@ from __future__ import annotations
 import ctypes as C
 import gzip
 import os
-import struct
 import time
 from dataclasses import dataclass
 
 import numpy as np
 
 from .loci import resolve_contig
+from .tabix_text import TabixText
 
 __all__ = ["SnvCandidates", "read_snv_vcf", "IndexedSnvVcf", "open_snv_candidates"]
 
@@ -99,84 +99,15 @@ class _Column:
         return list(self) == list(other)
 
 
-def _bgzf_block_bytes(comp: np.ndarray, off: int) -> tuple[int, int]:
-    """(compressed size, decompressed size) of the BGZF block at compressed offset `off`."""
-    if off + 18 > comp.size or comp[off] != 0x1F or comp[off + 1] != 0x8B or not comp[off + 3] & 4:
-        raise ValueError(f"not a BGZF block at byte {off}")
-    xlen = int(comp[off + 10]) | int(comp[off + 11]) << 8
-    x, bsize = off + 12, -1
-    while x + 4 <= off + 12 + xlen <= comp.size:
-        slen = int(comp[x + 2]) | int(comp[x + 3]) << 8
-        if comp[x] == 66 and comp[x + 1] == 67 and slen == 2:
-            bsize = int(comp[x + 4]) | int(comp[x + 5]) << 8
-        x += 4 + slen
-    if bsize < 0 or off + bsize + 1 > comp.size:
-        raise ValueError(f"truncated BGZF block at byte {off}")
-    isize, = struct.unpack("<I", comp[off + bsize - 3:off + bsize + 1].tobytes())
-    return bsize + 1, isize
-
-
-class IndexedSnvVcf:
+class IndexedSnvVcf(TabixText):
     """Region access to a BGZF-compressed VCF through its tabix index, the reference's per-block query (call_sample.py:124):
     `window` inflates the BGZF blocks the index names for [beg, end) and has the library turn their text into candidate arrays
     — on the device (front_end="device": a strk_dbam object of its own holds the inflated piece in HBM; strk_dbam_vcf_snvs) or
-    on the host cores (strk_bgzf_inflate_range + strk_vcf_snvs).  A range is walked in pieces of about `piece_bytes`
-    decompressed bytes; a piece resumes at the block that holds the first line the piece before left incomplete."""
+    on the host cores (strk_bgzf_inflate_range + strk_vcf_snvs).  The range is walked in pieces (TabixText.walk)."""
 
     def __init__(self, path: str, index: str | None = None, front_end: str = "host", device: int = 0, piece_bytes: int = 32 << 20,
                  tile_bytes: int = 0):
-        from .tabix import TabixIndex
-        if front_end not in ("host", "device"):
-            raise ValueError(f"front_end must be 'host' or 'device', not {front_end!r}")
-        self.path, self.front_end, self.piece_bytes, self.tile_bytes = path, front_end, int(piece_bytes), int(tile_bytes)
-        self.index = TabixIndex(index or path + ".tbi", path)
-        self.comp = np.memmap(path, np.uint8, "r")
-        self.compressed_bytes = 0        # compressed bytes inflated so far (a block inflated twice counts twice)
-        self.n_queries = 0
-        self.seconds = 0.0
-        self.text_bytes = 0              # decompressed bytes handed to the parser
-        self.kernel_ms = [0.0, 0.0]      # device: HIP-event time of the inflation kernel, of the VCF kernels
-        self._h = None
-        if front_end == "device":
-            from .. import _lib
-            h = C.c_void_p()
-            _lib.check(_lib.load().strk_dbam_open(int(device), C.byref(h)))
-            self._h = h
-
-    @property
-    def references(self) -> list[str]:
-        return list(self.index.names)
-
-    def kernel_s(self) -> float:
-        from .. import _lib
-        return float(_lib.load().strk_dbam_kernel_ms(self._h)) / 1e3 if self._h is not None else 0.0
-
-    def close(self) -> None:
-        if self._h is not None:
-            from .. import _lib
-            _lib.load().strk_dbam_close(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _piece(self, coff: int, limit: int, want: int) -> tuple[list[int], list[int], int]:
-        """The blocks from `coff` on that a piece takes: at least one, then as long as the piece stays within `want` decompressed
-        bytes and below `limit` -> (their compressed offsets, where each starts in the piece, the offset of the next block)."""
-        coffs, outs, total = [], [], 0
-        while coff < limit:
-            csize, isize = _bgzf_block_bytes(self.comp, coff)
-            if coffs and total + isize > want:
-                break
-            coffs.append(coff)
-            outs.append(total)
-            total += isize
-            coff += csize
-        outs.append(total)
-        return coffs, outs, coff
+        super().__init__(path, index or path + ".tbi", front_end, device, piece_bytes, tile_bytes, "vcf")
 
     def _parse(self, L, buf, n, start, name, beg, end, final, prev, seen):
         """One library call over a piece, with the arrays grown to what it asks for -> (pos, ref, id_off, ids, end_off, past)."""
@@ -213,56 +144,21 @@ class IndexedSnvVcf:
         self.n_queries += 1
         beg, end = max(0, int(beg)), max(0, int(end))
         parts = []
+        state = [-1, 0]     # the last position reported; whether a record of the contig was seen
+
+        def consume(buf, n, start, final):
+            pos, ref, id_off, ids, end_off, past = self._parse(L, buf, n, start, name.encode(), beg, end, final, state[0], state[1])
+            if len(pos):
+                parts.append((pos, ref, id_off, ids))
+                state[0] = int(pos[-1])
+            # (a record of the contig seen: only through one that was kept or lies past the window; one in front of it keeps
+            # the walk going, which is all `seen` is for)
+            state[1] = int(state[1] or len(pos) > 0)
+            return end_off, past
+
         rng = self.index.block_range(name, beg, end)
         if rng is not None:
-            voff, last = rng
-            coff, start = voff >> 16, voff & 0xFFFF
-            limit = min(self.comp.size, last + _bgzf_block_bytes(self.comp, last)[0]) if last < self.comp.size else self.comp.size
-            want, prev, seen = self.piece_bytes, -1, 0
-            buf = None
-            while coff < limit:
-                coffs, outs, nxt = self._piece(coff, limit, want)
-                n = outs[-1]
-                self.compressed_bytes += nxt - coff
-                got = C.c_int64(0)
-                if self._h is not None:
-                    ms0 = L.strk_dbam_kernel_ms(self._h)
-                    r = L.strk_dbam_inflate(self._h, self.comp.ctypes.data, nxt, coff, max(n, 1), C.byref(got))
-                    ms1 = L.strk_dbam_kernel_ms(self._h)
-                    self.kernel_ms[0] += ms1 - ms0
-                else:
-                    if buf is None or buf.size < n + 16:
-                        buf = np.empty(n + 16, np.uint8)
-                    r = L.strk_bgzf_inflate_range(self.comp.ctypes.data, nxt, coff, buf.ctypes.data, buf.size, C.byref(got), 0)
-                if r < 0:
-                    _lib.check(int(r))
-                if int(r) != n or got.value != nxt:
-                    raise ValueError(f"{self.path}: the blocks at byte {coff} inflate to {int(r)} bytes, their headers say {n}")
-                # the text ends its file when nothing but empty blocks (the EOF marker) follows
-                final = int(self._only_empty(nxt))
-                self.text_bytes += n - start
-                try:
-                    pos, ref, id_off, ids, end_off, past = self._parse(L, buf, n, start, name.encode(), beg, end, final, prev, seen)
-                except _lib.StrkError as e:
-                    raise _lib.StrkError(e.code, f"{self.path} (text inflated from compressed byte {coff}): {e}") from None
-                if self._h is not None:
-                    self.kernel_ms[1] += L.strk_dbam_kernel_ms(self._h) - ms1
-                if len(pos):
-                    parts.append((pos, ref, id_off, ids))
-                    prev = int(pos[-1])
-                # (a record of the contig seen: only through one that was kept or lies past the window; one in front of it keeps
-                # the walk going, which is all `seen` is for)
-                seen = int(seen or len(pos) > 0)
-                if past or nxt >= limit:        # (a line cut off by the range's last block begins past every wanted record)
-                    break
-                if end_off >= n:                # the piece ended on a line end
-                    coff, start, want = nxt, 0, self.piece_bytes
-                    continue
-                b = int(np.searchsorted(outs[:-1], end_off, side="right")) - 1
-                if coffs[b] == coff and end_off - outs[b] == start:
-                    want = max(2 * want, 2 * n)     # not one complete line in the piece: a longer one
-                else:
-                    coff, start, want = coffs[b], end_off - outs[b], self.piece_bytes
+            self.walk(rng, consume)
         self.seconds += time.perf_counter() - t0
         if not parts:
             z = np.zeros(0, np.int64)
@@ -273,14 +169,6 @@ class IndexedSnvVcf:
         base = np.cumsum([0] + [len(p[3]) for p in parts])
         id_off = np.concatenate([p[2][:-1] + base[i] for i, p in enumerate(parts)] + [base[-1:]]).astype(np.int64)
         return ContigSnvs(pos, _Column(ids, id_off), _Column(ref, np.arange(len(ref) + 1, dtype=np.int64)))
-
-    def _only_empty(self, coff: int) -> bool:
-        while coff < self.comp.size:
-            csize, isize = _bgzf_block_bytes(self.comp, coff)
-            if isize:
-                return False
-            coff += csize
-        return True
 
 
 def open_snv_candidates(path: str, front_end: str = "host", device: int = 0):

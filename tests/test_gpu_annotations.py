@@ -1,4 +1,4 @@
-"""GPU: strk_dbam_gff_overlaps (k_vcf_count / k_vcf_scan / k_vcf_starts, k_gff_coords, k_gff_gather, k_gff_classes, k_gff_join,
+"""GPU: strk_dbam_gff_overlaps (k_lines_count / k_lines_scan / k_lines_starts of strk_lines.h, k_gff_coords, k_gff_gather, k_gff_classes, k_gff_join,
 k_gff_hits, k_gff_order, k_gff_ids, k_gff_text) on the corpus of annot_cases.py: identical to frontend/annotations.py's rule on every
 case, with the default tile and with tile_bytes = 256; the refusals match the host's; the device IndexedAnnotations equals the host one
 on the synth_annot files; one end-to-end `call --front-end device --gff` equals the host front end's report."""

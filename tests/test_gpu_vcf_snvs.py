@@ -1,4 +1,4 @@
-"""GPU: strk_dbam_vcf_snvs (k_vcf_count / k_vcf_scan / k_vcf_starts / k_vcf_parse / k_vcf_compact) on the corpus of vcf_cases.py:
+"""GPU: strk_dbam_vcf_snvs (k_lines_count / k_lines_scan / k_lines_starts of strk_lines.h, k_vcf_parse / k_vcf_compact) on the corpus of vcf_cases.py:
 identical to the host twin (strk_vcf_snvs) and to read_snv_vcf on every case and window, for both tile sizes, over whole files,
 whole index ranges and one-block pieces; the refusals match."""
 import ctypes as C

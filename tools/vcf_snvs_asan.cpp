@@ -1,10 +1,12 @@
-// The host side of the candidate-SNV reader (strk_vcf.h: the rule of one line, the closing pass with its capacities) over the corpus
+// The host side of the candidate-SNV reader (strk_vcf.h: the rule of one line, the host walk with its slice merge, the closing pass
+// with its capacities; strk_lines.h: the lines) over the corpus
 // of tests/vcf_cases.py and over every truncation of every corpus text at every byte length.  Every text is a heap block of
 // exactly its length, so a read one byte past a line, a field or the text is reported under AddressSanitizer / UBSan
 // (tools/vcf_snvs_asan.sh); tests/test_vcf_snvs_host.py builds it plain and requires exit 0.
 //   vcf_snvs_asan <directory written by vcf_cases.dump()>
 // Per window of a case (<name>.q: contig beg end start, then the expected positions or "refuse"): the whole text must give the
-// expected positions; a truncation, read as a piece (not final), must give a prefix of them and an end_off on a line start.
+// expected positions; a truncation, read as a piece (not final), must give a prefix of them and an end_off on a line start.  Every
+// text is walked twice, as one slice and in slices of three lines, which must agree in everything.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -30,39 +32,42 @@ void expect(bool ok, const char* what, const std::string& where, long long detai
     }
 }
 
-struct Result { int64_t n = 0, end_off = 0; bool refused = false; std::vector<int64_t> pos; std::vector<uint8_t> ref, ids; std::vector<int64_t> id_off; };
+struct Result {
+    int64_t n = 0, end_off = 0;
+    int32_t past = 0;
+    bool refused = false;
+    std::vector<int64_t> pos;
+    std::vector<uint8_t> ref, ids;
+    std::vector<int64_t> id_off;
+    bool operator==(const Result& o) const {
+        return n == o.n && end_off == o.end_off && past == o.past && refused == o.refused && pos == o.pos && ref == o.ref && ids == o.ids && id_off == o.id_off;
+    }
+};
 
-// the walk of strk_vcf_snvs on one thread: lines by memchr, parse_line, finish into arrays of exactly the size asked for
-Result run(const uint8_t* t, int64_t n_bytes, int64_t start, const std::string& contig, int64_t beg, int64_t end, bool final) {
+// strk_vcf_snvs with `par` for its threads: snvs_host, then finish twice (the size query, then arrays of exactly those sizes)
+template <class Par>
+Result run_par(const uint8_t* t, int64_t n_bytes, int64_t start, const std::string& contig, int64_t beg, int64_t end, bool final, Par&& par) {
     Result r;
-    std::vector<int64_t> starts{start};
-    for (int64_t p = start; p < n_bytes;) {
-        const void* nl = memchr(t + p, '\n', (size_t)(n_bytes - p));
-        if (!nl) break;
-        p = (const uint8_t*)nl - t + 1;
-        starts.push_back(p);
-    }
-    const int64_t n_nl = (int64_t)starts.size() - 1, n_lines = n_nl + ((final && starts.back() < n_bytes) ? 1 : 0);
-    r.end_off = n_lines > n_nl ? n_bytes : starts.back();
-    strk_vcf::Kept k;
-    k.id_off.push_back(0);
-    int64_t bad = -1;
-    for (int64_t i = 0; i < n_lines; ++i) {
-        const int64_t a = starts[(size_t)i], e = i < n_nl ? starts[(size_t)i + 1] - 1 : n_bytes;
-        const strk_vcf::Line ln = strk_vcf::parse_line(t, a, e, (const uint8_t*)contig.data(), (int32_t)contig.size(), beg, end);
-        if (ln.status == strk_vcf::kBadPos && bad < 0) bad = a;
-        if (ln.status != strk_vcf::kKeep) continue;
-        k.pos.push_back(ln.pos); k.line.push_back(a); k.ref.push_back(ln.ref);
-        k.ids.insert(k.ids.end(), t + ln.id_a, t + ln.id_a + ln.id_len);
-        k.id_off.push_back((int64_t)k.ids.size());
-    }
+    strk_vcf::Walk w;
+    strk_vcf::snvs_host(t, n_bytes, start, contig.c_str(), beg, end, final ? 1 : 0, 0, &w, par);
+    r.end_off = w.end_off; r.past = w.past;
     strk_vcf::Message msg;
     int64_t id_bytes = 0, none[1];
-    const int64_t n = strk_vcf::finish(k, bad, -1, 0, nullptr, nullptr, none, nullptr, 0, &id_bytes, &msg);   // the size query
+    const int64_t n = strk_vcf::finish(w.kept, w.bad_off, -1, 0, nullptr, nullptr, none, nullptr, 0, &id_bytes, &msg);   // the size query
     if (n < 0) { r.refused = true; return r; }
     r.pos.resize((size_t)n); r.ref.resize((size_t)n); r.id_off.resize((size_t)n + 1); r.ids.resize((size_t)id_bytes);
-    r.n = strk_vcf::finish(k, bad, -1, n, r.pos.data(), r.ref.data(), r.id_off.data(), r.ids.data(), id_bytes, &id_bytes, &msg);
+    r.n = strk_vcf::finish(w.kept, w.bad_off, -1, n, r.pos.data(), r.ref.data(), r.id_off.data(), r.ids.data(), id_bytes, &id_bytes, &msg);
     return r;
+}
+
+// one slice, then slices of three lines handed over last to first (the merge has to order them): both must give the same
+Result run(const uint8_t* t, int64_t n_bytes, int64_t start, const std::string& contig, int64_t beg, int64_t end, bool final, const std::string& where) {
+    const Result one = run_par(t, n_bytes, start, contig, beg, end, final, [](int32_t m, auto&& body) { body(0, m); });
+    const Result sliced = run_par(t, n_bytes, start, contig, beg, end, final, [](int32_t m, auto&& body) {
+        for (int32_t i0 = (m - 1) / 3 * 3; m > 0 && i0 >= 0; i0 -= 3) body(i0, std::min(m, i0 + 3));
+    });
+    expect(one == sliced, "slices of three lines give what one slice gives", where, (long long)n_bytes);
+    return one;
 }
 
 std::vector<uint8_t> slurp(const std::string& path) {
@@ -103,7 +108,7 @@ int main(int argc, char** argv) {
             // the whole text, in a block of exactly its length
             uint8_t* whole = (uint8_t*)malloc(text.size() ? text.size() : 1);
             memcpy(whole, text.data(), text.size());
-            const Result full = run(whole, (int64_t)text.size(), start, contig, beg, end, true);
+            const Result full = run(whole, (int64_t)text.size(), start, contig, beg, end, true, name + " " + row);
             free(whole);
             expect(full.refused == refuse, "refusal", name + " " + row);
             g_refusals += full.refused;
@@ -116,7 +121,7 @@ int main(int argc, char** argv) {
                 uint8_t* cut = (uint8_t*)malloc(len ? len : 1);
                 memcpy(cut, text.data(), len);
                 for (int final = 0; final < 2; ++final) {
-                    const Result r = run(cut, (int64_t)len, start, contig, beg, end, final != 0);
+                    const Result r = run(cut, (int64_t)len, start, contig, beg, end, final != 0, name + " " + row);
                     if (r.refused) { ++g_refusals; continue; }
                     bool ok = r.end_off >= start && r.end_off <= (int64_t)len && (final ? r.end_off == (int64_t)len : (r.end_off == start || cut[r.end_off - 1] == '\n'));
                     expect(ok, "end_off of a truncation", name + " " + row, (long long)len);

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The rule of a VCF line and the closing pass of strk_vcf.h under AddressSanitizer + UBSan on the host (no GPU needed), over the
+# The rule of a VCF line, the host walk (as one slice and in slices of three lines) and the closing pass of strk_vcf.h under AddressSanitizer + UBSan on the host (no GPU needed), over the
 # corpus of tests/vcf_cases.py and every truncation of its texts.
 set -e
 D=${TMPDIR:-/tmp}/strk_vcf_snvs_asan
