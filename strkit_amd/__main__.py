@@ -161,6 +161,10 @@ def main(argv=None) -> int:
         ap.error(f"--gff {a.annotation_file}: the file and its tabix index ({a.annotation_file}.tbi) must exist")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1:   # python -m torch.distributed.run --nproc-per-node N -m strkit_amd call ...: one rank per GPU
+        from .frontend.gather import SHARDING_REFUSALS
+        for name in SHARDING_REFUSALS:      # before the process group is made, in the words of call_sample's refusals
+            if getattr(a, name):
+                ap.error(SHARDING_REFUSALS[name])
         import torch
         import torch.distributed as dist
         local = int(os.environ.get("LOCAL_RANK", "0"))

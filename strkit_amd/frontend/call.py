@@ -4,7 +4,6 @@ per-locus path is in block.py.  SNV phasing, haplotags and partial-order alignme
 from __future__ import annotations
 
 import dataclasses
-import gc
 import itertools
 import json
 import sys
@@ -18,7 +17,7 @@ from .. import _lib
 from .bam import BamFile
 from .block import _call_block_native, _call_block_python, _locus_dict, _locus_row  # noqa: F401 (the last two: as before)
 from .fasta import Fasta
-from .gather import _distributed, call_blocks_sharded, deal_locus_blocks
+from .gather import SHARDING_REFUSALS, _collector_paused, _distributed, call_blocks_sharded, deal_locus_blocks, shared_seed
 from .loci import Locus, load_loci, resolve_contig
 from .native import DeviceBam, IndexedBam, NativeBam
 from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, AnnotationCallOptions, CallOptions, MethylCallOptions, PhasedCallOptions, PhaseSetCallOptions, PloidyCallOptions, PoaCallOptions, ReadSelectionCallOptions,
@@ -58,20 +57,17 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, *, sample_
     `front_end` (for a `bam` given as a path): "device" = the file is inflated, scanned and cut on the GPU (DeviceBam), whole or
     in spans of at most `span_bytes` compressed bytes; "host" = on the host cores (IndexedBam, or NativeBam without an index);
     "auto" = "device" where that is possible (reader.choose_reader has the rule, reader.BackgroundOpener the retry when device
-    memory runs out).  Under torch.distributed every rank opens the file on its own GPU and calls its share of the blocks."""
+    memory runs out).  Under torch.distributed every rank opens the file on its own GPU and calls its share of the blocks, genotypes
+    included; `seed=None` is then drawn by rank 0 and broadcast, so that every rank calls with one seed and reports
+    it: the seed of a locus is locus_seeds(run seed, t_idx), so a call does not depend on which rank owns its locus.
+    `snv_phase_sets` and `use_methyl` are refused there (NotImplementedError), before a file is opened."""
     opts = with_keywords(opts, **option_keywords)
+    for name, why in SHARDING_REFUSALS.items():
+        if getattr(opts, name, False) and _distributed():
+            raise NotImplementedError(why)
     if opts.call_alleles and opts.seed is None:
-        opts = dataclasses.replace(opts, seed=int(np.random.default_rng().integers(0, 1 << 63)))
+        opts = dataclasses.replace(opts, seed=shared_seed() if _distributed() else int(np.random.default_rng().integers(0, 1 << 63)))
     opts.validate()
-    if opts.count_kmers != "none" and _distributed():
-        raise NotImplementedError("count_kmers under torch.distributed: the fixed-size records that the ranks gather "
-                                  "(call_blocks_sharded) have no fields for k-mer counts yet; run one process")
-    if opts.call_alleles and _distributed():
-        raise NotImplementedError("call_alleles=True under torch.distributed: the fixed-size records that the ranks gather "
-                                  "(call_blocks_sharded) have no fields for calls and sequences yet; run one process")
-    if getattr(opts, "use_methyl", False) and _distributed():
-        raise NotImplementedError("use_methyl=True under torch.distributed: the fixed-size records that the ranks gather "
-                                  "(call_blocks_sharded) have no fields for methylation yet; run one process")
     t_open = time.perf_counter()
     own_reader = isinstance(bam, str)
     # a path: a host reader at once, or a device reader that opens in the background
@@ -103,7 +99,13 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, *, sample_
         print(f"strkit_amd: {n_catalog - n_loaded} of {n_catalog} catalog loci lie on contigs that the alignment file or "
               f"the reference does not have; they are not called", file=sys.stderr)
 
-    run = lambda bl: call_blocks(bl, bam, ref, opts, ctx, ref_cache=ref_cache)  # noqa: E731
+    def run(bl):
+        if not (_distributed() and getattr(opts, "use_hp", False)):
+            return call_blocks(bl, bam, ref, opts, ctx, ref_cache=ref_cache)
+        ps_ids: dict = {}       # this rank numbers the phase sets it meets; the gather needs the values the numbers stand for
+        rows, n, tm_ = call_blocks(bl, bam, ref, opts, ctx, ref_cache=ref_cache, ps_ids=ps_ids)
+        return rows, n, {**tm_, "ps_ids": ps_ids}
+
     try:
         if _distributed():          # launched under torch.distributed (one rank per GPU): shard the blocks
             # a reader that loads what its blocks need (spans of the file / blocks through the index) gets ONE run of
@@ -143,20 +145,6 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, *, sample_
             "errors": errors,
             "avg_read_depth": n_depth / max(1, sum(1 for r in results if "reads" in r)),
             "runtime": time.perf_counter() - t0, "stage_times": {k: (round(v, 4) if isinstance(v, float) else v) for k, v in tm.items()}}
-
-
-@contextmanager
-def _collector_paused():
-    # The report is hundreds of thousands of small dicts that reference nothing but strings and numbers: the cyclic collector
-    # finds nothing in them and costs a third of the time it takes to build them (it runs every 700 new containers, and its
-    # older generations grow with the report).  It is paused while the blocks run, and left as it was found.
-    was_on = gc.isenabled()
-    gc.disable()
-    try:
-        yield
-    finally:
-        if was_on:
-            gc.enable()
 
 
 @contextmanager
@@ -217,11 +205,13 @@ class _PrefetchFeed:
         self.pool.shutdown(wait=True)
 
 
-def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = None, ctx=None, ref_cache: dict | None = None):
+def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = None, ctx=None, ref_cache: dict | None = None,
+                ps_ids: dict | None = None):
     """Worker loop over blocks of loci (strkit/call/call_sample.py:103-197): (results in locus order, reads kept,
     stage times).  An error of the library inside a block is handled the way the reference's worker handles any
     exception of call_locus (call_sample.py:159-166: logged, the locus is dropped, the run goes on): the block is
-    re-run locus by locus so that only the locus that fails is lost; `stage times["errors"]` lists them."""
+    re-run locus by locus so that only the locus that fails is lost; `stage times["errors"]` lists them.  `ps_ids` (a dict,
+    with use_hp): filled with {phase-set number in the rows: original PS value, -1 for reads with HP and no PS}."""
     opts = opts or CallOptions()
     opts.validate()
     blocks, _ = ploidy_blocks(blocks, opts)
@@ -282,6 +272,8 @@ def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = Non
             if sets is not None:
                 sets.finish_contig(results[first_row:])
                 tm["phase_sets_s"] = sets.seconds
+            if ps_ids is not None and phase_run is not None:
+                ps_ids.update(phase_run.remap.originals())
     results.sort(key=lambda r: r["locus_index"])
     return results, n_depth, tm
 

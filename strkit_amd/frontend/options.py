@@ -33,7 +33,7 @@ class CallOptions:
     tie_rule: int = _lib.STRK_TIE_FIRST
     end_flags: int = _lib.STRK_SG_ALL
     narrowing: int = _lib.STRK_NARROW_NONE
-    # genotypes (off by default; not under torch.distributed yet).  `call_alleles`: a genotype per locus (call, intervals,
+    # genotypes (off by default).  `call_alleles`: a genotype per locus (call, intervals,
     # peaks, a peak label `p` per read) from the GPU allele caller, with the locus seed alleles.locus_seed(seed, locus index).
     # `consensus` (needs call_alleles): the sequence of every allele and of its start anchor as peaks.seqs /
     # peaks.start_anchor_seqs.  `seed`: the run seed (an int once a run has started).  `n_alleles`: 1 or 2, for all contigs or

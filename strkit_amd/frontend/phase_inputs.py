@@ -214,6 +214,10 @@ class PhaseSetRemap:
     def clear(self) -> None:
         self._ids.clear()
 
+    def originals(self) -> dict[int, int]:
+        """{number handed out: the original value it stands for (-1: HP without PS)}."""
+        return {number: value for value, number in self._ids.items()}
+
     def snapshot(self) -> dict:
         """The ids handed out so far; restore() puts them back (a block that failed is run again and numbers its phase sets anew)."""
         return dict(self._ids)
