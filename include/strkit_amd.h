@@ -181,6 +181,21 @@ int strk_band_list(strk_ctx* ctx, int32_t band_class, int32_t* out_reads, int32_
 int32_t strk_classify(int32_t nfl, int32_t ntr, int32_t nfr, int32_t m, int32_t lo, int32_t n, int32_t force_generic, int32_t ref_mode);
 void strk_score_constants(int32_t* out, int32_t cap);
 int strk_class_counts(strk_ctx* ctx, int32_t* out, int32_t cap);
+/* Test support for the band pass ("Band path: seam corpus"): what k_dp_band and k_dp_band_wide write, on HOST buffers.
+ * Plans the batch as a counting call does (candidate window est_cn +- params->window, which must be > 0: the adaptive default is
+ * not consulted) with the band on for every read (no probation, no dedupe) and the band placement tune[3] = {span_w, slack_m8,
+ * max_m} (all zeros: the library's defaults), runs the planning kernel and the two band kernels and nothing behind them (no
+ * replay pass, no exact kernel), and returns per read r the window (out_lo[r], out_n[r]), out_class[r] and, for a read a band
+ * class scored, the band scores and their bounds in out_scores / out_ub[r * table_stride .. + out_n[r]).  out_class: 0..7 the band
+ * class that scored the read; -1 the band geometry refuses it; -2 the band kernel handed it on for a symbol outside its six fixed
+ * classes; the rows of both kinds are left as the caller filled them.  flags & 1: order the wide classes longest first (two more
+ * kernels) as a counting call may.  Only params->window and params->end_flags are used.  The context's band probation, grid
+ * history and the process's window level are neither read nor changed; the call does use the context's workspace, staging
+ * buffer and class lists like any scoring call, so strk_band_list afterwards reports THIS call's lists (strk_class_counts keeps
+ * the counters of the last finished scoring call).  Refuses a context with a submitted call pending. */
+int strk_band_tables(strk_ctx* ctx, const strk_batch* batch, const strk_params* params, const int32_t* tune, int32_t flags,
+                     int32_t* out_lo, int32_t* out_n, int32_t* out_class, int32_t table_stride, int32_t* out_scores,
+                     int32_t* out_ub, strk_stats* stats);
 /* Forget what the library has learnt about the current sample (the default candidate-window level per motif-length bucket,
  * process-wide): call it when a process moves on to ANOTHER sample (the reference runs one sample per process,
  * call_sample.py:265).  Per-context state (band probation, grid history) goes with strk_destroy. */

@@ -29,7 +29,7 @@ _i64p = C.POINTER(C.c_int64)
 
 def build(force: bool = False) -> str:
     src = os.path.join(_HERE, "strk_oracle.c")
-    newest = max(os.path.getmtime(src), os.path.getmtime(os.path.join(_HERE, "strk_simd.c")))
+    newest = max(os.path.getmtime(src), os.path.getmtime(os.path.join(_HERE, "strk_simd.c")), os.path.getmtime(os.path.join(_HERE, "strk_band.c")))
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < newest:
         subprocess.check_call(["make", "-C", _HERE, "-B", "libstrk_oracle.so"], stdout=subprocess.DEVNULL)
     return _SO
@@ -61,6 +61,8 @@ def lib():
                                      C.POINTER(C.c_uint32), C.c_int32]
         L.strk_o_realign.restype = C.c_int32
         L.strk_o_ref_repeat_count.argtypes = ([C.c_int32] + [_u8p, C.c_int32] * 4 + [C.c_int32] * 8 + [_i32p])
+        L.strk_o_band_scores.restype = C.c_int
+        L.strk_o_band_scores.argtypes = [_u8p] + [C.c_int32] * 3 + [_u8p] + [C.c_int32] * 11 + [_i32p, _i32p]
         L.strk_o_set_simd.restype = C.c_int
         L.strk_o_set_simd.argtypes = [C.c_int]
         L.strk_o_simd_available.restype = C.c_int
@@ -177,6 +179,23 @@ def realign(s1, s2, open_: int = 7, ext: int = 0, gap_pref: int = 0):
     if n < 0:
         raise ValueError("realign: empty input" if n == -2 else "realign: CIGAR capacity")
     return sc.value, e2.value, np.frombuffer(cig, dtype=np.uint32, count=n).copy()
+
+
+BAND_NONE = -(2 ** 31)
+
+
+def band_scores(fl, tr, fr, motif, lo: int, n: int, geo: dict, lmax: bool, flags: int = SG_ALL, with_top: bool = False):
+    """The banded first pass restated (strk_band.c): S_band of the candidates lo .. lo + n - 1 inside the bands of `geo`
+    (dlo, wd, bdlo, bwd, cmin, ncol: band_geometry's, from the caller); BAND_NONE where no cell of both bands exists.
+    with_top: also, per entry, the fork row's cell on the band's last diagonal completed by gaps (strk_band.c: out_top)."""
+    bd, nd = _b(fl + tr + fr)
+    bm, nm = _b(motif)
+    out, top = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    rc = lib().strk_o_band_scores(bd, nd, len(fl), len(fr), bm, nm, lo, n, geo["dlo"], geo["wd"], geo["bdlo"], geo["bwd"],
+                                  geo["cmin"], geo["ncol"], int(lmax), flags, out.ctypes.data_as(_i32p), top.ctypes.data_as(_i32p))
+    if rc:
+        raise ValueError("band_scores: bad lengths")
+    return (out, top) if with_top else out
 
 
 def set_simd(on: bool) -> bool:

@@ -179,6 +179,50 @@ def get_ref_repeat_count(start_count: int, tr_seq: str, flank_left_seq: str, fla
     return final, l_off, r_off, (n_scored, n_final), (fl, tr, fr)
 
 
+def _banded(rows: str, cols: str, d_lo: int, width: int, top_free: bool, left_free: bool) -> dict:
+    """{(r, j): H} of the cells with d_lo <= j - r < d_lo + width: linear gaps, boundary values where in the band and in the one
+    boundary cell on each side that borders the band's edge cell of row 1 / column 1 (strk_band.c)."""
+    g = indel_penalty
+    a, b = _enc(rows), _enc(cols)
+    H: dict = {}
+    for r in range(len(a) + 1):
+        beside = [0] if r > 0 and r + d_lo == 1 else ([d_lo + width] if r == 0 and 0 <= d_lo + width <= len(b) else [])
+        for j in beside + list(range(max(0, r + d_lo), min(len(b), r + d_lo + width - 1) + 1)):
+            if r == 0:
+                H[r, j] = 0 if top_free else -g * j
+            elif j == 0:
+                H[r, j] = 0 if left_free else -g * r
+            else:
+                cand = [H[r - 1, j - 1] + dna_matrix[b[j - 1]][a[r - 1]]] if (r - 1, j - 1) in H else []
+                cand += [H[r - 1, j] - g] if (r - 1, j) in H else []
+                cand += [H[r, j - 1] - g] if (r, j - 1) in H else []
+                if cand:
+                    H[r, j] = max(cand)
+    return H
+
+
+def band_scores(fl: str, tr: str, fr: str, motif: str, lo: int, n: int, geo: dict, lmax: bool, flags: int = 15):
+    """The banded first pass (strk_band.c states the definition), for small cases: S_band of the candidates lo .. lo + n - 1, None
+    where no cell of both bands exists.  flags: 1 db begin, 2 db end, 4 candidate begin, 8 candidate end free."""
+    g = indel_penalty
+    db = fl + tr + fr
+    ndb, nfl, nfr, m = len(db), len(fl), len(fr), len(motif)
+    F = _banded(fl + motif * (lo + n - 1), db, geo["dlo"], geo["wd"], bool(flags & 1), bool(flags & 4))
+    B = _banded(fr[::-1], db[::-1], geo["bdlo"], geo["bwd"], bool(flags & 2), bool(flags & 8))
+    out = []
+    for i in range(lo, lo + n):
+        R = nfl + i * m
+        cols = range(max(0, geo["cmin"]), min(ndb, geo["cmin"] + geo["ncol"] - 1) + 1)
+        in_f = lambda r, j: geo["dlo"] <= j - r < geo["dlo"] + geo["wd"] and (r, j) in F           # noqa: E731  (cells of the band only)
+        in_b = lambda k, j: geo["bdlo"] <= j - k < geo["bdlo"] + geo["bwd"] and (k, j) in B       # noqa: E731
+        vals = [F[R, j] + B[nfr, ndb - j] for j in cols if in_f(R, j) and in_b(nfr, ndb - j)]
+        if lmax and flags & 8:
+            last = [(r, min(ndb, r + geo["dlo"] + geo["wd"] - 1)) for r in range(1, R + 1)]
+            vals += [F[r, c] - g * (ndb - c) for r, c in last if in_f(r, c)]
+        out.append(max(vals) if vals else None)
+    return out
+
+
 def count_locus(reads, motif: str, est_cns, max_iters: int = 50, local_search_range: int = 3, step_size: int = 1,
                 feedback: bool = True, tie_last: bool = False):
     """Caller protocol call_locus.py:1125-1161.  reads: [(fl, tr, fr)].  -> [(cn, score, n_iters, start)]."""

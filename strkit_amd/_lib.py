@@ -94,7 +94,7 @@ EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk
            "strk_gff_overlaps", "strk_dbam_gff_overlaps", "strk_gff_constants",
            "strk_mi_trio", "strk_mi_trio_host", "strk_mi_constants",
            "strk_select_reads", "strk_dbam_select_reads", "strk_select_constants",
-           "strk_classify", "strk_score_constants", "strk_class_counts")
+           "strk_classify", "strk_score_constants", "strk_class_counts", "strk_band_tables")
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -145,6 +145,8 @@ def load(build: bool = True):
         L.strk_score_constants.argtypes = [_i32p, C.c_int32]
         L.strk_class_counts.restype = C.c_int
         L.strk_class_counts.argtypes = [C.c_void_p, _i32p, C.c_int32]
+        L.strk_band_tables.restype = C.c_int
+        L.strk_band_tables.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, _i32p, C.c_int32] + [C.c_void_p] * 3 + [C.c_int32] + [C.c_void_p] * 3
         L.strk_adaptive_reset.restype = None
         L.strk_adaptive_reset.argtypes = []
         L.strk_repeat_count.restype = C.c_int

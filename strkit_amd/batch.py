@@ -15,7 +15,7 @@ from .repeat_count_params import RepeatCountParams, default_read_rc_params
 from .synth import LocusBatch
 
 __all__ = ["count_loci", "score_table", "score_ref_table", "make_params", "batch_struct", "calc_adj_score", "filter_reads",
-           "score_constants", "classify", "class_counts"]
+           "score_constants", "classify", "class_counts", "band_tables"]
 
 
 def make_params(rc_params: RepeatCountParams | None = None, feedback: bool = True, window: int = 0,
@@ -140,6 +140,31 @@ def classify(nfl: int, ntr: int, nfr: int, m: int, lo: int, n: int, force_generi
     """The list the planning kernel gives such an item (strk_classify): 0 .. kNumClasses - 1 the fast classes, then the
     column-tiled kernel, then the generic kernel."""
     return int(_lib.load().strk_classify(nfl, ntr, nfr, m, lo, n, int(force_generic), int(ref_mode)))
+
+
+BAND_ROW_UNTOUCHED = np.int32(-(2 ** 31))
+
+
+def band_tables(b: LocusBatch, window: int, end_flags: int = _lib.STRK_SG_ALL, tune=(0, 0, 0), sort_wide: bool = False,
+                table_stride: int | None = None, ctx: _lib.Context | None = None, with_stats: bool = False):
+    """What the band kernels write (strk_band_tables): dict of lo, n, cls (0..7 the band class, -1 refused by the band geometry,
+    -2 handed on for a symbol outside the fixed classes) per read and scores, ub as [n_reads, table_stride] int32 arrays; rows
+    and entries the kernels did not write hold BAND_ROW_UNTOUCHED."""
+    ctx = ctx or _lib.default_context()
+    ts = int(table_stride or 2 * window + 1)
+    p = make_params(window=window, end_flags=end_flags, dedupe=False)
+    s, keep = batch_struct(b)
+    nr = max(b.n_reads, 1)
+    out = {k: np.zeros(nr, np.int32) for k in ("lo", "n", "cls")}
+    out["scores"] = np.full((nr, ts), BAND_ROW_UNTOUCHED, np.int32)
+    out["ub"] = np.full((nr, ts), BAND_ROW_UNTOUCHED, np.int32)
+    t = (C.c_int32 * 3)(*[int(x) for x in tune])
+    st = _lib.StrkStats()
+    _lib.check(_lib.load().strk_band_tables(ctx.handle, C.byref(s), C.byref(p), t, int(sort_wide), _ptr(out["lo"]), _ptr(out["n"]),
+                                            _ptr(out["cls"]), ts, _ptr(out["scores"]), _ptr(out["ub"]), C.byref(st)))
+    del keep
+    out = {k: v[:b.n_reads] for k, v in out.items()}
+    return (out, st.as_dict()) if with_stats else out
 
 
 def class_counts(ctx: _lib.Context | None = None) -> np.ndarray:

@@ -938,6 +938,92 @@ int strk_class_counts(strk_ctx* c, int32_t* out, int32_t cap) {
     return kNumClasses + 2;
 }
 
+// Test support for the band pass: k_plan in mode 0 with the band on for every read, then k_dp_band and k_dp_band_wide and
+// nothing behind them, so that KArgs::table and KArgs::ub come back as the band kernels left them (in a counting call pass 1 of
+// k_replay uses or replaces them on the device).  Launched here and not through enqueue_scoring, whose band pass needs the
+// replay pass behind it; the context's BandGate, GridHistory and the process's WindowPolicy are neither read nor written.
+int strk_band_tables(strk_ctx* ctx, const strk_batch* batch, const strk_params* params, const int32_t* tune, int32_t flags,
+                     int32_t* out_lo, int32_t* out_n, int32_t* out_class, int32_t table_stride, int32_t* out_scores,
+                     int32_t* out_ub, strk_stats* stats) {
+    if (!ctx) return fail(STRK_E_INVALID, "ctx is NULL");
+    if (ctx->pending) return fail(STRK_E_INVALID, "strk_band_tables: a submitted call is pending on this context");
+    if (stats) memset(stats, 0, sizeof *stats);
+    strk_params p;
+    int rc;
+    if ((rc = check_params(params, &p))) return rc;
+    if (params->window <= 0) return fail(STRK_E_INVALID, "strk_band_tables: params->window must be given (> 0)");
+    if (!tune || table_stride < 1 || table_stride > 2 * kTableMax + 1) return fail(STRK_E_INVALID, "strk_band_tables: tune is NULL or table_stride is not in [1, %d]", 2 * kTableMax + 1);
+    if (batch && batch->n_reads > 0 && batch->n_loci > 0 && (!out_lo || !out_n || !out_class || !out_scores || !out_ub))
+        return fail(STRK_E_INVALID, "strk_band_tables: output pointer is NULL");
+    strk_batch d;
+    hipStream_t st;
+    if ((rc = upload_batch(ctx, batch, &d, &st))) return rc;
+    if (batch->n_reads == 0 || batch->n_loci == 0) return 0;
+    const size_t nr = (size_t)batch->n_reads, tab = nr * (size_t)table_stride;
+    if ((rc = ensure_workspace(ctx, batch->n_reads, batch->n_loci, tab, nr, true))) return rc;
+    for (int k = 0; k < kWinBuckets; ++k) ctx->p_window_b[k] = 0;   // params->window for every motif length
+    KArgs a = make_args(ctx, &d, p.end_flags, params->window, table_stride, batch->n_reads, nullptr);
+    a.spec = static_cast<int4*>(ctx->spec.p);
+    a.rep = ctx->rep.as<int32_t>();
+    a.rhash = nullptr;   // no dedupe: every read owns its row
+    a.exact = ctx->exact.as<uint8_t>();
+    a.band_mode = 1;
+    a.band_limit = INT32_MAX;
+    if (tune[0] || tune[1] || tune[2]) a.band_tune = {tune[0], tune[1], tune[2]};
+    const int plan_scope = plan_scope_of(batch->n_reads);
+    const int blocks = std::max(1, std::min(256 * kBandBlocksPerCU, (a.list_stride + 3) / 4));
+    const size_t recs = (size_t)kNumBandClasses * nr * 2;
+    std::vector<int32_t> h_cnt(kCntTotal), h_list(recs), h_tab(tab), h_ub(tab);
+    std::vector<uint8_t> h_exact(nr);
+    rc = timed_launch(ctx, st, stats, "strk_band_tables", "the band pass", (flags & 1) ? 5 : 3, [&] {
+        (void)hipMemsetAsync(ctx->counters.p, 0, kCountersAllBytes, st);
+        hipLaunchKernelGGL(k_plan, dim3((batch->n_reads + plan_scope - 1) / plan_scope), dim3(kPlanThreads), 0, st, a, 0, (const int32_t*)nullptr,
+                           batch->n_reads, 0, plan_reads_per_thread(batch->n_reads));
+        hipLaunchKernelGGL(k_dp_band, dim3(blocks), dim3(256), 0, st, a);
+        KArgs aw = a;
+        if (flags & 1) {   // longest first, as enqueue_scoring orders the wide classes of a call with few wide chunks
+            hipLaunchKernelGGL(k_sort_wide_hist, dim3(kSortWideBlocks, kNumWideLists), dim3(256), 0, st, a);
+            hipLaunchKernelGGL(k_sort_wide, dim3(kSortWideBlocks, kNumWideLists), dim3(256), 0, st, a, ctx->band_recs_w.as<int4>());
+            aw.band_recs_w = ctx->band_recs_w.as<int4>();
+        }
+        hipLaunchKernelGGL(k_dp_band_wide, dim3(blocks), dim3(256), 0, st, aw);
+    }, [&] {
+        HIP_TRY(hipMemcpyAsync(h_cnt.data(), ctx->counters.p, h_cnt.size() * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_list.data(), ctx->cls_list.as<int32_t>() + (size_t)kBandClass0 * nr * 2, recs * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_exact.data(), ctx->exact.p, nr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_tab.data(), ctx->table.p, tab * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h_ub.data(), ctx->ub.p, tab * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out_lo, a.win_lo, nr * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(out_n, a.win_n, nr * 4, hipMemcpyDeviceToHost, st));
+        return 0;
+    });
+    if (rc) return rc;
+    if ((rc = check_error_bits(h_cnt[kCntError] & ~kErrEmpty))) return rc;
+    for (size_t r = 0; r < nr; ++r) out_class[r] = -1;
+    int n_band = 0;
+    for (int c = 0; c < kNumBandClasses; ++c) {
+        const int cnt = std::min(h_cnt[kCntClass0 + kBandClass0 + c], batch->n_reads);
+        n_band += cnt;
+        for (int k = 0; k < cnt; ++k) {
+            const int32_t r = h_list[((size_t)c * nr + k) * 2];
+            if (r < 0 || (size_t)r >= nr) return fail(STRK_E_DEVICE, "strk_band_tables: band list %d holds read %d", c, r);
+            out_class[r] = h_exact[r] ? -2 : c;
+        }
+    }
+    for (size_t r = 0; r < nr; ++r) {   // rows of the reads a band class scored; every other row stays as the caller left it
+        if (out_class[r] < 0) continue;
+        const size_t n = (size_t)std::max(0, std::min(out_n[r], table_stride));
+        memcpy(out_scores + r * table_stride, h_tab.data() + r * table_stride, n * 4);
+        memcpy(out_ub + r * table_stride, h_ub.data() + r * table_stride, n * 4);
+    }
+    if (stats) {
+        stats->n_band_reads = n_band;
+        stats->n_band_fallback = h_cnt[kCntBandFallback];
+        stats->window_used = params->window;
+    }
+    return 0;
+}
+
 void strk_adaptive_reset(void) { g_window.reset(); }
 
 int strk_host_register(void* ptr, int64_t bytes) {
