@@ -3,6 +3,7 @@
 //   strk_host.h     the calling thread's error message (fail, HIP_TRY) and the owning types: DevBuf, PinnedBuf, Stream, Event
 //   strk_policy.h   the adaptive policies as plain state machines: default window, band gate, grid history (no HIP in it)
 //   strk_groups.h   groups of byte strings as three calls take them: the view, its one check, the piece cutter (no HIP in it)
+//   strk_threads.h  the CPUs of the process, the two thread fans, the first malformed item, the piece loop (no HIP in it)
 //   strk_alleles_check.h, strk_phase_check.h   the input of the three allele calls and its checks (no HIP in them)
 //   strk_realign_plan.h   strk_realign's input check, chunks and workspace layout (no HIP in it)
 // and the other parts live in include fragments spliced into this file:
@@ -23,6 +24,7 @@
 #include "strk_host.h"
 #include "strk_policy.h"
 #include "strk_groups.h"
+#include "strk_threads.h"
 #include "strk_phase_check.h"
 #include "strk_phase_inputs.h"
 #include "strk_methyl.h"
@@ -46,7 +48,6 @@
 #include <thread>
 #include <vector>
 #include <fcntl.h>
-#include <sched.h>
 #include <sys/stat.h>
 #include <unistd.h>
 
@@ -80,13 +81,7 @@ std::mutex g_band_chain_mu;
 hipEvent_t g_band_chain_ev = nullptr;
 int g_band_chain_dev = -1;
 
-// CPUs this process may run on (a container's share, not the machine's core count)
-int host_cpus() {
-    cpu_set_t set;
-    CPU_ZERO(&set);
-    if (sched_getaffinity(0, sizeof set, &set) == 0 && CPU_COUNT(&set) > 0) return CPU_COUNT(&set);
-    return std::max(1u, std::thread::hardware_concurrency());
-}
+using strk_threads::host_cpus;
 
 // device layout of the `counters` buffer: int32[kCntTotal] | pad | u64 cells | u64 scratch_used
 constexpr size_t kCellsOff = 64 * sizeof(int32_t);

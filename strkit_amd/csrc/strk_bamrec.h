@@ -7,6 +7,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "strk_groups.h"
+
 #if defined(__HIPCC__)
 #define STRK_FE_HD __host__ __device__ inline
 #else
@@ -87,6 +89,39 @@ STRK_FE_HD bool parse_rec(const uint8_t* buf, int64_t n_bytes, int64_t off, Rec*
         }
     }
     return true;
+}
+
+// Substitute alignments of a call's items (realigned reads): item i walks ops[off[i] .. off[i + 1]) from reference position
+// start[i] in place of its record's CIGAR when that range is not empty.  ops == off == NULL: no item has one; start == NULL:
+// every start is 0.  The one statement of the triple that strk_extract_reads, strk_phase_cells, strk_methyl and their device
+// twins take as alt_cigar, alt_cigar_off, alt_start.
+struct AltCigars {
+    const uint32_t* ops;
+    const int64_t* off;
+    const int64_t* start;
+};
+
+// The triple of a call of n_items > 0 items, checked before any thread or launch reads it.  Returns 0, or
+// strk_groups::kInvalid and in `msg` what is wrong.
+inline int check_alt(int32_t n_items, const AltCigars& alt, strk_groups::Message* msg) {
+    if ((alt.ops == nullptr) != (alt.off == nullptr)) return msg->invalid("alt_cigar and alt_cigar_off must both be given or both be NULL");
+    if (!alt.off) return 0;
+    if (alt.off[0] != 0) return msg->invalid("alt_cigar_off[0] must be 0");
+    for (int32_t i = 0; i < n_items; ++i) {
+        const int64_t n = alt.off[i + 1] - alt.off[i];
+        if (n < 0 || n > INT32_MAX) return msg->invalid("item %d: alt_cigar_off is decreasing (or a CIGAR too long)", i);
+    }
+    return 0;
+}
+
+// the alignment item `it` of a checked call is walked along
+STRK_FE_HD void item_alignment(const Rec& r, int32_t it, const AltCigars& alt, const uint8_t** cig, int32_t* n_cig, int64_t* start) {
+    *cig = r.cigar; *n_cig = r.n_cigar; *start = r.pos;
+    if (alt.off && alt.off[it + 1] > alt.off[it]) {   // a realigned read: its new alignment
+        *cig = reinterpret_cast<const uint8_t*>(alt.ops + alt.off[it]);
+        *n_cig = (int32_t)(alt.off[it + 1] - alt.off[it]);
+        *start = alt.start ? alt.start[it] : 0;
+    }
 }
 
 // Reference span and the two soft clips of an alignment (what the record scan keeps per record).

@@ -111,26 +111,21 @@ __global__ void __launch_bounds__(256) k_dbam_scan(const uint8_t* data, int64_t 
 // length of its name.  Pass 2 (after the host has summed the lengths): bases (4 bit -> ASCII, low-quality bases -> 'X').
 // alt_*: optional substitute CIGARs (realigned reads), as in strk_extract_reads.
 __global__ void __launch_bounds__(256) k_dbam_extract1(const uint8_t* data, int64_t n_data, int n_items, const int64_t* rec_off,
-                                                       const int64_t* coords, const uint32_t* alt_cigar, const int64_t* alt_off,
-                                                       const int64_t* alt_start, int flank_size, int min_avg_phred, int32_t* status,
-                                                       int32_t* nfl, int32_t* ntr, int32_t* nfr, int64_t* cut_a, int32_t* name_len,
-                                                       int32_t* bad) {
+                                                       const int64_t* coords, strk_fe::AltCigars alt, int flank_size, int min_avg_phred,
+                                                       int32_t* status, int32_t* nfl, int32_t* ntr, int32_t* nfr, int64_t* cut_a,
+                                                       int32_t* name_len, int32_t* bad) {
     const int it = blockIdx.x * blockDim.x + threadIdx.x;
     if (it >= n_items) return;
     status[it] = 1; nfl[it] = 0; ntr[it] = 0; nfr[it] = 0; cut_a[it] = 0; name_len[it] = 0;
     strk_fe::Rec r;
     int64_t next = 0;
-    if (!strk_fe::parse_rec(data, n_data, rec_off[it], &r, &next)) { atomicMax(bad, it + 1); return; }
+    if (!strk_fe::parse_rec(data, n_data, rec_off[it], &r, &next)) { atomicMax(bad, INT32_MAX - it); return; }
     name_len[it] = r.l_name > 0 ? r.l_name - 1 : 0;
     int64_t q[4];
-    const uint8_t* cig = r.cigar;
-    int32_t n_cig = r.n_cigar;
-    int64_t start = r.pos;
-    if (alt_off && alt_off[it + 1] > alt_off[it]) {   // a realigned read: its new alignment
-        cig = reinterpret_cast<const uint8_t*>(alt_cigar + alt_off[it]);
-        n_cig = (int32_t)(alt_off[it + 1] - alt_off[it]);
-        start = alt_start ? alt_start[it] : 0;
-    }
+    const uint8_t* cig;
+    int32_t n_cig;
+    int64_t start;
+    strk_fe::item_alignment(r, it, alt, &cig, &n_cig, &start);
     if (!strk_fe::read_coords_linear(cig, n_cig, start, coords[4 * (size_t)it], coords[4 * (size_t)it + 1],
                                      coords[4 * (size_t)it + 2], coords[4 * (size_t)it + 3], q))
         return;
@@ -229,14 +224,17 @@ int dbam_big_ensure(int device, DevBuf& b, size_t bytes) {
 struct strk_dbam {
     int device = 0;
     DevBuf comp, blocks, data, lens, status;
-    DevBuf w_a, w_b, w_c, w_d, w_e, w_f, seqs;   // scan / extraction work buffers, the extracted bases
-    // strk_dbam_phase_cells (strk_phase_inputs.inc): the cells of its last call (base | quality), their offsets per item and the
-    // candidate offsets on the device, and what strk_dbam_useful_snvs checks its input against
-    DevBuf pc_cells, pc_cell_off, pc_cand_off, pc_in, pc_work;
+    // w_a: the staging (strk_host.h) of a call on items: extraction, names, useful SNVs, methylation, selection; the scan's starts
+    DevBuf w_a, w_b, w_c, w_d, w_e, w_f, seqs;   // scan / selection work buffers, the extracted bases (until the next extraction)
+    // strk_dbam_phase_cells (strk_phase_inputs.inc): the cells of its last call (base | quality) and its staging, of which the
+    // cells' offsets per item (at pc_cell_off) and the candidate offsets (at pc_cand_off) serve strk_dbam_useful_snvs: no other
+    // entry stages into these two.  And what strk_dbam_useful_snvs checks its input against.
+    DevBuf pc_cells, pc_in;
+    PinnedBuf stage;   // the host image of the call in progress (Staging)
+    size_t pc_cell_off = 0, pc_cand_off = 0;
     std::vector<int32_t> pc_item_locus, pc_cand_off_h;
     std::vector<int64_t> pc_cell_off_h;
     bool pc_valid = false;
-    DevBuf me_in;   // strk_dbam_methyl (strk_methyl.inc): its inputs and outputs
     DevBuf ln_tiles, ln_starts, ln_query;   // the lines of a text (strk_lines.inc): per tile, the line starts; a reader's status words and contig name
     DevBuf vc_lines, vc_out;   // strk_dbam_vcf_snvs (strk_vcf.inc): per line, per kept line
     DevBuf gf_lines, gf_feat, gf_join, gf_pairs, gf_out, gf_text;   // strk_dbam_gff_overlaps (strk_gff.inc): per line, feature, locus, pair; what is downloaded
@@ -677,49 +675,32 @@ int strk_dbam_extract(strk_dbam* d, int32_t n_items, const int64_t* rec_off, con
     for (int32_t it = 0; it < n_items; ++it)
         if (rec_off[it] < 0 || rec_off[it] > d->n_data - 36)
             return fail(STRK_E_INVALID, "item %d: record offset %lld outside the stream", it, (long long)rec_off[it]);
+    const strk_fe::AltCigars alt{alt_cigar, alt_cigar_off, alt_start};
+    strk_groups::Message msg;
+    if (strk_fe::check_alt(n_items, alt, &msg)) return fail(STRK_E_INVALID, "%s", msg.text);
     HIP_TRY(hipSetDevice(d->device));
     const size_t n = (size_t)n_items;
     int rc;
-    // w_a: rec_off | coords;  w_b: status nfl ntr nfr name_len;  w_c: cut_a;  w_d: seq_off;  w_e: bad
-    if ((rc = d->w_a.ensure(n * 8 * 5)) || (rc = d->w_b.ensure(n * 4 * 5)) || (rc = d->w_c.ensure(n * 8)) || (rc = d->w_d.ensure((n + 1) * 8)) ||
-        (rc = d->w_e.ensure(16)))
-        return rc;
-    int64_t* d_rec = d->w_a.as<int64_t>();
-    int64_t* d_coords = d_rec + n;
-    int32_t* d_status = d->w_b.as<int32_t>();
-    int32_t *d_nfl = d_status + n, *d_ntr = d_nfl + n, *d_nfr = d_ntr + n, *d_nl = d_nfr + n;
-    HIP_TRY(hipMemcpy(d_rec, rec_off, n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_coords, coords, n * 32, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d->w_e.p, 0, 16));
-    const uint32_t* d_acig = nullptr;
-    const int64_t *d_aoff = nullptr, *d_astart = nullptr;
-    if (alt_cigar && alt_cigar_off && alt_cigar_off[n] > 0) {   // substitute CIGARs: ops | offsets | starts in one buffer
-        const size_t n_ops = (size_t)alt_cigar_off[n];
-        const size_t o_off = (n_ops * 4 + 7) & ~(size_t)7, o_start = o_off + (n + 1) * 8;
-        if ((rc = d->w_f.ensure(o_start + n * 8))) return rc;
-        uint8_t* base = d->w_f.as<uint8_t>();
-        HIP_TRY(hipMemcpy(base, alt_cigar, n_ops * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(base + o_off, alt_cigar_off, (n + 1) * 8, hipMemcpyHostToDevice));
-        if (alt_start) HIP_TRY(hipMemcpy(base + o_start, alt_start, n * 8, hipMemcpyHostToDevice));
-        else HIP_TRY(hipMemset(base + o_start, 0, n * 8));
-        d_acig = reinterpret_cast<const uint32_t*>(base);
-        d_aoff = reinterpret_cast<const int64_t*>(base + o_off);
-        d_astart = reinterpret_cast<const int64_t*>(base + o_start);
-    }
+    // w_a: rec_off | coords | alt | bad || status nfl ntr nfr name_len || cut_a | seq_off
+    Staging st(d->stage);
+    const size_t o_rec = st.put(rec_off, n * 8), o_coords = st.put(coords, n * 32);
+    const StagedAlt s_alt = stage_alt(st, n, alt);
+    const size_t o_bad = st.zero(4), o_out = st.room(n * 4 * 5), o_cut = st.room(n * 8), o_soff = st.room((n + 1) * 8);
+    if ((rc = st.upload(d->w_a))) return rc;
+    int64_t* const d_rec = d->w_a.at<int64_t>(o_rec);
+    int32_t* const d_status = d->w_a.at<int32_t>(o_out);
+    int32_t *const d_nfl = d_status + n, *const d_ntr = d_nfl + n, *const d_nfr = d_ntr + n, *const d_nl = d_nfr + n;
     d->tic();
     hipLaunchKernelGGL(k_dbam_extract1, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d->data.as<uint8_t>(), d->n_data, n_items,
-                       d_rec, d_coords, d_acig, d_aoff, d_astart, flank_size, min_avg_phred, d_status, d_nfl, d_ntr, d_nfr,
-                       d->w_c.as<int64_t>(), d_nl, d->w_e.as<int32_t>());
+                       d_rec, d->w_a.at<int64_t>(o_coords), s_alt.on(d->w_a), flank_size, min_avg_phred, d_status, d_nfl, d_ntr, d_nfr,
+                       d->w_a.at<int64_t>(o_cut), d_nl, d->w_a.at<int32_t>(o_bad));
     HIP_TRY(hipGetLastError());
     d->toc();
-    int32_t bad = 0;
-    HIP_TRY(hipMemcpy(&bad, d->w_e.p, 4, hipMemcpyDeviceToHost));
-    if (bad) return fail(STRK_E_INVALID, "item %d: malformed BAM record", bad - 1);
-    HIP_TRY(hipMemcpy(status, d_status, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(nfl, d_nfl, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ntr, d_ntr, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(nfr, d_nfr, n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(name_len, d_nl, n * 4, hipMemcpyDeviceToHost));
+    if ((rc = st.download(d->w_a, o_bad, o_cut))) return rc;
+    const int64_t bad = strk_threads::first_bad_of_word(*st.at<int32_t>(o_bad), INT32_MAX);
+    if (bad >= 0) return fail(STRK_E_INVALID, "item %d: malformed BAM record", (int)bad);
+    int32_t* const outs[5] = {status, nfl, ntr, nfr, name_len};
+    for (int j = 0; j < 5; ++j) memcpy(outs[j], st.at<int32_t>(o_out) + (size_t)j * n, n * 4);
     int64_t w = 0;
     seq_off[0] = 0;
     for (size_t it = 0; it < n; ++it) {
@@ -727,10 +708,10 @@ int strk_dbam_extract(strk_dbam* d, int32_t n_items, const int64_t* rec_off, con
         seq_off[it + 1] = w;
     }
     if ((rc = d->seqs.ensure((size_t)w + 16))) return rc;
-    HIP_TRY(hipMemcpy(d->w_d.p, seq_off, (n + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d->w_a.at<char>(o_soff), seq_off, (n + 1) * 8, hipMemcpyHostToDevice));
     d->tic();
     hipLaunchKernelGGL(k_dbam_extract2, dim3((unsigned)((n * 8 + 255) / 256)), dim3(256), 0, 0, d->data.as<uint8_t>(), d->n_data, n_items,
-                       d_rec, d_status, d_nfl, d_ntr, d_nfr, d->w_c.as<int64_t>(), d->w_d.as<int64_t>(), wildcard_threshold,
+                       d_rec, d_status, d_nfl, d_ntr, d_nfr, d->w_a.at<int64_t>(o_cut), d->w_a.at<int64_t>(o_soff), wildcard_threshold,
                        d->seqs.as<uint8_t>());
     HIP_TRY(hipGetLastError());
     d->toc();
@@ -755,14 +736,15 @@ int strk_dbam_names(strk_dbam* d, int64_t n, const int64_t* rec_off, const int64
     }
     if (out_off[n] == 0) return 0;
     HIP_TRY(hipSetDevice(d->device));
+    // w_a: rec_off | out_off || the names
+    Staging st(d->stage);
+    const size_t o_rec = st.put(rec_off, (size_t)n * 8), o_off = st.put(out_off, (size_t)(n + 1) * 8), o_out = st.room((size_t)out_off[n] + 16);
     int rc;
-    if ((rc = d->w_a.ensure((size_t)n * 8)) || (rc = d->w_d.ensure((size_t)(n + 1) * 8)) || (rc = d->w_c.ensure((size_t)out_off[n] + 16))) return rc;
-    HIP_TRY(hipMemcpy(d->w_a.p, rec_off, (size_t)n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d->w_d.p, out_off, (size_t)(n + 1) * 8, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_dbam_names, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d->data.as<uint8_t>(), (int)n, d->w_a.as<int64_t>(),
-                       d->w_d.as<int64_t>(), d->w_c.as<uint8_t>());
+    if ((rc = st.upload(d->w_a))) return rc;
+    hipLaunchKernelGGL(k_dbam_names, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d->data.as<uint8_t>(), (int)n, d->w_a.at<int64_t>(o_rec),
+                       d->w_a.at<int64_t>(o_off), d->w_a.at<uint8_t>(o_out));
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpy(out, d->w_c.p, (size_t)out_off[n], hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d->w_a.at<char>(o_out), (size_t)out_off[n], hipMemcpyDeviceToHost));   // (straight into the caller's bytes)
     return 0;
 }
 

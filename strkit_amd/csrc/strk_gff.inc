@@ -38,7 +38,7 @@ int64_t strk_gff_overlaps(const uint8_t* buf, int64_t n_bytes, int64_t start, co
     strk_gff::Result r;
     strk_gff::Message msg;
     if (strk_gff::overlaps_host(buf, n_bytes, start, contig, gtf, final, prev_beg, n_loci, l_start, l_end, &r, &msg,
-                                [](int32_t n, auto&& body) { pi_parallel(n, body); }))
+                                [](int32_t n, auto&& body) { strk_threads::parallel_slices(n, 1024, 32, body); }))
         return fail(STRK_E_INVALID, "%s: %s", who, msg.text);
     *end_off = r.end_off; *past = r.past;
     return strk_gff::emit(r, n_loci, pair_cap, pair_locus, pair_feat, feat_cap, f_beg, f_end, f_kind, f_text_off, text_cap, text, sizes);

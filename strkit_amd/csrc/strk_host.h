@@ -7,9 +7,12 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/strkit_amd.h"
+#include "strk_bamrec.h"
 
 namespace {
 
@@ -111,6 +114,77 @@ struct PinnedBuf : OwnedMem<hipHostFree> {
         return 0;
     }
 };
+
+// What one call sends to a device buffer and takes back from it, as one image in page-locked memory of its owner: every part
+// has its 256-aligned offset in the image and in the buffer alike.  put() and zero() name what goes up (the bytes are read by
+// upload(): they must still be there), room() reserves what only the kernels write.  upload() gathers the parts into the image
+// and sends every stretch of neighbouring parts with one hipMemcpy; a part of kDirectBytes or more goes up from where it lies
+// instead (the runtime locks its pages and copies at the same rate; gathering 12 MB first cost a call of 300 000 items more
+// than half a millisecond, profiles/r30_item_stages.txt).  download() brings one range of the buffer back into the image in
+// one copy, and at() reads a part of it there.
+struct Staging {
+    static constexpr size_t kDirectBytes = (size_t)256 << 10;
+    explicit Staging(PinnedBuf& image) : image_(image) {}
+    Carve cv;
+    size_t room(size_t bytes) { return cv.take(bytes); }
+    size_t zero(size_t bytes) { return put(nullptr, bytes); }
+    size_t put(const void* src, size_t bytes) {
+        const size_t at = cv.take(bytes);
+        parts_.push_back(Part{at, src, bytes});
+        return at;
+    }
+    int upload(DevBuf& b) {
+        int rc;
+        if ((rc = b.ensure(cv.bytes)) || (rc = image_.ensure(cv.bytes))) return rc;
+        size_t from = 0, to = 0;   // the stretch of the image that has been gathered and not sent
+        for (const Part& p : parts_) {
+            const bool direct = p.src && p.bytes >= kDirectBytes;
+            if (direct || to == from) {
+                if (to > from) HIP_TRY(hipMemcpy(b.at<char>(from), image_.at<char>(from), to - from, hipMemcpyHostToDevice));
+                from = to = p.at;
+            }
+            if (direct) {
+                HIP_TRY(hipMemcpy(b.at<char>(p.at), p.src, p.bytes, hipMemcpyHostToDevice));
+                continue;
+            }
+            if (p.src) memcpy(image_.at<char>(p.at), p.src, p.bytes);
+            else memset(image_.at<char>(p.at), 0, p.bytes);
+            to = p.at + p.bytes;
+        }
+        if (to > from) HIP_TRY(hipMemcpy(b.at<char>(from), image_.at<char>(from), to - from, hipMemcpyHostToDevice));
+        return 0;
+    }
+    int download(const DevBuf& b, size_t from, size_t to) {   // (after upload(): the image has room for every part)
+        if (to > from) HIP_TRY(hipMemcpy(image_.at<char>(from), b.at<char>(from), to - from, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    template <class T> const T* at(size_t byte_off) const { return image_.at<T>(byte_off); }
+
+  private:
+    struct Part { size_t at; const void* src; size_t bytes; };
+    PinnedBuf& image_;
+    std::vector<Part> parts_;
+};
+
+// The substitute alignments of a call of n items (strk_bamrec.h, checked by check_alt) into its staging: ops | offsets | starts
+// (zeros for start == NULL).  A triple that holds no operation at all is absent: on() then gives three NULLs.
+struct StagedAlt {
+    bool present = false;
+    size_t ops = 0, off = 0, start = 0;
+    strk_fe::AltCigars on(const DevBuf& b) const {
+        if (!present) return strk_fe::AltCigars{nullptr, nullptr, nullptr};
+        return strk_fe::AltCigars{b.at<uint32_t>(ops), b.at<int64_t>(off), b.at<int64_t>(start)};
+    }
+};
+inline StagedAlt stage_alt(Staging& st, size_t n, const strk_fe::AltCigars& alt) {
+    StagedAlt s;
+    if (!alt.off || alt.off[n] <= 0) return s;
+    s.present = true;
+    s.ops = st.put(alt.ops, (size_t)alt.off[n] * 4);
+    s.off = st.put(alt.off, (n + 1) * 8);
+    s.start = alt.start ? st.put(alt.start, n * 8) : st.zero(n * 8);
+    return s;
+}
 
 // A stream or an event, destroyed with its owner.  Empty until the owner creates it (hipStreamCreate...(&s.h)); converts to the
 // plain handle wherever the runtime wants one.

@@ -1,6 +1,6 @@
 // strk_host_files.inc — the file front end on the CPU: record scan, read names, read extraction and BGZF inflation over host
 // buffers (strk_bam_scan*, strk_bam_names, strk_extract_reads, strk_bgzf_inflate*).  No device work, no context.
-// Part of strk_api.hip: included inside its extern "C" block (uses fail() and host_cpus() defined there, the record parser
+// Part of strk_api.hip: included inside its extern "C" block (uses fail() defined there, the threads of strk_threads.h, the record parser
 // of strk_frontend.h); not a stand-alone header.
 static int64_t bam_scan_impl(const uint8_t* buf, int64_t n_bytes, int64_t first_rec, int64_t cap, int64_t* rec_off, int32_t* tid,
                              int32_t* pos, int32_t* end, int32_t* flag, int32_t* l_seq, int32_t* clip_l, int32_t* clip_r, int64_t* end_off) {
@@ -73,31 +73,27 @@ int strk_extract_reads(const uint8_t* buf, int64_t n_bytes, int32_t n_items, con
     if (n_items < 0 || flank_size < 0) return fail(STRK_E_INVALID, "bad argument");
     if (n_items == 0) { if (seq_off) seq_off[0] = 0; return 0; }
     if (!buf || !rec_off || !coords || !status || !nfl || !ntr || !nfr || !seq_off) return fail(STRK_E_INVALID, "NULL argument");
+    const strk_fe::AltCigars alt{alt_cigar, alt_cigar_off, alt_start};
+    strk_groups::Message msg;
+    if (strk_fe::check_alt(n_items, alt, &msg)) return fail(STRK_E_INVALID, "%s", msg.text);
     static const char kBases[] = "=ACMGRSVTWYHKDBN";
-    // one thread per thousand items: starting threads costs more than a few hundred items do, and a caller that loads the next
-    // block's records meanwhile (IndexedBam) needs the other cores
-    const int nt = std::max(1, std::min<int>({host_cpus(), 32, n_items / 1024}));
-    auto parallel = [&](auto&& body) {   // body(first item, last item): contiguous slices, one per thread
-        std::vector<std::thread> th;
-        const int32_t per = (n_items + nt - 1) / nt;
-        for (int t = 1; t < nt; ++t)
-            if (t * per < n_items) th.emplace_back(body, t * per, std::min(n_items, (t + 1) * per));
-        body(0, std::min(n_items, per));
-        for (auto& x : th) x.join();
-    };
+    // contiguous slices, one thread per thousand items (strk_threads.h)
+    auto parallel = [&](auto&& body) { strk_threads::parallel_slices(n_items, 1024, 32, body); };
     // pass 1: where each read's flank | tract | flank lies (read positions a <= b <= c <= d), status, lengths
     std::vector<int64_t> cut((size_t)n_items * 2);   // a and b; c = b + ntr, d = c + nfr
-    std::atomic<int> bad{-1};
+    strk_threads::FirstBad bad;
     parallel([&](int32_t i0, int32_t i1) {
         strk_fe::Runs runs;
         for (int32_t it = i0; it < i1; ++it) {
             status[it] = 1; nfl[it] = ntr[it] = nfr[it] = 0;
             strk_fe::Rec r;
             int64_t next = 0;
-            if (!strk_fe::parse_rec(buf, n_bytes, rec_off[it], &r, &next)) { bad.store(it); return; }
-            const bool alt = alt_cigar && alt_cigar_off && alt_cigar_off[it + 1] > alt_cigar_off[it];
-            if (alt) runs.build(reinterpret_cast<const uint8_t*>(alt_cigar + alt_cigar_off[it]), (int32_t)(alt_cigar_off[it + 1] - alt_cigar_off[it]), alt_start ? alt_start[it] : 0);
-            else runs.build(r.cigar, r.n_cigar, r.pos);
+            if (!strk_fe::parse_rec(buf, n_bytes, rec_off[it], &r, &next)) { bad.report(it); return; }
+            const uint8_t* cig;
+            int32_t n_cig;
+            int64_t start;
+            strk_fe::item_alignment(r, it, alt, &cig, &n_cig, &start);
+            runs.build(cig, n_cig, start);
             int64_t q[4];
             if (!strk_fe::read_coords(runs, coords[4 * (size_t)it], coords[4 * (size_t)it + 1], coords[4 * (size_t)it + 2], coords[4 * (size_t)it + 3], q)) continue;
             const int64_t b = q[1], c = q[2];
@@ -114,7 +110,7 @@ int strk_extract_reads(const uint8_t* buf, int64_t n_bytes, int32_t n_items, con
             cut[2 * (size_t)it] = a;
         }
     });
-    if (bad.load() >= 0) return fail(STRK_E_INVALID, "item %d: malformed BAM record", bad.load());
+    if (bad.get() >= 0) return fail(STRK_E_INVALID, "item %d: malformed BAM record", (int)bad.get());
     int64_t w = 0;
     seq_off[0] = 0;
     for (int32_t it = 0; it < n_items; ++it) {
@@ -154,32 +150,15 @@ int strk_select_reads(const uint8_t* buf, int64_t n_bytes, int32_t n_loci, const
     if (n_loci == 0) return 0;
     const int64_t n_items = item_off[n_loci];
     if (!out_n_kept || (n_items > 0 && (!buf || !out_reason || !out_status))) return fail(STRK_E_INVALID, "strk_select_reads: NULL argument");
-    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)host_cpus(), 32, n_items / 4096}));
-    auto run = [&](auto&& body) {
-        std::vector<std::thread> th;
-        for (int t = 1; t < nt; ++t) th.emplace_back(body);
-        body();
-        for (auto& x : th) x.join();
-    };
-    std::atomic<int64_t> bad{INT64_MAX}, next_item{0};
-    run([&]() {
-        for (;;) {
-            const int64_t i0 = next_item.fetch_add(4096);
-            if (i0 >= n_items) return;
-            const int64_t b = strk_sel::host_first_bad(buf, in, i0, std::min(n_items, i0 + 4096));
-            int64_t cur = bad.load();
-            while (b >= 0 && b < cur && !bad.compare_exchange_weak(cur, b)) {}
-        }
+    const int nt = (int)std::min<int64_t>({(int64_t)host_cpus(), 32, n_items / 4096});
+    strk_threads::FirstBad bad;
+    strk_threads::parallel_chunks(n_items, 4096, nt, [&](int64_t i0, int64_t i1) {
+        const int64_t b = strk_sel::host_first_bad(buf, in, i0, i1);
+        if (b >= 0) bad.report(b);
     });
-    if (bad.load() != INT64_MAX) return fail(STRK_E_INVALID, "strk_select_reads: item %lld: malformed BAM record", (long long)bad.load());
-    std::atomic<int64_t> next_locus{0};
-    run([&]() {
-        strk_sel::HostTable table;
-        for (;;) {
-            const int64_t l0 = next_locus.fetch_add(16);
-            if (l0 >= n_loci) return;
-            for (int32_t l = (int32_t)l0; l < std::min<int64_t>(n_loci, l0 + 16); ++l) strk_sel::host_locus(buf, in, l, table, out_reason, out_status, out_n_kept);
-        }
+    if (bad.get() >= 0) return fail(STRK_E_INVALID, "strk_select_reads: item %lld: malformed BAM record", (long long)bad.get());
+    strk_threads::parallel_chunks<strk_sel::HostTable>(n_loci, 16, nt, [&](int64_t l0, int64_t l1, strk_sel::HostTable& table) {
+        for (int32_t l = (int32_t)l0; l < l1; ++l) strk_sel::host_locus(buf, in, l, table, out_reason, out_status, out_n_kept);
     });
     return 0;
 }
@@ -189,21 +168,13 @@ int strk_select_reads(const uint8_t* buf, int64_t n_bytes, int32_t n_loci, const
 // few blocks is not worth starting threads for).
 static bool bgzf_inflate_blocks(const uint8_t* comp, const std::vector<strk_fe::BgzfBlock>& blocks, uint8_t* out, int32_t n_threads,
                                 bool thread_per_16) {
-    const int nt = std::max(1, std::min<int>(n_threads > 0 ? n_threads : host_cpus(), 32));
-    std::atomic<size_t> next{0};
+    int nt = std::max(1, std::min<int>(n_threads > 0 ? n_threads : host_cpus(), 32));
+    if (thread_per_16) nt = (int)std::min<size_t>((size_t)nt, 1 + (blocks.size() + 15) / 16);
     std::atomic<int> bad{0};
-    auto work = [&]() {
-        for (;;) {
-            const size_t i = next.fetch_add(16);
-            if (i >= blocks.size()) return;
-            for (size_t k = i; k < std::min(blocks.size(), i + 16); ++k)
-                if (!strk_fe::bgzf_inflate_block(comp, blocks[k], out)) bad.store(1);
-        }
-    };
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt && (!thread_per_16 || (size_t)t * 16 < blocks.size() + 16); ++t) th.emplace_back(work);
-    work();
-    for (auto& t : th) t.join();
+    strk_threads::parallel_chunks((int64_t)blocks.size(), 16, nt, [&](int64_t k0, int64_t k1) {
+        for (int64_t k = k0; k < k1; ++k)
+            if (!strk_fe::bgzf_inflate_block(comp, blocks[(size_t)k], out)) bad.store(1);
+    });
     return bad.load() == 0;
 }
 

@@ -54,16 +54,6 @@ int strk_mi_trio_host(int32_t n_loci, const int64_t* grp_off, const int32_t* cn,
     // threads take pieces of consecutive loci from a counter; every locus has its own outputs, so the cut changes nothing
     const int32_t piece = params->piece_loci > 0 ? params->piece_loci : kMiHostPieceLoci;
     const int64_t n_pieces = ((int64_t)n_loci + piece - 1) / piece;
-    std::atomic<int64_t> next{0};
-    const auto body = [&] {
-        std::vector<uint64_t> keys;
-        std::vector<int32_t> tval, tcnt;
-        std::vector<strk_mi::U128> ws;
-        for (int64_t k; (k = next.fetch_add(1)) < n_pieces;) {
-            const int64_t l1 = std::min<int64_t>(n_loci, (k + 1) * piece);
-            for (int64_t l = k * piece; l < l1; ++l) strk_mi::host_locus(a, l, keys, tval, tcnt, ws);
-        }
-    };
     // threads: the CPUs this process may run on, at most OMP_NUM_THREADS where it is set and 16 where it is not (a machine
     // may show many more CPUs than a command is meant to use)
     int64_t cap = 16;
@@ -71,11 +61,14 @@ int strk_mi_trio_host(int32_t n_loci, const int64_t* grp_off, const int32_t* cn,
         const long v = strtol(e, nullptr, 10);
         if (v > 0) cap = std::min<long>(v, 256);
     }
-    const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)host_cpus(), cap, n_pieces}));
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t) th.emplace_back(body);
-    body();
-    for (auto& x : th) x.join();
+    struct Scratch {
+        std::vector<uint64_t> keys;
+        std::vector<int32_t> tval, tcnt;
+        std::vector<strk_mi::U128> ws;
+    };
+    strk_threads::parallel_chunks<Scratch>(n_loci, piece, (int)std::min<int64_t>({(int64_t)host_cpus(), cap, n_pieces}), [&](int64_t l0, int64_t l1, Scratch& s) {
+        for (int64_t l = l0; l < l1; ++l) strk_mi::host_locus(a, l, s.keys, s.tval, s.tcnt, s.ws);
+    });
     return 0;
 }
 

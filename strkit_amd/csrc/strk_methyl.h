@@ -188,8 +188,7 @@ struct Input {
     int32_t n_items;
     const int64_t* rec_off;
     const int64_t* coords;
-    const uint32_t* alt_cigar;       // optional, as in strk_extract_reads
-    const int64_t *alt_cigar_off, *alt_start;
+    strk_fe::AltCigars alt;          // optional, as in strk_extract_reads
     int32_t threshold;
 };
 
@@ -199,27 +198,10 @@ inline int check_input(const Input& in, strk_groups::Message* msg) {
     if (in.threshold < 0 || in.threshold > 255) return msg->invalid("threshold %d outside 0 .. 255", in.threshold);
     if (in.n_items == 0) return 0;
     if (!in.rec_off || !in.coords) return msg->invalid("NULL argument");
-    if ((in.alt_cigar == nullptr) != (in.alt_cigar_off == nullptr)) return msg->invalid("alt_cigar and alt_cigar_off must both be given or both be NULL");
-    if (in.alt_cigar_off && in.alt_cigar_off[0] != 0) return msg->invalid("alt_cigar_off[0] must be 0");
-    for (int32_t i = 0; i < in.n_items; ++i) {
+    if (strk_fe::check_alt(in.n_items, in.alt, msg)) return strk_groups::kInvalid;
+    for (int32_t i = 0; i < in.n_items; ++i)
         if (in.rec_off[i] < 0 || in.rec_off[i] > in.n_bytes - 4) return msg->invalid("item %d: rec_off outside the buffer", i);
-        if (in.alt_cigar_off) {
-            const int64_t n = in.alt_cigar_off[i + 1] - in.alt_cigar_off[i];
-            if (n < 0 || n > INT32_MAX) return msg->invalid("item %d: alt_cigar_off is decreasing (or a CIGAR too long)", i);
-        }
-    }
     return 0;
-}
-
-// the alignment an item is walked along
-STRK_FE_HD void item_alignment(const strk_fe::Rec& r, int32_t it, const uint32_t* alt_cigar, const int64_t* alt_off, const int64_t* alt_start,
-                               const uint8_t** cig, int32_t* n_cig, int64_t* start) {
-    *cig = r.cigar; *n_cig = r.n_cigar; *start = r.pos;
-    if (alt_off && alt_off[it + 1] > alt_off[it]) {   // a realigned read: its new alignment
-        *cig = reinterpret_cast<const uint8_t*>(alt_cigar + alt_off[it]);
-        *n_cig = (int32_t)(alt_off[it + 1] - alt_off[it]);
-        *start = alt_start ? alt_start[it] : 0;
-    }
 }
 
 // ---- host twin ------------------------------------------------------------------------------------------------------------------
@@ -233,7 +215,7 @@ inline int host_item(const uint8_t* buf, const Input& in, int32_t it, int32_t* s
     const uint8_t* cig;
     int32_t n_cig;
     int64_t start;
-    item_alignment(r, it, in.alt_cigar, in.alt_cigar_off, in.alt_start, &cig, &n_cig, &start);
+    strk_fe::item_alignment(r, it, in.alt, &cig, &n_cig, &start);
     Item x;
     const int st = item_prepare(buf, in.rec_off[it], r, cig, n_cig, start, in.coords + 4 * (size_t)it, &x);
     if (st != kOk) return st;
@@ -289,13 +271,13 @@ inline int host_item(const uint8_t* buf, const Input& in, int32_t it, int32_t* s
     return *known > 0 ? kOk : kNoSites;
 }
 
-// Items [i0, i1) of a checked call.  Returns -1, or the last item of the slice whose record or auxiliary chain is malformed.
+// Items [i0, i1) of a checked call.  Returns -1, or the first item of the slice whose record or auxiliary chain is malformed.
 inline int32_t host_methyl(const uint8_t* buf, const Input& in, int32_t i0, int32_t i1, int32_t* out_status, int32_t* out_sites,
                            int32_t* out_known, int32_t* out_mc) {
     int32_t bad = -1;
     for (int32_t it = i0; it < i1; ++it) {
         const int st = host_item(buf, in, it, &out_sites[it], &out_known[it], &out_mc[it]);
-        if (st == kBadChain) bad = it;
+        if (st == kBadChain && bad < 0) bad = it;
         out_status[it] = st == kBadChain ? kNotSpanning : st;
         if (st != kOk && st != kNoSites) out_sites[it] = 0;
     }
@@ -332,12 +314,12 @@ __device__ inline unsigned long long below(int lane) { return (1ull << lane) - 1
 //   per window of kWindow ordinals of the tract: the taken entry's numbers once more (an inclusive scan of d + 1 with a carry
 //     gives the ordinals, the walk resumes at the pass where the window before it ended) into the wave's LDS bytes (0 = no
 //     call, 1 = a call, 2 = a call above the threshold), then the tract's chunks, each lane testing its sites against them.
-// No floating point, no atomics but atomicMax(bad, item + 1) for a broken record; the counts are wave sums.
+// No floating point, no atomics but atomicMax(bad, INT32_MAX - item) for a broken record (the first such item wins); the counts
+// are wave sums.
 // item0: the first item of this launch (a call is cut into pieces of items).
 __global__ void __launch_bounds__(256) k_dbam_methyl(const uint8_t* data, int64_t n_data, int item0, int item1, const int64_t* rec_off,
-                                                     const int64_t* coords, const uint32_t* alt_cigar, const int64_t* alt_off,
-                                                     const int64_t* alt_start, int threshold, int32_t* out_status, int32_t* out_sites,
-                                                     int32_t* out_known, int32_t* out_mc, int32_t* bad) {
+                                                     const int64_t* coords, strk_fe::AltCigars alt, int threshold, int32_t* out_status,
+                                                     int32_t* out_sites, int32_t* out_known, int32_t* out_mc, int32_t* bad) {
     // win_mem[w] belongs to wave w alone: its lanes store bytes into it and other lanes of the SAME wave load them afterwards.  A
     // wave issues its LDS operations in order and the loops around them are wave-uniform (every lane is at the same store and at
     // the same load), so __threadfence_block(), which keeps the compiler and the memory counters from moving a load in front of a
@@ -358,11 +340,11 @@ __global__ void __launch_bounds__(256) k_dbam_methyl(const uint8_t* data, int64_
         const uint8_t* cig;
         int32_t n_cig;
         int64_t start;
-        item_alignment(r, it, alt_cigar, alt_off, alt_start, &cig, &n_cig, &start);
+        strk_fe::item_alignment(r, it, alt, &cig, &n_cig, &start);
         st = item_prepare(data, rec_off[it], r, cig, n_cig, start, coords + 4 * (size_t)it, &x);
     }
     if (st == kBadChain) {
-        if (lane == 0) atomicMax(bad, it + 1);
+        if (lane == 0) atomicMax(bad, INT32_MAX - it);
         return finish(kNotSpanning, 0, 0, 0);
     }
     if (st != kOk) return finish(st, 0, 0, 0);

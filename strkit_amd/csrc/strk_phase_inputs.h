@@ -155,8 +155,7 @@ struct CellsInput {
     int32_t n_loci;
     const int32_t* cand_off;
     const int64_t* cand_pos;
-    const uint32_t* alt_cigar;       // optional, as in strk_extract_reads
-    const int64_t *alt_cigar_off, *alt_start;
+    strk_fe::AltCigars alt;          // optional, as in strk_extract_reads
     int32_t clip_threshold, take_in;
 };
 
@@ -179,15 +178,10 @@ inline int check_cells(const CellsInput& in, std::vector<int64_t>& cell_off, str
     cell_off.push_back(0);
     if (in.n_items == 0) return 0;
     if (!in.rec_off || !in.item_locus) return msg->invalid("NULL argument");
-    if ((in.alt_cigar == nullptr) != (in.alt_cigar_off == nullptr)) return msg->invalid("alt_cigar and alt_cigar_off must both be given or both be NULL");
-    if (in.alt_cigar_off && in.alt_cigar_off[0] != 0) return msg->invalid("alt_cigar_off[0] must be 0");
+    if (strk_fe::check_alt(in.n_items, in.alt, msg)) return strk_groups::kInvalid;
     for (int32_t i = 0; i < in.n_items; ++i) {
         if (in.rec_off[i] < 0 || in.rec_off[i] > in.n_bytes - 4) return msg->invalid("item %d: rec_off outside the buffer", i);
         if (in.item_locus[i] < 0 || in.item_locus[i] >= in.n_loci) return msg->invalid("item %d: item_locus out of range", i);
-        if (in.alt_cigar_off) {
-            const int64_t n = in.alt_cigar_off[i + 1] - in.alt_cigar_off[i];
-            if (n < 0 || n > INT32_MAX) return msg->invalid("item %d: alt_cigar_off is decreasing (or a CIGAR too long)", i);
-        }
         cell_off.push_back(cell_off.back() + (in.cand_off[in.item_locus[i] + 1] - in.cand_off[in.item_locus[i]]));
     }
     return 0;
@@ -230,14 +224,10 @@ inline int32_t host_cells(const uint8_t* buf, const CellsInput& in, const int64_
         if (!strk_fe::parse_rec(buf, in.n_bytes, in.rec_off[it], &r, &next)) return it;
         if (!rec_tags(buf, in.rec_off[it], r, &out_hp[it], &out_ps[it])) return it;
         const int32_t l = in.item_locus[it];
-        const uint8_t* cig = r.cigar;
-        int32_t n_cig = r.n_cigar;
-        int64_t start = r.pos;
-        if (in.alt_cigar_off && in.alt_cigar_off[it + 1] > in.alt_cigar_off[it]) {   // a realigned read: its new alignment
-            cig = reinterpret_cast<const uint8_t*>(in.alt_cigar + in.alt_cigar_off[it]);
-            n_cig = (int32_t)(in.alt_cigar_off[it + 1] - in.alt_cigar_off[it]);
-            start = in.alt_start ? in.alt_start[it] : 0;
-        }
+        const uint8_t* cig;
+        int32_t n_cig;
+        int64_t start;
+        strk_fe::item_alignment(r, it, in.alt, &cig, &n_cig, &start);
         item_cells(r, cig, n_cig, start, in.clip_threshold, in.take_in, in.cand_pos + in.cand_off[l], in.cand_off[l + 1] - in.cand_off[l],
                    out_base + cell_off[it], out_qual + cell_off[it]);
     }
@@ -287,9 +277,9 @@ __device__ inline int64_t wave_scan_incl(int64_t v, int lane) {
 // item0: the first item of this launch (a call is cut into pieces of items).
 __global__ void __launch_bounds__(256) k_dbam_phase_cells(const uint8_t* data, int64_t n_data, int item0, int item1, const int64_t* rec_off,
                                                           const int32_t* item_locus, const int32_t* cand_off, const int64_t* cand_pos,
-                                                          const int64_t* cell_off, const uint32_t* alt_cigar, const int64_t* alt_off,
-                                                          const int64_t* alt_start, int clip_threshold, int take_in, int32_t* hp,
-                                                          int32_t* ps, uint8_t* cells_base, uint8_t* cells_qual, int32_t* bad) {
+                                                          const int64_t* cell_off, strk_fe::AltCigars alt, int clip_threshold, int take_in,
+                                                          int32_t* hp, int32_t* ps, uint8_t* cells_base, uint8_t* cells_qual,
+                                                          int32_t* bad) {
     const int lane = threadIdx.x & 63;
     const int it = item0 + blockIdx.x * 4 + (threadIdx.x >> 6);
     if (it >= item1) return;
@@ -304,19 +294,15 @@ __global__ void __launch_bounds__(256) k_dbam_phase_cells(const uint8_t* data, i
     const bool ok = strk_fe::parse_rec(data, n_data, rec_off[it], &r, &next);
     if (lane == 0) {
         int32_t h = -1, p = -1;
-        if (!ok || !rec_tags(data, rec_off[it], r, &h, &p)) atomicMax(bad, it + 1);
+        if (!ok || !rec_tags(data, rec_off[it], r, &h, &p)) atomicMax(bad, INT32_MAX - it);
         hp[it] = h; ps[it] = p;
     }
     if (!ok) return;
     __threadfence_block();
-    const uint8_t* cig = r.cigar;
-    int32_t n_cig = r.n_cigar;
-    int64_t car_r = r.pos, car_q = 0;
-    if (alt_off && alt_off[it + 1] > alt_off[it]) {   // a realigned read: its new alignment
-        cig = reinterpret_cast<const uint8_t*>(alt_cigar + alt_off[it]);
-        n_cig = (int32_t)(alt_off[it + 1] - alt_off[it]);
-        car_r = alt_start ? alt_start[it] : 0;
-    }
+    const uint8_t* cig;
+    int32_t n_cig;
+    int64_t car_r, car_q = 0;
+    strk_fe::item_alignment(r, it, alt, &cig, &n_cig, &car_r);
     const bool has_qual = !(r.l_seq > 0 && r.qual[0] == 0xFF);
     int32_t clip_l, clip_r;
     cigar_clips(cig, n_cig, &clip_l, &clip_r);

@@ -5,18 +5,6 @@
 
 namespace {
 
-// body(first item, last item) over contiguous slices of n items, one thread per 1 024 items (as strk_extract_reads)
-template <class Body>
-void pi_parallel(int32_t n, Body&& body) {
-    const int nt = std::max(1, std::min<int>({host_cpus(), 32, n / 1024}));
-    const int32_t per = (n + nt - 1) / std::max(nt, 1);
-    std::vector<std::thread> th;
-    for (int t = 1; t < nt; ++t)
-        if (t * per < n) th.emplace_back(body, t * per, std::min(n, (t + 1) * per));
-    body(0, std::min(n, per));
-    for (auto& x : th) x.join();
-}
-
 // snv_off and the packed offsets from the loci's choices; returns the number of packed cells
 int64_t pi_offsets(int32_t n_loci, const int32_t* kept_off, const int32_t* n_sel, int32_t* snv_off, std::vector<int64_t>& pack_off) {
     pack_off.assign((size_t)n_loci + 1, 0);
@@ -36,7 +24,7 @@ int strk_phase_cells(const uint8_t* buf, int64_t n_bytes, int32_t n_items, const
                      int32_t n_loci, const int32_t* cand_off, const int64_t* cand_pos, const uint32_t* alt_cigar,
                      const int64_t* alt_cigar_off, const int64_t* alt_start, int32_t clip_threshold, int32_t take_in, int32_t* out_hp,
                      int32_t* out_ps, uint8_t* out_base, uint8_t* out_qual, int64_t cell_cap) {
-    const strk_pi::CellsInput in{n_bytes, n_items, rec_off, item_locus, n_loci, cand_off, cand_pos, alt_cigar, alt_cigar_off, alt_start,
+    const strk_pi::CellsInput in{n_bytes, n_items, rec_off, item_locus, n_loci, cand_off, cand_pos, {alt_cigar, alt_cigar_off, alt_start},
                                  clip_threshold, take_in};
     strk_groups::Message msg;
     std::vector<int64_t> cell_off;
@@ -46,15 +34,12 @@ int strk_phase_cells(const uint8_t* buf, int64_t n_bytes, int32_t n_items, const
     if (cell_off.back() > 0 && (!out_base || !out_qual)) return fail(STRK_E_INVALID, "strk_phase_cells: NULL argument");
     if (cell_cap < cell_off.back())
         return fail(STRK_E_NOMEM, "strk_phase_cells: cell buffers too small (%lld < %lld)", (long long)cell_cap, (long long)cell_off.back());
-    std::atomic<int32_t> bad{INT32_MAX};
-    pi_parallel(n_items, [&](int32_t i0, int32_t i1) {
+    strk_threads::FirstBad bad;
+    strk_threads::parallel_slices(n_items, 1024, 32, [&](int32_t i0, int32_t i1) {
         const int32_t b = strk_pi::host_cells(buf, in, cell_off.data(), i0, i1, out_hp, out_ps, out_base, out_qual);
-        if (b >= 0) {
-            int32_t cur = bad.load();
-            while (b < cur && !bad.compare_exchange_weak(cur, b)) {}
-        }
+        if (b >= 0) bad.report(b);
     });
-    if (bad.load() != INT32_MAX) return fail(STRK_E_INVALID, "strk_phase_cells: item %d: malformed BAM record or auxiliary fields", bad.load());
+    if (bad.get() >= 0) return fail(STRK_E_INVALID, "strk_phase_cells: item %d: malformed BAM record or auxiliary fields", (int)bad.get());
     return 0;
 }
 
@@ -81,7 +66,7 @@ int64_t strk_useful_snvs(int32_t n_items, const int32_t* item_locus, int32_t n_l
     if (strk_pi::check_useful(in, &msg)) return fail(STRK_E_INVALID, "strk_useful_snvs: %s", msg.text);
     if (!out_snv_cand || (cell_off.back() > 0 && (!cells_base || !cells_qual))) return fail(STRK_E_INVALID, "strk_useful_snvs: NULL argument");
     std::vector<int32_t> n_sel((size_t)n_loci), sel((size_t)n_loci * strk_pi::kMaxSnvs);
-    pi_parallel(n_loci, [&](int32_t l0, int32_t l1) {
+    strk_threads::parallel_slices(n_loci, 1024, 32, [&](int32_t l0, int32_t l1) {
         for (int32_t l = l0; l < l1; ++l)
             n_sel[(size_t)l] = strk_pi::host_useful_locus(in, cand_off, cell_off.data(), cells_base, l, sel.data() + (size_t)l * strk_pi::kMaxSnvs);
     });
@@ -109,7 +94,7 @@ int strk_dbam_phase_cells(strk_dbam* d, int32_t n_items, const int64_t* rec_off,
                           int32_t* out_ps) {
     if (!d || piece_items < 0) return fail(STRK_E_INVALID, "strk_dbam_phase_cells: bad argument");
     d->pc_valid = false;
-    const strk_pi::CellsInput in{d->n_data, n_items, rec_off, item_locus, n_loci, cand_off, cand_pos, alt_cigar, alt_cigar_off, alt_start,
+    const strk_pi::CellsInput in{d->n_data, n_items, rec_off, item_locus, n_loci, cand_off, cand_pos, {alt_cigar, alt_cigar_off, alt_start},
                                  clip_threshold, take_in};
     strk_groups::Message msg;
     if (strk_pi::check_cells(in, d->pc_cell_off_h, &msg)) return fail(STRK_E_INVALID, "strk_dbam_phase_cells: %s", msg.text);
@@ -124,49 +109,34 @@ int strk_dbam_phase_cells(strk_dbam* d, int32_t n_items, const int64_t* rec_off,
     if (n_items == 0) { d->pc_valid = true; return 0; }
     HIP_TRY(hipSetDevice(d->device));
     const size_t n = (size_t)n_items, n_cand = (size_t)cand_off[n_loci];
-    const bool alt = alt_cigar_off && alt_cigar_off[n] > 0;
-    const size_t n_ops = alt ? (size_t)alt_cigar_off[n] : 0;
-    // pc_in: rec_off | alt_off | alt_start | cand_pos | item_locus | hp | ps | alt ops | bad
-    Carve cv;
-    const size_t o_rec = cv.take(n * 8), o_aoff = cv.take((n + 1) * 8), o_astart = cv.take(n * 8), o_cand = cv.take(n_cand * 8 + 8),
-                 o_loc = cv.take(n * 4), o_hp = cv.take(n * 4), o_ps = cv.take(n * 4), o_ops = cv.take(n_ops * 4 + 4), o_bad = cv.take(4);
+    // pc_in: rec_off | item_locus | cand_pos | cand_off | cell_off | alt | bad || hp | ps
+    Staging st(d->stage);
+    const size_t o_rec = st.put(rec_off, n * 8), o_loc = st.put(item_locus, n * 4), o_cand = st.put(cand_pos, n_cand * 8);
+    d->pc_cand_off = st.put(cand_off, ((size_t)n_loci + 1) * 4);
+    d->pc_cell_off = st.put(cell_off.data(), (n + 1) * 8);
+    const StagedAlt s_alt = stage_alt(st, n, in.alt);
+    const size_t o_bad = st.zero(4), o_hp = st.room(n * 4), o_ps = st.room(n * 4);
     int rc;
-    if ((rc = d->pc_in.ensure(cv.bytes)) || (rc = d->pc_cells.ensure((size_t)(2 * n_cells) + 16)) || (rc = d->pc_cell_off.ensure((n + 1) * 8)) ||
-        (rc = d->pc_cand_off.ensure(((size_t)n_loci + 1) * 4)))
-        return rc;
-    HIP_TRY(hipMemcpy(d->pc_in.at<char>(o_rec), rec_off, n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d->pc_in.at<char>(o_loc), item_locus, n * 4, hipMemcpyHostToDevice));
-    if (n_cand) HIP_TRY(hipMemcpy(d->pc_in.at<char>(o_cand), cand_pos, n_cand * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d->pc_cand_off.p, cand_off, ((size_t)n_loci + 1) * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d->pc_cell_off.p, cell_off.data(), (n + 1) * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d->pc_in.at<char>(o_bad), 0, 4));
-    if (alt) {
-        HIP_TRY(hipMemcpy(d->pc_in.at<char>(o_ops), alt_cigar, n_ops * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(d->pc_in.at<char>(o_aoff), alt_cigar_off, (n + 1) * 8, hipMemcpyHostToDevice));
-        if (alt_start) HIP_TRY(hipMemcpy(d->pc_in.at<char>(o_astart), alt_start, n * 8, hipMemcpyHostToDevice));
-        else HIP_TRY(hipMemset(d->pc_in.at<char>(o_astart), 0, n * 8));
-    }
+    if ((rc = st.upload(d->pc_in)) || (rc = d->pc_cells.ensure((size_t)(2 * n_cells) + 16))) return rc;
     uint8_t* const cells_base = d->pc_cells.as<uint8_t>();
     uint8_t* const cells_qual = cells_base + n_cells;
     // launches of at most piece_items items (0: all of them in one); every item's cells have their place, so the cut changes nothing
-    const int32_t piece = piece_items > 0 ? piece_items : n_items;
     d->tic();
-    for (int32_t i0 = 0; i0 < n_items; i0 += piece) {
-        const int32_t i1 = std::min<int64_t>(n_items, (int64_t)i0 + piece);
+    rc = strk_threads::for_pieces(n_items, piece_items, [&](int32_t i0, int32_t i1) {
         hipLaunchKernelGGL(strk_pi::k_dbam_phase_cells, dim3((unsigned)((i1 - i0 + 3) / 4)), dim3(256), 0, 0, d->data.as<uint8_t>(), d->n_data, i0,
-                           i1, d->pc_in.at<int64_t>(o_rec), d->pc_in.at<int32_t>(o_loc), d->pc_cand_off.as<int32_t>(), d->pc_in.at<int64_t>(o_cand),
-                           d->pc_cell_off.as<int64_t>(), alt ? d->pc_in.at<uint32_t>(o_ops) : (const uint32_t*)nullptr,
-                           alt ? d->pc_in.at<int64_t>(o_aoff) : (const int64_t*)nullptr, alt ? d->pc_in.at<int64_t>(o_astart) : (const int64_t*)nullptr,
-                           clip_threshold, take_in, d->pc_in.at<int32_t>(o_hp), d->pc_in.at<int32_t>(o_ps), cells_base, cells_qual,
-                           d->pc_in.at<int32_t>(o_bad));
+                           i1, d->pc_in.at<int64_t>(o_rec), d->pc_in.at<int32_t>(o_loc), d->pc_in.at<int32_t>(d->pc_cand_off),
+                           d->pc_in.at<int64_t>(o_cand), d->pc_in.at<int64_t>(d->pc_cell_off), s_alt.on(d->pc_in), clip_threshold, take_in,
+                           d->pc_in.at<int32_t>(o_hp), d->pc_in.at<int32_t>(o_ps), cells_base, cells_qual, d->pc_in.at<int32_t>(o_bad));
         HIP_TRY(hipGetLastError());
-    }
+        return 0;
+    });
+    if (rc) return rc;
     d->toc();
-    int32_t bad = 0;
-    HIP_TRY(hipMemcpy(&bad, d->pc_in.at<char>(o_bad), 4, hipMemcpyDeviceToHost));
-    if (bad) return fail(STRK_E_INVALID, "strk_dbam_phase_cells: item %d: malformed BAM record or auxiliary fields", bad - 1);
-    HIP_TRY(hipMemcpy(out_hp, d->pc_in.at<char>(o_hp), n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(out_ps, d->pc_in.at<char>(o_ps), n * 4, hipMemcpyDeviceToHost));
+    if ((rc = st.download(d->pc_in, o_bad, st.cv.bytes))) return rc;
+    const int64_t bad = strk_threads::first_bad_of_word(*st.at<int32_t>(o_bad), INT32_MAX);
+    if (bad >= 0) return fail(STRK_E_INVALID, "strk_dbam_phase_cells: item %d: malformed BAM record or auxiliary fields", (int)bad);
+    memcpy(out_hp, st.at<int32_t>(o_hp), n * 4);
+    memcpy(out_ps, st.at<int32_t>(o_ps), n * 4);
     d->pc_valid = true;
     return 0;
 }
@@ -194,42 +164,44 @@ int64_t strk_dbam_useful_snvs(strk_dbam* d, int32_t n_loci, const int32_t* kept_
     out_snv_off[0] = 0;
     if (n_loci == 0) return 0;
     if (!out_snv_cand) return fail(STRK_E_INVALID, "strk_dbam_useful_snvs: NULL argument");
+    if (d->pc_item_locus.empty()) {   // a cells call without items staged nothing: no locus has a read, none a useful SNV
+        std::fill(out_snv_off, out_snv_off + n_loci + 1, 0);
+        return 0;
+    }
     HIP_TRY(hipSetDevice(d->device));
     const size_t nl = (size_t)n_loci, n_kept = (size_t)kept_off[n_loci];
-    // pc_work: kept_off | kept_item | n_sel | sel | pack_off
-    Carve cv;
-    const size_t o_koff = cv.take((nl + 1) * 4), o_kit = cv.take(n_kept * 4 + 4), o_nsel = cv.take(nl * 4), o_sel = cv.take(nl * strk_pi::kMaxSnvs * 4),
-                 o_pack = cv.take((nl + 1) * 8);
+    // w_a: kept_off | kept_item || n_sel | sel || pack_off
+    Staging st(d->stage);
+    const size_t o_koff = st.put(kept_off, (nl + 1) * 4), o_kit = st.put(kept_item, n_kept * 4);
+    const size_t o_nsel = st.room(nl * 4), o_sel = st.room(nl * strk_pi::kMaxSnvs * 4), o_pack = st.room((nl + 1) * 8);
     int rc;
-    if ((rc = d->pc_work.ensure(cv.bytes))) return rc;
-    HIP_TRY(hipMemcpy(d->pc_work.at<char>(o_koff), kept_off, (nl + 1) * 4, hipMemcpyHostToDevice));
-    if (n_kept) HIP_TRY(hipMemcpy(d->pc_work.at<char>(o_kit), kept_item, n_kept * 4, hipMemcpyHostToDevice));
+    if ((rc = st.upload(d->w_a))) return rc;
     const int64_t n_cells = d->pc_cell_off_h.back();
     const uint8_t* const cells_base = d->pc_cells.as<uint8_t>();
+    const int64_t* const d_cell_off = d->pc_in.at<int64_t>(d->pc_cell_off);
     d->tic();
-    hipLaunchKernelGGL(strk_pi::k_snv_useful, dim3((unsigned)n_loci), dim3(256), 0, 0, d->pc_cand_off.as<int32_t>(), d->pc_work.at<int32_t>(o_koff),
-                       d->pc_work.at<int32_t>(o_kit), d->pc_cell_off.as<int64_t>(), cells_base, min_allele_reads, d->pc_work.at<int32_t>(o_nsel),
-                       d->pc_work.at<int32_t>(o_sel));
+    hipLaunchKernelGGL(strk_pi::k_snv_useful, dim3((unsigned)n_loci), dim3(256), 0, 0, d->pc_in.at<int32_t>(d->pc_cand_off), d->w_a.at<int32_t>(o_koff),
+                       d->w_a.at<int32_t>(o_kit), d_cell_off, cells_base, min_allele_reads, d->w_a.at<int32_t>(o_nsel), d->w_a.at<int32_t>(o_sel));
     HIP_TRY(hipGetLastError());
     d->toc();
-    std::vector<int32_t> n_sel(nl), sel(nl * strk_pi::kMaxSnvs);
-    HIP_TRY(hipMemcpy(n_sel.data(), d->pc_work.at<char>(o_nsel), nl * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(sel.data(), d->pc_work.at<char>(o_sel), nl * strk_pi::kMaxSnvs * 4, hipMemcpyDeviceToHost));
+    if ((rc = st.download(d->w_a, o_nsel, o_pack))) return rc;
+    const int32_t* const n_sel = st.at<int32_t>(o_nsel);
+    const int32_t* const sel = st.at<int32_t>(o_sel);
     std::vector<int64_t> pack_off;
-    const int64_t total = pi_offsets(n_loci, kept_off, n_sel.data(), out_snv_off, pack_off);
+    const int64_t total = pi_offsets(n_loci, kept_off, n_sel, out_snv_off, pack_off);
     for (int32_t l = 0; l < n_loci; ++l)
         for (int32_t j = 0; j < n_sel[(size_t)l]; ++j) out_snv_cand[out_snv_off[l] + j] = sel[(size_t)l * strk_pi::kMaxSnvs + j];
     if (total > cap || total == 0) return total;
     if (!out_base || !out_qual) return fail(STRK_E_INVALID, "strk_dbam_useful_snvs: NULL argument");
     if ((rc = d->w_f.ensure((size_t)(2 * total) + 16))) return rc;
-    HIP_TRY(hipMemcpy(d->pc_work.at<char>(o_pack), pack_off.data(), (nl + 1) * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d->w_a.at<char>(o_pack), pack_off.data(), (nl + 1) * 8, hipMemcpyHostToDevice));
     d->tic();
-    hipLaunchKernelGGL(strk_pi::k_snv_gather, dim3((unsigned)n_loci), dim3(256), 0, 0, d->pc_work.at<int32_t>(o_koff), d->pc_work.at<int32_t>(o_kit),
-                       d->pc_cell_off.as<int64_t>(), cells_base, cells_base + n_cells, d->pc_work.at<int32_t>(o_nsel), d->pc_work.at<int32_t>(o_sel),
-                       d->pc_work.at<int64_t>(o_pack), d->w_f.as<uint8_t>(), d->w_f.as<uint8_t>() + total);
+    hipLaunchKernelGGL(strk_pi::k_snv_gather, dim3((unsigned)n_loci), dim3(256), 0, 0, d->w_a.at<int32_t>(o_koff), d->w_a.at<int32_t>(o_kit), d_cell_off,
+                       cells_base, cells_base + n_cells, d->w_a.at<int32_t>(o_nsel), d->w_a.at<int32_t>(o_sel), d->w_a.at<int64_t>(o_pack),
+                       d->w_f.as<uint8_t>(), d->w_f.as<uint8_t>() + total);
     HIP_TRY(hipGetLastError());
     d->toc();
-    HIP_TRY(hipMemcpy(out_base, d->w_f.p, (size_t)total, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out_base, d->w_f.p, (size_t)total, hipMemcpyDeviceToHost));   // (straight into the caller's two arrays)
     HIP_TRY(hipMemcpy(out_qual, d->w_f.as<uint8_t>() + total, (size_t)total, hipMemcpyDeviceToHost));
     return total;
 }

@@ -34,23 +34,17 @@ int strk_dbam_select_reads(strk_dbam* d, int32_t n_loci, const int64_t* item_off
     }
     const size_t n_small = lists.size(), n_large = large.size();
     lists.insert(lists.end(), large.begin(), large.end());
-    // one upload into w_a: item_off | rec_off | table_off | the lists;  one download from w_b: bad | n_kept | reason | status;
+    // w_a: item_off | rec_off | table_off | the lists | bad | n_kept || reason | status;
     // w_d: rep | first | status of the large tables;  w_f: slot_why of the large loci's items
-    Carve ca, cb, cd;
-    const size_t a_item = ca.take((nl + 1) * 8), a_rec = ca.take(n * 8), a_toff = ca.take(n_large * 8 + 8), a_lists = ca.take(nl * 4);
-    const size_t b_bad = cb.take(4), b_kept = cb.take(nl * 4), b_reason = cb.take(n), b_status = cb.take(n);
+    Staging st(d->stage);
+    const size_t a_item = st.put(item_off, (nl + 1) * 8), a_rec = st.put(rec_off, n * 8), a_toff = st.put(table_off.data(), n_large * 8),
+                 a_lists = st.put(lists.data(), nl * 4), b_bad = st.zero(4), b_kept = st.zero(nl * 4), b_reason = st.room(n), b_status = st.room(n);
+    Carve cd;
     const size_t d_rep = cd.take((size_t)n_slots * 4), d_first = cd.take((size_t)n_slots * 4), d_status = cd.take((size_t)n_slots * 4);
     int rc;
-    if ((rc = d->w_a.ensure(ca.bytes)) || (rc = d->w_b.ensure(cb.bytes))) return rc;
-    if (n_large && ((rc = d->w_d.ensure(cd.bytes)) || (rc = d->w_f.ensure(n * 4)))) return rc;
-    std::vector<uint8_t> host(std::max(ca.bytes, cb.bytes));
-    memcpy(host.data() + a_item, item_off, (nl + 1) * 8);
-    memcpy(host.data() + a_rec, rec_off, n * 8);
-    if (n_large) memcpy(host.data() + a_toff, table_off.data(), n_large * 8);
-    memcpy(host.data() + a_lists, lists.data(), nl * 4);
-    HIP_TRY(hipMemcpy(d->w_a.p, host.data(), ca.bytes, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemset(d->w_b.at<char>(b_bad), 0, b_reason - b_bad));                     // bad and n_kept
+    if ((rc = st.upload(d->w_a))) return rc;
     if (n_large) {
+        if ((rc = d->w_d.ensure(cd.bytes)) || (rc = d->w_f.ensure(n * 4))) return rc;
         HIP_TRY(hipMemset(d->w_d.at<char>(d_rep), 0xFF, d_status - d_rep));              // rep = -1, first = kNoItem
         HIP_TRY(hipMemset(d->w_d.at<char>(d_status), 0, (size_t)n_slots * 4));
     }
@@ -58,10 +52,10 @@ int strk_dbam_select_reads(strk_dbam* d, int32_t n_loci, const int64_t* item_off
     const int64_t* const d_item = d->w_a.at<int64_t>(a_item);
     const int64_t* const d_rec = d->w_a.at<int64_t>(a_rec);
     const int32_t* const d_lists = d->w_a.at<int32_t>(a_lists);
-    uint8_t* const o_reason = d->w_b.at<uint8_t>(b_reason);
-    uint8_t* const o_status = d->w_b.at<uint8_t>(b_status);
-    int32_t* const o_kept = d->w_b.at<int32_t>(b_kept);
-    int32_t* const o_bad = d->w_b.at<int32_t>(b_bad);
+    uint8_t* const o_reason = d->w_a.at<uint8_t>(b_reason);
+    uint8_t* const o_status = d->w_a.at<uint8_t>(b_status);
+    int32_t* const o_kept = d->w_a.at<int32_t>(b_kept);
+    int32_t* const o_bad = d->w_a.at<int32_t>(b_bad);
     d->tic();
     if (n_small)
         hipLaunchKernelGGL(strk_sel::k_select_small, dim3((unsigned)n_small), dim3(strk_sel::kThreads), 0, 0, data, d->n_data, d_lists,
@@ -73,13 +67,12 @@ int strk_dbam_select_reads(strk_dbam* d, int32_t n_loci, const int64_t* item_off
                            d->w_f.as<int32_t>(), o_reason, o_status, o_kept, o_bad);
     HIP_TRY(hipGetLastError());
     d->toc();
-    HIP_TRY(hipMemcpy(host.data(), d->w_b.p, cb.bytes, hipMemcpyDeviceToHost));
-    int32_t bad = 0;
-    memcpy(&bad, host.data() + b_bad, 4);
-    if (bad) return fail(STRK_E_INVALID, "strk_dbam_select_reads: item %lld: malformed BAM record", (long long)n - bad);
-    memcpy(out_n_kept, host.data() + b_kept, nl * 4);
-    memcpy(out_reason, host.data() + b_reason, n);
-    memcpy(out_status, host.data() + b_status, n);
+    if ((rc = st.download(d->w_a, b_bad, st.cv.bytes))) return rc;
+    const int64_t bad = strk_threads::first_bad_of_word(*st.at<int32_t>(b_bad), (int64_t)n);
+    if (bad >= 0) return fail(STRK_E_INVALID, "strk_dbam_select_reads: item %lld: malformed BAM record", (long long)bad);
+    memcpy(out_n_kept, st.at<char>(b_kept), nl * 4);
+    memcpy(out_reason, st.at<char>(b_reason), n);
+    memcpy(out_status, st.at<char>(b_status), n);
     return 0;
 }
 

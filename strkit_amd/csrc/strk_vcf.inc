@@ -42,7 +42,7 @@ int64_t strk_vcf_snvs(const uint8_t* buf, int64_t n_bytes, int64_t start, const 
     if (rc) return rc;
     if (!buf && n_bytes > 0) return fail(STRK_E_INVALID, "%s: NULL argument", who);
     strk_vcf::Walk w;
-    strk_vcf::snvs_host(buf, n_bytes, start, contig, beg, end, final, contig_seen, &w, [](int32_t n, auto&& body) { pi_parallel(n, body); });
+    strk_vcf::snvs_host(buf, n_bytes, start, contig, beg, end, final, contig_seen, &w, [](int32_t n, auto&& body) { strk_threads::parallel_slices(n, 1024, 32, body); });
     *end_off = w.end_off; *past = w.past;
     return vcf_finish(who, w.kept, w.bad_off, prev_pos, cap, pos, ref, id_off, ids, ids_cap, id_bytes);
 }

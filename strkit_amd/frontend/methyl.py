@@ -219,13 +219,12 @@ def methyl(bam, rec: np.ndarray, coords: np.ndarray, alt: dict[int, tuple[np.nda
     """status / sites / known / mc (int32 arrays) of items (record index, four locus boundaries) of a reader of
     frontend/native.py; `alt` maps item number to (read-alignment CIGAR, reference start) for realigned reads.  A DeviceBam
     runs k_dbam_methyl over the file in HBM, a host reader strk_methyl over its buffer."""
-    from .native import DeviceBam
-    from .phase_inputs import _alt_arrays
+    from .native import DeviceBam, alt_arrays
     L = _lib.load()
     n = int(len(rec))
     rec_off = np.ascontiguousarray(bam.rec_off[np.asarray(rec, np.int64)], np.int64)
     coords = np.ascontiguousarray(coords, np.int64).reshape(n, 4)
-    a_cig, a_off, a_start = _alt_arrays(n, alt)
+    a_cig, a_off, a_start = alt_arrays(n, alt)
     out = {k: np.zeros(n, np.int32) for k in ("status", "sites", "known", "mc")}
     outs = [_lib.ptr(out[k]) for k in ("status", "sites", "known", "mc")]
     if isinstance(bam, DeviceBam):

@@ -631,6 +631,22 @@ def realign_cigar_to_read_alignment(cigar: np.ndarray) -> np.ndarray:
     return out
 
 
+def alt_arrays(n: int, alt: dict[int, tuple[np.ndarray, int]] | None):
+    """The substitute alignments of n items as the library takes them (alt_cigar, alt_cigar_off, alt_start); three None
+    without any.  `alt` maps item number to (read-alignment CIGAR, reference start) for realigned reads."""
+    if not alt:
+        return None, None, None
+    a_off = np.zeros(n + 1, np.int64)
+    a_start = np.zeros(n, np.int64)
+    parts = []
+    for i in range(n):
+        if i in alt:
+            parts.append(np.asarray(alt[i][0], np.uint32))
+            a_start[i] = alt[i][1]
+        a_off[i + 1] = a_off[i] + (parts[-1].size if i in alt else 0)
+    return (np.concatenate(parts) if parts else np.zeros(1, np.uint32)), a_off, a_start
+
+
 def extract_reads(bam: NativeBam, rec_idx: np.ndarray, coords: np.ndarray, flank_size: int, min_avg_phred: int,
                   wildcard_threshold: int = 3, alt: dict[int, tuple[np.ndarray, int]] | None = None) -> dict:
     """strk_extract_reads for items (record index, four locus boundaries).  `alt` maps item number to
@@ -640,41 +656,20 @@ def extract_reads(bam: NativeBam, rec_idx: np.ndarray, coords: np.ndarray, flank
     coords = np.ascontiguousarray(coords, np.int64).reshape(n, 4)
     status, nfl, ntr, nfr = (np.zeros(n, np.int32) for _ in range(4))
     seq_off = np.zeros(n + 1, np.int64)
-    a_cig = a_off = a_start = None
-    if alt:
-        a_off = np.zeros(n + 1, np.int64)
-        a_start = np.zeros(n, np.int64)
-        parts = []
-        for i in range(n):
-            if i in alt:
-                parts.append(np.asarray(alt[i][0], np.uint32))
-                a_start[i] = alt[i][1]
-                a_off[i + 1] = a_off[i] + parts[-1].size
-            else:
-                a_off[i + 1] = a_off[i]
-        a_cig = np.concatenate(parts) if parts else np.zeros(1, np.uint32)
+    a_cig, a_off, a_start = alt_arrays(n, alt)
+    L = _lib.load()
+    items = (n, _lib.ptr(rec_off), _lib.ptr(coords), _lib.ptr(a_cig), _lib.ptr(a_off), _lib.ptr(a_start), int(flank_size),
+             int(min_avg_phred), int(wildcard_threshold), _lib.ptr(status), _lib.ptr(nfl), _lib.ptr(ntr), _lib.ptr(nfr))
     if isinstance(bam, DeviceBam):
         name_len = np.zeros(max(n, 1), np.int32)
         d_seqs = C.c_void_p()
-        _lib.check(_lib.load().strk_dbam_extract(bam._h, n, rec_off.ctypes.data, coords.ctypes.data,
-                                                 a_cig.ctypes.data if a_cig is not None else None,
-                                                 a_off.ctypes.data if a_off is not None else None,
-                                                 a_start.ctypes.data if a_start is not None else None,
-                                                 int(flank_size), int(min_avg_phred), int(wildcard_threshold), status.ctypes.data,
-                                                 nfl.ctypes.data, ntr.ctypes.data, nfr.ctypes.data, seq_off.ctypes.data,
-                                                 name_len.ctypes.data, C.byref(d_seqs)))
+        _lib.check(L.strk_dbam_extract(bam._h, *items, _lib.ptr(seq_off), _lib.ptr(name_len), C.byref(d_seqs)))
         # the bases stay on the device: `seqs` is a stand-in for code that only asks for sizes
         return {"status": status, "nfl": nfl, "ntr": ntr, "nfr": nfr, "seqs": np.zeros(1, np.uint8), "seq_off": seq_off,
                 "d_seqs": d_seqs.value}
-    L = _lib.load()
 
     def call(seqs_ptr, cap):
-        return L.strk_extract_reads(bam.data.ctypes.data, bam.data.size, n, rec_off.ctypes.data, coords.ctypes.data,
-                                    a_cig.ctypes.data if a_cig is not None else None,
-                                    a_off.ctypes.data if a_off is not None else None,
-                                    a_start.ctypes.data if a_start is not None else None,
-                                    int(flank_size), int(min_avg_phred), int(wildcard_threshold), status.ctypes.data,
-                                    nfl.ctypes.data, ntr.ctypes.data, nfr.ctypes.data, seqs_ptr, cap, seq_off.ctypes.data)
+        return L.strk_extract_reads(_lib.ptr(bam.data), bam.data.size, *items, seqs_ptr, cap, _lib.ptr(seq_off))
 
     # A first attempt with room for tracts up to four times the reference window (one pass over the records); a read
     # may carry an expansion many times that (the flagship case): the library then says how much is needed, nothing is

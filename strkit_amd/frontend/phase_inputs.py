@@ -227,26 +227,12 @@ class PhaseSetRemap:
 
 
 # ---- the library's functions ----------------------------------------------------------------------------------------------
-def _alt_arrays(n: int, alt):
-    if not alt:
-        return None, None, None
-    a_off = np.zeros(n + 1, np.int64)
-    a_start = np.zeros(n, np.int64)
-    parts = []
-    for i in range(n):
-        if i in alt:
-            parts.append(np.asarray(alt[i][0], np.uint32))
-            a_start[i] = alt[i][1]
-        a_off[i + 1] = a_off[i] + (parts[-1].size if i in alt else 0)
-    return (np.concatenate(parts) if parts else np.zeros(1, np.uint32)), a_off, a_start
-
-
 def phase_cells(bam, rec_idx: np.ndarray, item_locus: np.ndarray, cand_off: np.ndarray, cand_pos: np.ndarray,
                 alt: dict[int, tuple[np.ndarray, int]] | None = None, clip_threshold: int = SIGNIFICANT_CLIP_THRESHOLD,
                 take_in: int = SIGNIFICANT_CLIP_SNV_TAKE_IN, piece_items: int = 0, download: bool = False) -> dict:
     """Tags and cells of items (record index, locus) of a reader of frontend/native.py.  A DeviceBam runs k_dbam_phase_cells and
     keeps the cells in HBM (download=True copies them back too); a host reader runs strk_phase_cells and returns them."""
-    from .native import DeviceBam
+    from .native import DeviceBam, alt_arrays
     L = _lib.load()
     n = int(len(rec_idx))
     rec_off = np.ascontiguousarray(bam.rec_off[np.asarray(rec_idx, np.int64)], np.int64)
@@ -255,7 +241,7 @@ def phase_cells(bam, rec_idx: np.ndarray, item_locus: np.ndarray, cand_off: np.n
     cand_pos = np.ascontiguousarray(cand_pos, np.int64)
     n_loci = int(cand_off.size) - 1
     hp, ps = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
-    a_cig, a_off, a_start = _alt_arrays(n, alt)
+    a_cig, a_off, a_start = alt_arrays(n, alt)
     n_cells = int((cand_off[item_locus + 1] - cand_off[item_locus]).sum()) if n else 0
     out = {"hp": hp, "ps": ps, "n_cells": n_cells, "item_locus": item_locus, "cand_off": cand_off}
     if isinstance(bam, DeviceBam):

@@ -410,9 +410,26 @@ def same_extraction(got: dict, seqs: np.ndarray, want: dict, lo: int = 0, hi: in
         raise AssertionError(("bases", lo + it, int(bad[0] - got["seq_off"][it]), seqs[bad[:8]].tobytes(), w[bad[:8]].tobytes()))
 
 
-def raw_extract(bam, rec_idx, coords, alt, param, alt_start: bool = True, rec_off=None, check: bool = True):
+def malformed_alt(n: int) -> list[tuple[tuple, bytes]]:
+    """The substitute-alignment triples of a call of n >= 3 items that strk_extract_reads and strk_dbam_extract refuse before
+    they read a record, each with the message of the shared check.  (The offsets alone are read: the operations never are.)"""
+    ops = np.full(4, 5 << 4, np.uint32)
+    off = np.zeros(n + 1, np.int64)
+    off[2:] = 2
+    start = np.zeros(n, np.int64)
+    both = b"alt_cigar and alt_cigar_off must both be given or both be NULL"
+    from1, down, huge = off + 1, off.copy(), off.copy()
+    down[2] = 3
+    huge[2:] = (1 << 31) + 1
+    return [((ops, None, start), both), ((None, off, start), both), ((ops, from1, start), b"alt_cigar_off[0] must be 0"),
+            ((ops, down, None), b"item 2: alt_cigar_off is decreasing (or a CIGAR too long)"),
+            ((ops, huge, None), b"item 1: alt_cigar_off is decreasing (or a CIGAR too long)")]
+
+
+def raw_extract(bam, rec_idx, coords, alt, param, alt_start: bool = True, rec_off=None, check: bool = True, alt_raw=None):
     """strk_extract_reads (a host reader) or strk_dbam_extract (a DeviceBam) called directly: (the outputs with `rc`, the bases).
-    alt_start=False passes NULL for the substitute alignments' starts; rec_off replaces the offsets of `rec_idx`."""
+    alt_start=False passes NULL for the substitute alignments' starts; rec_off replaces the offsets of `rec_idx`; alt_raw =
+    (alt_cigar, alt_cigar_off, alt_start) as arrays or None goes to the library as it is, in place of `alt`."""
     from strkit_amd import _lib
     L = _lib.load()
     n = len(rec_idx)
@@ -425,6 +442,8 @@ def raw_extract(bam, rec_idx, coords, alt, param, alt_start: bool = True, rec_of
         a_off = np.concatenate(([0], np.cumsum([alt[i][0].size if i in alt else 0 for i in range(n)]))).astype(np.int64)
         a_cig = np.concatenate([np.asarray(alt[i][0], np.uint32) for i in sorted(alt)] + [np.zeros(1, np.uint32)])
         a_start = np.array([alt[i][1] if i in alt else 0 for i in range(n)], np.int64) if alt_start else None
+    if alt_raw is not None:
+        a_cig, a_off, a_start = alt_raw
     mid = (_lib.ptr(a_cig), _lib.ptr(a_off), _lib.ptr(a_start), *(int(x) for x in param),
            *(_lib.ptr(out[k]) for k in ("status", "nfl", "ntr", "nfr")))
     if hasattr(bam, "_h"):

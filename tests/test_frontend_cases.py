@@ -135,3 +135,37 @@ def test_host_refusals(nb):
         rc = L.strk_bam_names(nb.data.ctypes.data, nb.data.size, 2, _lib.ptr(np.array([nb.rec_off[0], bad], np.int64)), None, 0, _lib.ptr(off))
         assert rc == _lib.STRK_E_INVALID, bad
     assert nb.names(np.array([0])) == [fc.corpus_file()["bam"].segments[0].name]
+
+
+def test_two_malformed_records_name_the_first(nb):
+    """2 100 items drawn with repetition from the corpus's first records, two threads at 1 024 items per thread where there
+    are two cores: items 1 500 and 5 point two bytes into a record, and the call names item 5 whichever thread is done first."""
+    L = _lib.load()
+    c, want = fc.corpus(), fc.corpus_file()["fields"]
+    pick = np.random.default_rng(30).integers(0, 64, 2100)
+    rec, coords = c["item_rec"][pick], c["coords"][pick]
+    off = nb.rec_off[rec].copy()
+    off[[1500, 5]] = want["rec_off"][int(np.nonzero(want["tid"] == 0)[0][40])] + 2
+    for _ in range(3):
+        got, _ = fc.raw_extract(nb, rec, coords, None, DEFAULT, rec_off=off, check=False)
+        assert got["rc"] == _lib.STRK_E_INVALID and L.strk_last_error() == b"item 5: malformed BAM record"
+    off[5] = nb.rec_off[rec[5]]
+    got, _ = fc.raw_extract(nb, rec, coords, None, DEFAULT, rec_off=off, check=False)
+    assert got["rc"] == _lib.STRK_E_INVALID and L.strk_last_error() == b"item 1500: malformed BAM record"
+
+
+def test_host_extraction_checks_the_substitute_alignments(nb):
+    """The four malformed triples are refused with the message of the check that strk_phase_cells and strk_methyl share; a triple
+    without operations, with or without its starts, is the call without substitute alignments."""
+    L = _lib.load()
+    c = fc.corpus()
+    n = 40
+    rec, coords = c["item_rec"][:n], c["coords"][:n]
+    for triple, msg in fc.malformed_alt(n):
+        got, _ = fc.raw_extract(nb, rec, coords, None, DEFAULT, alt_raw=triple, check=False)
+        assert got["rc"] == _lib.STRK_E_INVALID and L.strk_last_error() == msg, (msg, L.strk_last_error())
+    plain, plain_seqs = fc.raw_extract(nb, rec, coords, None, DEFAULT)
+    assert plain_seqs.size > 0
+    for start in (np.full(n, 7, np.int64), None):
+        got, seqs = fc.raw_extract(nb, rec, coords, None, DEFAULT, alt_raw=(np.zeros(1, np.uint32), np.zeros(n + 1, np.int64), start))
+        assert all(np.array_equal(got[k], plain[k]) for k in ("status", "nfl", "ntr", "nfr", "seq_off")) and np.array_equal(seqs, plain_seqs)

@@ -269,3 +269,36 @@ def test_names_refuses_offsets_and_slices_outside_the_stream(readers):
         rc = L.strk_dbam_names(db._h, 3, _lib.ptr(rec_off), _lib.ptr(out_off), _lib.ptr(out))
         assert rc == _lib.STRK_E_INVALID and msg in L.strk_last_error(), (msg, L.strk_last_error())
     assert db.names(np.arange(5)) == [s.name for s in fc.corpus_file()["bam"].segments[:5]]
+
+
+def test_two_malformed_records_name_the_first(readers):
+    """Items 299 and 3 of 300, in different workgroups of k_dbam_extract1, point two bytes into a record (inside the stream: the
+    kernel's parser refuses them): the call names item 3, and the handle gives the corpus's bytes afterwards."""
+    L = _lib.load()
+    nb, db = readers
+    c, want = fc.corpus(), fc.corpus_file()["fields"]
+    rec, coords = c["item_rec"][:300], c["coords"][:300]
+    off = want["rec_off"][rec].copy()
+    off[[299, 3]] = want["rec_off"][int(np.nonzero(want["tid"] == 0)[0][40])] + 2
+    got, _ = fc.raw_extract(db, rec, coords, None, fc.PARAMS[0], rec_off=off, check=False)
+    assert got["rc"] == _lib.STRK_E_INVALID and L.strk_last_error() == b"item 3: malformed BAM record"
+    got, seqs = fc.raw_extract(db, rec, coords, None, fc.PARAMS[0])
+    fc.same_extraction(got, seqs, fc.expected(fc.PARAMS[0], False), 0, 300)
+
+
+def test_extract_checks_the_substitute_alignments_before_any_launch(readers):
+    """The malformed triples get the host entry's refusal, word for word, from the check in front of the launches; a triple
+    without operations, with or without its starts, gives the bytes of the call without substitute alignments."""
+    L = _lib.load()
+    nb, db = readers
+    c = fc.corpus()
+    n = 40
+    rec, coords = c["item_rec"][:n], c["coords"][:n]
+    for triple, msg in fc.malformed_alt(n):
+        for bam in (nb, db):
+            got, _ = fc.raw_extract(bam, rec, coords, None, fc.PARAMS[0], alt_raw=triple, check=False)
+            assert got["rc"] == _lib.STRK_E_INVALID and L.strk_last_error() == msg, (msg, L.strk_last_error())
+    plain, plain_seqs = fc.raw_extract(nb, rec, coords, None, fc.PARAMS[0])
+    for start in (np.full(n, 7, np.int64), None):
+        got, seqs = fc.raw_extract(db, rec, coords, None, fc.PARAMS[0], alt_raw=(np.zeros(1, np.uint32), np.zeros(n + 1, np.int64), start))
+        assert all(np.array_equal(got[k], plain[k]) for k in ("status", "nfl", "ntr", "nfr", "seq_off")) and np.array_equal(seqs, plain_seqs)

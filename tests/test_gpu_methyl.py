@@ -92,3 +92,32 @@ def test_a_hostile_record_and_bad_arguments_fail_before_anything_is_trusted(read
     off[1] = nb.data.size
     rc = L.strk_dbam_methyl(db._h, 3, _lib.ptr(off), _lib.ptr(co), None, None, None, 127, 0, *[_lib.ptr(o) for o in out])
     assert rc == _lib.STRK_E_INVALID and "rec_off" in L.strk_last_error().decode()
+
+
+def _first(bam, n, **kw):
+    """The first n items of the corpus (a partly filled last workgroup of k_dbam_methyl for n = 9)."""
+    c = cases.corpus()
+    return me.methyl(bam, np.arange(n), c["coords"][:n], {k: v for k, v in c["alt"].items() if k < n}, **kw)
+
+
+@pytest.mark.parametrize("piece", [1, 8, 9, 10, 2 ** 31 - 1])
+def test_piece_seams_of_nine_items(readers, piece):
+    a, b = _first(readers[1], 9, piece_items=piece), _first(readers[0], 9)
+    for k in KEYS:
+        assert np.array_equal(a[k], b[k]), (piece, k)
+
+
+@pytest.mark.parametrize("piece", [0, 4])
+def test_two_malformed_records_name_the_first(readers, host, piece):
+    """Items 8 and 1 of 9 point two bytes into a record: different workgroups of four items, and with piece_items = 4 different
+    launches.  The call names item 1, and the handle gives the corpus's bytes afterwards."""
+    nb, db = readers
+    c = cases.corpus()
+    L = _lib.load()
+    off = nb.rec_off[:9].copy()
+    off[[8, 1]] += 2
+    co = np.ascontiguousarray(c["coords"][:9])
+    out = [np.zeros(9, np.int32) for _ in range(4)]
+    rc = L.strk_dbam_methyl(db._h, 9, _lib.ptr(off), _lib.ptr(co), None, None, None, 127, piece, *[_lib.ptr(o) for o in out])
+    assert rc == _lib.STRK_E_INVALID and L.strk_last_error() == b"strk_dbam_methyl: item 1: malformed BAM record or auxiliary fields"
+    _same(me.methyl(db, np.arange(len(c["records"])), c["coords"], c["alt"]), host)

@@ -94,3 +94,32 @@ def test_device_refusals(readers):
     rc = L.strk_dbam_phase_cells(db._h, 3, _lib.ptr(off), _lib.ptr(loc), 1, _lib.ptr(cand_off), _lib.ptr(cand), None, None, None, 100, 250, 0,
                                  _lib.ptr(hp), _lib.ptr(ps))
     assert rc == _lib.STRK_E_INVALID and b"item 1" in L.strk_last_error()
+
+
+def _first(bam, n, **kw):
+    """The first n items of the corpus (a partly filled last workgroup of k_dbam_phase_cells for n = 9)."""
+    c = cases.corpus()
+    alt = {k: v for k, v in c["alt"].items() if k < n}
+    return pi.phase_cells(bam, c["item_file_index"][:n], c["item_locus"][:n], c["cand_off"], c["cand_pos"], alt=alt, **kw)
+
+
+@pytest.mark.parametrize("piece", [1, 8, 9, 10, 2 ** 31 - 1])
+def test_piece_seams_of_nine_items(readers, piece):
+    _same_cells(_first(readers[1], 9, piece_items=piece, download=True), _first(readers[0], 9))
+
+
+@pytest.mark.parametrize("piece", [0, 4])
+def test_two_malformed_records_name_the_first(readers, host, piece):
+    """Items 8 and 1 of 9 point two bytes into a record: different workgroups of four items, and with piece_items = 4 different
+    launches.  The call names item 1, and the handle gives the corpus's bytes afterwards."""
+    L = _lib.load()
+    nb, db = readers
+    c = cases.corpus()
+    off = nb.rec_off[c["item_file_index"][:9]].copy()
+    off[[8, 1]] += 2
+    hp, ps, loc = np.zeros(9, np.int32), np.zeros(9, np.int32), np.zeros(9, np.int32)
+    cand_off, cand = np.array([0, 1], np.int32), np.array([1005], np.int64)
+    rc = L.strk_dbam_phase_cells(db._h, 9, _lib.ptr(off), _lib.ptr(loc), 1, _lib.ptr(cand_off), _lib.ptr(cand), None, None, None, 100, 250, piece,
+                                 _lib.ptr(hp), _lib.ptr(ps))
+    assert rc == _lib.STRK_E_INVALID and L.strk_last_error() == b"strk_dbam_phase_cells: item 1: malformed BAM record or auxiliary fields"
+    _same_cells(_cells(db, download=True), host[0])

@@ -80,3 +80,24 @@ def test_a_rec_off_in_mid_record_is_refused_and_the_handle_lives_on(readers):
         with pytest.raises(_lib.StrkError) as ei:
             select_items(dev, bad, item_off, 7, 250)
         assert ei.value.code == _lib.STRK_E_INVALID and "item 2:" in str(ei.value) and "outside" in str(ei.value)
+
+
+def test_two_malformed_records_name_the_first(readers):
+    """Two items in mid-record in one small locus, then one in a small and one in a large locus (the two kernels): the call
+    names the lower item, and the handle gives the same bytes afterwards."""
+    host, dev = readers
+    c = corpus()
+    loci = ["size_65", "size_%d" % (c.constants["small_items"] + 1), "flags_all"]
+    item_off, rec_off = c.item_arrays(host.rec_off, loci)
+    assert item_off[1] == 65 <= c.constants["small_items"]
+    good = select_items(host, rec_off, item_off, 7, 250)
+    for items in ((40, 3), (65 + 700, 3)):
+        bad = rec_off.copy()
+        bad[list(items)] += 5
+        with pytest.raises(_lib.StrkError) as ei:
+            select_items(dev, bad, item_off, 7, 250)
+        assert ei.value.code == _lib.STRK_E_INVALID and "item 3: malformed" in str(ei.value)
+        with pytest.raises(_lib.StrkError, match="item 3: malformed"):
+            select_items(host, bad, item_off, 7, 250)
+        after = select_items(dev, rec_off, item_off, 7, 250)
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(good, after))

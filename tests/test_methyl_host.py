@@ -152,6 +152,29 @@ def test_argument_checks():
     assert "NULL" in L.strk_last_error().decode()
 
 
+def test_two_malformed_records_name_the_first(bam):
+    """2 100 items drawn with repetition from the corpus's first records, two threads at 1 024 items per thread where there
+    are two cores: items 1 500 and 5 point two bytes into a record, and the call names item 5 (it named the last one)."""
+    L = _lib.load()
+    n = 2100
+    pick = np.random.default_rng(30).integers(0, 64, n)
+    off = bam.rec_off[pick].copy()
+    off[[1500, 5]] += 2
+    co = np.ascontiguousarray(cases.corpus()["coords"][pick], np.int64)
+    out = [np.zeros(n, np.int32) for _ in range(4)]
+
+    def call():
+        rc = L.strk_methyl(_lib.ptr(bam.data), bam.data.size, n, _lib.ptr(off), _lib.ptr(co), None, None, None, 127, *[_lib.ptr(o) for o in out])
+        return rc, L.strk_last_error().decode()
+
+    for _ in range(3):
+        assert call() == (_lib.STRK_E_INVALID, "strk_methyl: item 5: malformed BAM record or auxiliary fields")
+    off[5] -= 2
+    assert call() == (_lib.STRK_E_INVALID, "strk_methyl: item 1500: malformed BAM record or auxiliary fields")
+    off[1500] -= 2
+    assert call()[0] == 0
+
+
 def test_constants_are_exported():
     k = me.methyl_constants()
     assert k["seq_pass_bases"] == 64 * k["chunk_bases"] and k["mm_pass_bytes"] == 64 and k["window"] % 4 == 0 and k["window"] >= 64

@@ -186,6 +186,29 @@ def test_input_checks():
     assert rc == _lib.STRK_E_INVALID and "item 0" in msg
 
 
+def test_two_malformed_records_name_the_first(bam):
+    """2 100 items drawn with repetition from the corpus's first records, two threads at 1 024 items per thread where there
+    are two cores: items 1 500 and 5 point two bytes into a record, and the call names item 5."""
+    L = _lib.load()
+    n = 2100
+    off = bam.rec_off[np.random.default_rng(30).integers(0, 64, n)].copy()
+    off[[1500, 5]] += 2
+    loc, cand_off, cand = np.zeros(n, np.int32), np.array([0, 1], np.int32), np.array([1005], np.int64)
+    hp, ps, base, qual = np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+
+    def call():
+        rc = L.strk_phase_cells(_lib.ptr(bam.data), bam.data.size, n, _lib.ptr(off), _lib.ptr(loc), 1, _lib.ptr(cand_off), _lib.ptr(cand), None, None,
+                                None, 100, 250, _lib.ptr(hp), _lib.ptr(ps), _lib.ptr(base), _lib.ptr(qual), n)
+        return rc, L.strk_last_error().decode()
+
+    for _ in range(3):
+        assert call() == (_lib.STRK_E_INVALID, "strk_phase_cells: item 5: malformed BAM record or auxiliary fields")
+    off[5] -= 2
+    assert call() == (_lib.STRK_E_INVALID, "strk_phase_cells: item 1500: malformed BAM record or auxiliary fields")
+    off[1500] -= 2
+    assert call()[0] == 0
+
+
 # ---- useful SNVs --------------------------------------------------------------------------------------------------------
 def _useful(mats, kept, min_allele_reads=2):
     """mats: per locus the cells' bytes [n items, candidates]; kept: per locus the kept rows.  (library result, the rule's)"""

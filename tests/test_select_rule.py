@@ -152,6 +152,22 @@ def test_the_input_check_refuses(bam):
     assert _call(bam, [0], np.zeros(0, np.int64))[0] == 0            # no locus: valid
 
 
+def test_two_malformed_records_name_the_first(bam):
+    """9 000 items in loci of 90, drawn with repetition from the first records: two threads take them 4 096 at a time where
+    there are two cores.  Items 5 000 and 7, in different chunks, point into the middle of a record (five bytes in, as above):
+    the call names item 7."""
+    n = 9000
+    off = bam.rec_off[np.random.default_rng(30).integers(0, 64, n)].copy()
+    item_off = np.arange(0, n + 1, 90)
+    off[[5000, 7]] += 5
+    for _ in range(3):
+        assert _call(bam, item_off, off) == (_lib.STRK_E_INVALID, "strk_select_reads: item 7: malformed BAM record")
+    off[7] -= 5
+    assert _call(bam, item_off, off) == (_lib.STRK_E_INVALID, "strk_select_reads: item 5000: malformed BAM record")
+    off[5000] -= 5
+    assert _call(bam, item_off, off)[0] == 0
+
+
 def test_declared_bound_and_exported():
     text = open(os.path.join(ROOT, "include", "strkit_amd.h")).read()
     L = _lib.load()

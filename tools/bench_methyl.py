@@ -144,7 +144,8 @@ def main() -> None:
                   "statuses": np.bincount(h["status"], minlength=6).tolist()},
         "device_equals_host": bool(same), "make_file_s": round(t_make, 2), "repeats": a.repeats,
         "k_dbam_methyl_ms": {"median": med(kernel_ms), "min": round(min(kernel_ms), 4), "max": round(max(kernel_ms), 4)},
-        "device_call_wall_ms": med(wall_ms), "host_threads": min(len(cpus), max(1, a.host_threads)),
+        "device_call_wall_ms": med(wall_ms), "every_repeat_ms": {"kernel": [round(x, 4) for x in kernel_ms], "wall": [round(x, 4) for x in wall_ms]},
+        "host_threads": min(len(cpus), max(1, a.host_threads)),
         "host_strk_methyl_ms": med([x * 1e3 for x in host_s]), "call": share,
     }))
     if not same:

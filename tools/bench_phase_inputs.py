@@ -157,6 +157,8 @@ def main() -> None:
         "k_dbam_phase_cells_ms": {"median": med(cells_ms), "min": round(min(cells_ms), 4), "max": round(max(cells_ms), 4)},
         "k_snv_useful_and_gather_ms": {"median": med(useful_ms), "min": round(min(useful_ms), 4), "max": round(max(useful_ms), 4)},
         "device_call_wall_ms": {"cells": med(cells_wall), "useful": med(useful_wall)},
+        "every_repeat_ms": {k: [round(x, 4) for x in v] for k, v in (("cells_kernel", cells_ms), ("useful_kernel", useful_ms),
+                                                                     ("cells_wall", cells_wall), ("useful_wall", useful_wall))},
         "host_threads": min(len(cpus), max(1, a.host_threads)), "phased_call": share,
         "host_phase_cells_ms": med([x * 1e3 for x in host_cells_s]), "host_useful_snvs_ms": med([x * 1e3 for x in host_useful_s]),
     }))

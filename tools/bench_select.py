@@ -129,7 +129,8 @@ def main() -> None:
         t["names_ms"].append(n_ms)
         t["names_plus_python_ms"].append(all_ms)
     db.close()
-    stat = lambda xs: {"median": round(float(np.median(xs)), 4), "min": round(min(xs), 4), "max": round(max(xs), 4)}  # noqa: E731
+    stat = lambda xs: {"median": round(float(np.median(xs)), 4), "min": round(min(xs), 4), "max": round(max(xs), 4),  # noqa: E731
+                       "every_repeat": [round(x, 4) for x in xs]}
     rate = lambda xs: round(n_items / (float(np.median(xs)) / 1e3) / 1e6, 3)  # noqa: E731
     print(json.dumps({
         "shape": {"loci": a.loci, "reads": a.reads, "read_len": a.read_len, "items": n_items, "kept": int(d[2].sum()),

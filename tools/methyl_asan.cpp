@@ -232,12 +232,12 @@ void checkers() {
     { auto in = ok; in.threshold = 256; refuse(in, "threshold"); }
     { auto in = ok; in.rec_off = nullptr; refuse(in, "NULL"); }
     { auto in = ok; in.coords = nullptr; refuse(in, "NULL"); }
-    { auto in = ok; in.alt_cigar = nullptr; refuse(in, "both"); }
-    { auto in = ok; in.alt_cigar_off = nullptr; refuse(in, "both"); }
+    { auto in = ok; in.alt.ops = nullptr; refuse(in, "both"); }
+    { auto in = ok; in.alt.off = nullptr; refuse(in, "both"); }
     { auto in = ok; const int64_t o[2] = {-1, 40}; in.rec_off = o; refuse(in, "rec_off"); }
     { auto in = ok; const int64_t o[2] = {0, 97}; in.rec_off = o; refuse(in, "rec_off"); }
-    { auto in = ok; const int64_t a[3] = {1, 1, 2}; in.alt_cigar_off = a; refuse(in, "alt_cigar_off[0]"); }
-    { auto in = ok; const int64_t a[3] = {0, 2, 1}; in.alt_cigar_off = a; refuse(in, "decreasing"); }
+    { auto in = ok; const int64_t a[3] = {1, 1, 2}; in.alt.off = a; refuse(in, "alt_cigar_off[0]"); }
+    { auto in = ok; const int64_t a[3] = {0, 2, 1}; in.alt.off = a; refuse(in, "decreasing"); }
     { auto in = ok; in.n_items = 0; in.rec_off = nullptr; expect(strk_me::check_input(in, &msg) == 0, "no items"); }
     { auto in = ok; in.threshold = 0; expect(strk_me::check_input(in, &msg) == 0, "threshold 0"); }
     { auto in = ok; in.threshold = 255; expect(strk_me::check_input(in, &msg) == 0, "threshold 255"); }

@@ -274,9 +274,9 @@ void checkers(std::mt19937& rng) {
     { auto in = ok; std::vector<int64_t> ro = {-1, 40}; in.rec_off = ro.data(); refuse_cells(in, "rec_off"); }
     { auto in = ok; std::vector<int32_t> lc = {0, 2}; in.item_locus = lc.data(); refuse_cells(in, "item_locus"); }
     { auto in = ok; std::vector<int32_t> lc = {-1, 0}; in.item_locus = lc.data(); refuse_cells(in, "item_locus"); }
-    { auto in = ok; in.alt_cigar = nullptr; refuse_cells(in, "both"); }
-    { auto in = ok; std::vector<int64_t> ao = {1, 1, 1}; in.alt_cigar_off = ao.data(); refuse_cells(in, "alt_cigar_off[0]"); }
-    { auto in = ok; std::vector<int64_t> ao = {0, 1, 0}; in.alt_cigar_off = ao.data(); refuse_cells(in, "decreasing"); }
+    { auto in = ok; in.alt.ops = nullptr; refuse_cells(in, "both"); }
+    { auto in = ok; std::vector<int64_t> ao = {1, 1, 1}; in.alt.off = ao.data(); refuse_cells(in, "alt_cigar_off[0]"); }
+    { auto in = ok; std::vector<int64_t> ao = {0, 1, 0}; in.alt.off = ao.data(); refuse_cells(in, "decreasing"); }
 
     auto refuse_useful = [&](const strk_pi::UsefulInput& in, const char* needle) {
         strk_groups::Message mm;
