@@ -1,6 +1,7 @@
 // strk_api.hip — host side of libstrkit_amd.so (C ABI declared in include/strkit_amd.h).
 // The batched counting path is here.  It stands on two host-only headers:
-//   strk_host.h     the calling thread's error message (fail, HIP_TRY) and the owning types: DevBuf, PinnedBuf, Stream, Event
+//   strk_host.h     the calling thread's error message (fail, HIP_TRY), the owning types (DevBuf, PinnedBuf, Stream, Event) and
+//                   Staging: what a call sends up and takes back (its layout and copy plan: strk_stage_plan.h, no HIP in it)
 //   strk_policy.h   the adaptive policies as plain state machines: default window, band gate, grid history (no HIP in it)
 //   strk_groups.h   groups of byte strings as three calls take them: the view, its one check, the piece cutter (no HIP in it)
 //   strk_threads.h  the CPUs of the process, the two thread fans, the first malformed item, the piece loop (no HIP in it)
@@ -111,30 +112,6 @@ struct HostCounters {
     }
 };
 
-// The device copy of a view of groups (strk_groups.h), one per family of calls that takes one.
-struct GroupStage {
-    DevBuf off, start, len, seqs;
-    const uint8_t* bases = nullptr;   // the bases of the view uploaded last: the caller's d_seqs, or `seqs`
-    // Sizes the buffers and enqueues the copies of a checked view on `st`.  The bases are not copied when they are on the
-    // device already (d_seqs) or when no sequence has a byte.
-    int upload(const strk_groups::View& v, const strk_groups::Totals& t, const uint8_t* h_seqs, const uint8_t* d_seqs, hipStream_t st) {
-        const size_t ng = (size_t)v.n_groups, ns = (size_t)t.n_seqs;
-        int rc;
-        if ((rc = off.ensure((ng + 1) * 4))) return rc;
-        if ((rc = start.ensure(std::max<size_t>(ns, 1) * 8))) return rc;
-        if ((rc = len.ensure(std::max<size_t>(ns, 1) * 4))) return rc;
-        if (!d_seqs && (rc = seqs.ensure(std::max<size_t>((size_t)v.n_seq_bytes, 256)))) return rc;
-        bases = d_seqs ? d_seqs : seqs.as<uint8_t>();
-        if (!d_seqs && t.total_len > 0) HIP_TRY(hipMemcpyAsync(seqs.p, h_seqs, (size_t)v.n_seq_bytes, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(off.p, v.group_off, (ng + 1) * 4, hipMemcpyHostToDevice, st));
-        if (ns > 0) {
-            HIP_TRY(hipMemcpyAsync(start.p, v.seq_start, ns * 8, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(len.p, v.seq_len, ns * 4, hipMemcpyHostToDevice, st));
-        }
-        return 0;
-    }
-};
-
 }  // namespace
 
 struct strk_ctx {
@@ -155,22 +132,27 @@ struct strk_ctx {
     // in flight, and a context serves one host thread at a time.  It is non-blocking, so nothing on it is ordered against the
     // NULL stream: whatever such a call copies, sets or launches goes on this stream and is waited for on it.
     Stream side;
-    // allele calling (strk_call_alleles): what goes up, the workspaces, what comes down
-    DevBuf al_in, al_ws, al_out;
-    // phased allele calls (strk_call_alleles_phased): what goes up, what the kernels hand each other, the workspaces, what comes down
+    // The calls below hand their arrays to the device through a Staging (strk_host.h) on `side`: one staged buffer per call, one
+    // per piece where a call has pieces (what goes up and what comes down share it), beside the workspaces that only kernels
+    // touch.  `image` is the page-locked image of whichever of them is running; a piece's wait (timed_launch) gives it back.
+    PinnedBuf image;
+    // allele calling (strk_call_alleles, _n) and trio inheritance
+    DevBuf al_stage, al_ws;
+    DevBuf mi_stage, mi_ws;
+    // phased allele calls (strk_call_alleles_phased) keep carved buffers and a copy per array, as measured in
+    // profiles/r31_context_staging.txt: what goes up, what the kernels hand each other, the workspaces, what comes down
     DevBuf ph_in, ph_mid, ph_ws, ph_out;
-    // best representatives (strk_best_representatives)
-    GroupStage cs_in;
-    DevBuf cs_bound, cs_out;
-    // distinct windows (strk_count_kmers)
-    GroupStage km_in;
-    DevBuf km_k, km_cnt, km_eoff, km_list, km_slist, km_wsoff, km_ws, km_out;
-    // allele sequences by partial-order alignment (strk_consensus); its own stage, because the call runs the best-representative
-    // pass on some of its groups while its own arrays are still in use
-    GroupStage po_in;
-    DevBuf po_res, po_pool, po_poolof, po_list, po_ws, po_out, po_outoff;
-    // trio inheritance (strk_mi_trio): what goes up, the workspaces, what comes down
-    DevBuf mi_in, mi_ws, mi_out;
+    // best representatives (strk_best_representatives): the view and the results; the parked rows of long patterns
+    DevBuf cs_stage, cs_bound;
+    // distinct windows (strk_count_kmers): what the call holds, what a piece of k_kmers_sort holds, its runs, the entries
+    DevBuf km_call, km_piece, km_ws, km_out;
+    // allele sequences by partial-order alignment (strk_consensus): what the call holds, what a piece of k_poa holds (then the
+    // gather's offsets and choices), the graphs, the pooled consensus bytes, the gathered bytes.  The call runs the
+    // best-representative pass on some of its groups in mid-call, while the results of its own kernels lie in an image and wait
+    // to be merged with that pass's: so what the call holds, results included, has an image of its own, and its pieces, the nested
+    // pass and the gather take `image` in turn.
+    PinnedBuf po_image;
+    DevBuf po_call, po_piece, po_ws, po_pool, po_out;
     HostCounters h_counters;        // pinned: counters + cells + scratch_used
     // a chain of events along one call: start | after k_hash + k_plan | after k_dp_band | after k_dp_band_wide | after the
     // first k_replay pass | after k_dp_all / k_dp_ref | after k_dp_long | after k_dp_generic | end (after k_replay and the

@@ -13,6 +13,7 @@
 
 #include "../../include/strkit_amd.h"
 #include "strk_bamrec.h"
+#include "strk_stage_plan.h"
 
 namespace {
 
@@ -86,15 +87,7 @@ struct DevBuf : OwnedMem<hipFree> {
     }
 };
 
-// Sub-buffers of one device buffer, each 256-aligned: take() every part, ensure(bytes) the DevBuf, add the offsets to its p.
-struct Carve {
-    size_t bytes = 0;
-    size_t take(size_t n) {
-        const size_t at = bytes;
-        bytes += (n + 255) & ~(size_t)255;
-        return at;
-    }
-};
+using strk_stage::Carve;   // (strk_stage_plan.h)
 
 // Page-locked host memory.
 struct PinnedBuf : OwnedMem<hipHostFree> {
@@ -116,54 +109,74 @@ struct PinnedBuf : OwnedMem<hipHostFree> {
 };
 
 // What one call sends to a device buffer and takes back from it, as one image in page-locked memory of its owner: every part
-// has its 256-aligned offset in the image and in the buffer alike.  put() and zero() name what goes up (the bytes are read by
-// upload(): they must still be there), room() reserves what only the kernels write.  upload() gathers the parts into the image
-// and sends every stretch of neighbouring parts with one hipMemcpy; a part of kDirectBytes or more goes up from where it lies
-// instead (the runtime locks its pages and copies at the same rate; gathering 12 MB first cost a call of 300 000 items more
-// than half a millisecond, profiles/r30_item_stages.txt).  download() brings one range of the buffer back into the image in
-// one copy, and at() reads a part of it there.
-struct Staging {
-    static constexpr size_t kDirectBytes = (size_t)256 << 10;
+// has its 256-aligned offset in the image and in the buffer alike (the layout and the plan of copies: strk_stage_plan.h).
+// put() and zero() name what goes up (the bytes are read by upload(): they must still be there), room() reserves what only the
+// kernels write, get() what comes back.  upload() gathers the parts into the image and sends every stretch of neighbouring
+// parts with one copy; a part of kDirectBytes or more goes up from where it lies instead (the runtime locks its pages and
+// copies at the same rate; gathering 12 MB first cost a call of 300 000 items more than half a millisecond,
+// profiles/r30_item_stages.txt), and zeros of that size are set on the device.  download() brings the get() parts back the
+// same way (small neighbours in one copy into the image, large ones straight to where they go) or one range of the buffer
+// into the image; scatter() hands the small results to their arrays, and at() reads a part in the image.
+// Without a stream the copies are synchronous (the item stages of an alignment file).  With one they are enqueued on it (the
+// context calls, strk_ctx::side), and the image belongs to the stream until the caller has waited on it: after an upload
+// nothing gathers into the same image before that wait, and after a download the image is read, and scatter() called, only
+// after it.
+struct Staging : strk_stage::Layout {
+    static constexpr size_t kDirectBytes = strk_stage::kDirectBytes;
     explicit Staging(PinnedBuf& image) : image_(image) {}
-    Carve cv;
-    size_t room(size_t bytes) { return cv.take(bytes); }
-    size_t zero(size_t bytes) { return put(nullptr, bytes); }
-    size_t put(const void* src, size_t bytes) {
-        const size_t at = cv.take(bytes);
-        parts_.push_back(Part{at, src, bytes});
-        return at;
-    }
-    int upload(DevBuf& b) {
-        int rc;
-        if ((rc = b.ensure(cv.bytes)) || (rc = image_.ensure(cv.bytes))) return rc;
-        size_t from = 0, to = 0;   // the stretch of the image that has been gathered and not sent
-        for (const Part& p : parts_) {
-            const bool direct = p.src && p.bytes >= kDirectBytes;
-            if (direct || to == from) {
-                if (to > from) HIP_TRY(hipMemcpy(b.at<char>(from), image_.at<char>(from), to - from, hipMemcpyHostToDevice));
-                from = to = p.at;
-            }
-            if (direct) {
-                HIP_TRY(hipMemcpy(b.at<char>(p.at), p.src, p.bytes, hipMemcpyHostToDevice));
-                continue;
-            }
-            if (p.src) memcpy(image_.at<char>(p.at), p.src, p.bytes);
-            else memset(image_.at<char>(p.at), 0, p.bytes);
-            to = p.at + p.bytes;
-        }
-        if (to > from) HIP_TRY(hipMemcpy(b.at<char>(from), image_.at<char>(from), to - from, hipMemcpyHostToDevice));
-        return 0;
-    }
+    int upload(DevBuf& b) { return upload_by(b, Sync{}); }
+    int upload(DevBuf& b, hipStream_t st) { return upload_by(b, OnStream{st}); }
     int download(const DevBuf& b, size_t from, size_t to) {   // (after upload(): the image has room for every part)
-        if (to > from) HIP_TRY(hipMemcpy(image_.at<char>(from), b.at<char>(from), to - from, hipMemcpyDeviceToHost));
+        if (to > from) HIP_TRY(Sync{}.copy(image_.at<char>(from), b.at<char>(from), to - from, hipMemcpyDeviceToHost));
         return 0;
+    }
+    int download(const DevBuf& b, size_t from, size_t to, hipStream_t st) {
+        if (to > from) HIP_TRY(OnStream{st}.copy(image_.at<char>(from), b.at<char>(from), to - from, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    int download(const DevBuf& b, hipStream_t st) {   // every get() part
+        std::vector<strk_stage::Part> parts = down_;
+        for (strk_stage::Part& p : parts)
+            if (!p.mem) p.mem = image_.at<char>(p.at);
+        for (const strk_stage::Copy& k : strk_stage::plan(parts)) {
+            void* dst = k.kind == strk_stage::Copy::kImage ? image_.at<char>(k.at) : const_cast<void*>(k.mem);
+            HIP_TRY(OnStream{st}.copy(dst, b.at<char>(k.at), k.bytes, hipMemcpyDeviceToHost));
+        }
+        return 0;
+    }
+    void scatter() const {
+        for (const strk_stage::Part& p : down_)
+            if (p.mem && p.bytes < kDirectBytes) memcpy(const_cast<void*>(p.mem), image_.at<char>(p.at), p.bytes);
     }
     template <class T> const T* at(size_t byte_off) const { return image_.at<T>(byte_off); }
+    template <class T> T* mut(size_t byte_off) { return image_.at<T>(byte_off); }   // (a result that the caller completes in place)
 
   private:
-    struct Part { size_t at; const void* src; size_t bytes; };
+    struct Sync {
+        hipError_t copy(void* d, const void* s, size_t n, hipMemcpyKind k) const { return hipMemcpy(d, s, n, k); }
+        hipError_t clear(void* d, size_t n) const { return hipMemset(d, 0, n); }
+    };
+    struct OnStream {
+        hipStream_t st;
+        hipError_t copy(void* d, const void* s, size_t n, hipMemcpyKind k) const { return hipMemcpyAsync(d, s, n, k, st); }
+        hipError_t clear(void* d, size_t n) const { return hipMemsetAsync(d, 0, n, st); }
+    };
+    template <class How>
+    int upload_by(DevBuf& b, const How& how) {
+        int rc;
+        if ((rc = b.ensure(cv.bytes)) || (rc = image_.ensure(cv.bytes))) return rc;
+        for (const strk_stage::Part& p : up_) {
+            if (p.bytes >= kDirectBytes) continue;
+            if (p.mem) memcpy(image_.at<char>(p.at), p.mem, p.bytes);
+            else memset(image_.at<char>(p.at), 0, p.bytes);
+        }
+        for (const strk_stage::Copy& k : strk_stage::plan(up_)) {
+            if (k.kind == strk_stage::Copy::kClear) HIP_TRY(how.clear(b.at<char>(k.at), k.bytes));
+            else HIP_TRY(how.copy(b.at<char>(k.at), k.kind == strk_stage::Copy::kDirect ? k.mem : image_.at<char>(k.at), k.bytes, hipMemcpyHostToDevice));
+        }
+        return 0;
+    }
     PinnedBuf& image_;
-    std::vector<Part> parts_;
 };
 
 // The substitute alignments of a call of n items (strk_bamrec.h, checked by check_alt) into its staging: ops | offsets | starts
@@ -183,6 +196,27 @@ inline StagedAlt stage_alt(Staging& st, size_t n, const strk_fe::AltCigars& alt)
     s.ops = st.put(alt.ops, (size_t)alt.off[n] * 4);
     s.off = st.put(alt.off, (n + 1) * 8);
     s.start = alt.start ? st.put(alt.start, n * 8) : st.zero(n * 8);
+    return s;
+}
+
+// A checked view of groups (strk_groups.h) into a call's staging: offsets | starts | lengths | bases.  With d_seqs the bases are
+// on the device already: none are staged, and on() gives the caller's pointer.  Nor are they when no sequence has a byte.
+struct StagedGroups {
+    size_t off = 0, start = 0, len = 0, seqs = 0;
+    const uint8_t* d_seqs = nullptr;
+    struct Ptrs { const int32_t* off; const int64_t* start; const int32_t* len; const uint8_t* seqs; };
+    Ptrs on(const DevBuf& b) const {
+        return Ptrs{b.at<int32_t>(off), b.at<int64_t>(start), b.at<int32_t>(len), d_seqs ? d_seqs : b.at<uint8_t>(seqs)};
+    }
+};
+inline StagedGroups stage_groups(Staging& st, const strk_groups::View& v, const strk_groups::Totals& t, const uint8_t* h_seqs, const uint8_t* d_seqs) {
+    StagedGroups s;
+    const size_t ns = (size_t)t.n_seqs;
+    s.d_seqs = d_seqs;
+    s.off = st.put(v.group_off, ((size_t)v.n_groups + 1) * 4);
+    s.start = st.put(v.seq_start, ns * 8);
+    s.len = st.put(v.seq_len, ns * 4);
+    if (!d_seqs) s.seqs = t.total_len > 0 ? st.put(h_seqs, (size_t)v.n_seq_bytes) : st.room(1);
     return s;
 }
 

@@ -2,7 +2,7 @@
 // §9, §15): input checks (strk_alleles_check.h), pieces, launches, for rows of W = 2 or kMaxAlleles allele slots; and what
 // strk_call_alleles_phased (strk_host_phase.inc) shares with it: the piece constants, AlleleOut and its scatter, the rule's
 // part of an AlleleArgs, the piece-relative offsets.
-// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf and Carve of strk_host.h, and
+// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf and Staging of strk_host.h, and
 // strk_ctx, side_stream and timed_launch defined there); not a stand-alone header.
 // ---------------------------------------------------------------------------------------------
 // Allele calling: strk_call_alleles, strk_call_alleles_n
@@ -89,8 +89,7 @@ int call_alleles_impl(strk_ctx* c, const char* fn, const strk_alleles_check::Inp
     using R = AlleleRow<W>;
     const int B = p->num_bootstrap;
     std::vector<int64_t> ws_off;
-    std::vector<int32_t> off_rel, oi;
-    std::vector<double> od;
+    std::vector<int32_t> off_rel;
     auto locus_ws = [&](size_t l) {
         const int n = read_off[l + 1] - read_off[l];
         return (int64_t)(n >= p->min_reads ? allele_ws_bytes(n, B, W == 2 ? 2 : in.n_alleles[l]) : 0);
@@ -102,47 +101,34 @@ int call_alleles_impl(strk_ctx* c, const char* fn, const strk_alleles_check::Inp
                                              ws_off, &wsum);
         const int32_t nl = l1 - l0, r0 = read_off[l0], nr = read_off[l1] - r0;
         piece_offsets(read_off, l0, nl, off_rel);
-        const size_t snl = (size_t)nl, snr = std::max<size_t>(nr, 1);
-        Carve ci, co;
-        const size_t i_off = ci.take((snl + 1) * 4), i_cn = ci.take(snr * 4), i_w = ci.take(snr * 8), i_nal = ci.take(snl * 4),
-                     i_seed = ci.take(snl * 8), i_wsoff = ci.take(snl * 8);
-        const size_t o_i = co.take(snl * R::kOutI * 4), o_d = co.take(snl * R::kOutD * 8), o_rp = co.take(snr * 4);
+        const size_t snl = (size_t)nl, snr = (size_t)nr;
+        Staging sg(c->image);
+        const size_t i_off = sg.put(off_rel.data(), (snl + 1) * 4), i_cn = sg.put(in.cn + r0, snr * 4), i_w = sg.put(in.w + r0, snr * 8),
+                     i_nal = sg.put(in.n_alleles + l0, snl * 4), i_seed = sg.put(in.seed + l0, snl * 8), i_wsoff = sg.put(ws_off.data(), snl * 8);
+        const size_t o_i = sg.get(nullptr, snl * R::kOutI * 4), o_d = sg.get(nullptr, snl * R::kOutD * 8), o_rp = sg.get(out.read_peak + r0, snr * 4);
         int rc;
-        if ((rc = c->al_in.ensure(ci.bytes))) return rc;
         if ((rc = c->al_ws.ensure(std::max<size_t>((size_t)wsum, 256)))) return rc;
-        if ((rc = c->al_out.ensure(co.bytes))) return rc;
+        if ((rc = sg.upload(c->al_stage, st))) return rc;
+        const DevBuf& d = c->al_stage;
         AlleleArgs a = allele_rule_args(p);
-        a.read_off = c->al_in.at<int32_t>(i_off);
-        a.cn = c->al_in.at<int32_t>(i_cn);
-        a.w = c->al_in.at<double>(i_w);
-        a.n_alleles = c->al_in.at<int32_t>(i_nal);
-        a.seed = c->al_in.at<uint64_t>(i_seed);
-        a.ws_off = c->al_in.at<int64_t>(i_wsoff);
+        a.read_off = d.at<int32_t>(i_off);
+        a.cn = d.at<int32_t>(i_cn);
+        a.w = d.at<double>(i_w);
+        a.n_alleles = d.at<int32_t>(i_nal);
+        a.seed = d.at<uint64_t>(i_seed);
+        a.ws_off = d.at<int64_t>(i_wsoff);
         a.ws = c->al_ws.as<char>();
-        a.out_i = c->al_out.at<int32_t>(o_i);
-        a.out_d = c->al_out.at<double>(o_d);
-        a.read_peak = c->al_out.at<int32_t>(o_rp);
+        a.out_i = d.at<int32_t>(o_i);
+        a.out_d = d.at<double>(o_d);
+        a.read_peak = d.at<int32_t>(o_rp);
         a.n_loci = nl;
         a.min_reads = p->min_reads;
         a.min_allele_reads = p->min_allele_reads;
-        char* di = c->al_in.as<char>();
-        HIP_TRY(hipMemcpyAsync(di + i_off, off_rel.data(), (snl + 1) * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(di + i_cn, in.cn + r0, (size_t)nr * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(di + i_w, in.w + r0, (size_t)nr * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(di + i_nal, in.n_alleles + l0, snl * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(di + i_seed, in.seed + l0, snl * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(di + i_wsoff, ws_off.data(), snl * 8, hipMemcpyHostToDevice, st));
-        oi.resize(snl * R::kOutI);
-        od.resize(snl * R::kOutD);
         if ((rc = timed_launch(c, st, stats, fn, "allele kernel", 1, [&] {
                 hipLaunchKernelGGL(k_alleles_w<W>, dim3(nl), dim3(allele_threads(B)), 0, st, a);
-            }, [&] {
-                HIP_TRY(hipMemcpyAsync(oi.data(), a.out_i, oi.size() * 4, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(od.data(), a.out_d, od.size() * 8, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipMemcpyAsync(out.read_peak + r0, a.read_peak, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
-                return 0;
-            }))) return rc;
-        scatter_alleles<W>(out, l0, nl, oi.data(), R::kOutI, od.data());
+            }, [&] { return sg.download(d, st); }))) return rc;
+        sg.scatter();
+        scatter_alleles<W>(out, l0, nl, sg.at<int32_t>(o_i), R::kOutI, sg.at<double>(o_d));
     }
     return 0;
 }

@@ -1,5 +1,5 @@
 // Host side of strk_best_representatives / strk_best_representatives_dseqs: input checks, pieces, launches.
-// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, strk_ctx, check_groups,
+// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, Staging, strk_ctx, check_groups,
 // side_stream and timed_launch defined there); not a stand-alone header.
 // ---------------------------------------------------------------------------------------------
 // Best representative of every group: strk_best_representatives
@@ -24,37 +24,39 @@ int best_rep_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int32_t* 
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st;
     if ((rc = side_stream(c, &st))) return rc;
-    if ((rc = c->cs_out.ensure((size_t)n_groups * 16))) return rc;
-    if ((rc = c->cs_in.upload(view, tot, seqs, d_seqs, st))) return rc;
+    // the view and the results in one staged buffer, sized here once: the pieces below keep its pointers
+    Staging sg(c->image);
+    const StagedGroups s_in = stage_groups(sg, view, tot, seqs, d_seqs);
+    const size_t o_dist = sg.get(out_dist_sum, (size_t)n_groups * 8), o_index = sg.get(out_index, (size_t)n_groups * 4),
+                 o_method = sg.get(out_method, (size_t)n_groups * 4);
+    if ((rc = sg.upload(c->cs_stage, st))) return rc;
+    const DevBuf& d = c->cs_stage;
+    const StagedGroups::Ptrs in = s_in.on(d);
     // a pattern (the shorter string of a pair) beyond one pass parks a row of deltas per wave; the row is as long as the text
     const size_t bound_stride = max_len > kConsPassRows ? ((size_t)max_len + 63) & ~(size_t)63 : 0;
     const int32_t piece = bound_stride ? (int32_t)std::max<size_t>(1, std::min<size_t>(kConsPieceGroups, kConsBoundBudget / (bound_stride * kConsWaves)))
                                        : kConsPieceGroups;
     if (bound_stride && (rc = c->cs_bound.ensure((size_t)std::min(piece, n_groups) * kConsWaves * bound_stride))) return rc;
-    int64_t* d_dist = c->cs_out.as<int64_t>();
-    int32_t* d_index = reinterpret_cast<int32_t*>(d_dist + n_groups);
-    int32_t* d_method = d_index + n_groups;
     for (int32_t g0 = 0; g0 < n_groups; g0 += piece) {
         const int32_t ng = std::min(piece, n_groups - g0);
         ConsArgs a{};
-        a.group_off = c->cs_in.off.as<int32_t>() + g0;
-        a.seqs = c->cs_in.bases;
-        a.seq_start = c->cs_in.start.as<int64_t>();
-        a.seq_len = c->cs_in.len.as<int32_t>();
+        a.group_off = in.off + g0;
+        a.seqs = in.seqs;
+        a.seq_start = in.start;
+        a.seq_len = in.len;
         a.bound = bound_stride ? c->cs_bound.as<uint8_t>() : nullptr;
         a.bound_stride = (int64_t)bound_stride;
-        a.out_index = d_index + g0;
-        a.out_method = d_method + g0;
-        a.out_dist = d_dist + g0;
+        a.out_index = d.at<int32_t>(o_index) + g0;
+        a.out_method = d.at<int32_t>(o_method) + g0;
+        a.out_dist = d.at<int64_t>(o_dist) + g0;
         a.n_groups = ng;
         if ((rc = timed_launch(c, st, stats, fn, "best-representative kernel", 1, [&] {
                 hipLaunchKernelGGL(k_best_rep, dim3(ng), dim3(kConsThreads), 0, st, a);
             }))) return rc;
     }
-    HIP_TRY(hipMemcpyAsync(out_dist_sum, d_dist, (size_t)n_groups * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out_index, d_index, (size_t)n_groups * 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(out_method, d_method, (size_t)n_groups * 4, hipMemcpyDeviceToHost, st));
+    if ((rc = sg.download(d, st))) return rc;
     const hipError_t q = hipStreamSynchronize(st);
     if (q != hipSuccess) return fail(STRK_E_DEVICE, "%s: best-representative results: %s", fn, hipGetErrorString(q));
+    sg.scatter();
     return 0;
 }

@@ -1,5 +1,5 @@
 // Host side of strk_count_kmers / strk_count_kmers_dseqs / strk_count_kmers_ws: input checks, launch lists, pieces, prefix sums.
-// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, strk_ctx, check_groups,
+// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, Staging, strk_ctx, check_groups,
 // side_stream and timed_launch defined there); not a stand-alone header.
 // ---------------------------------------------------------------------------------------------
 // Distinct windows of every group: strk_count_kmers
@@ -51,45 +51,46 @@ int64_t count_kmers_impl(strk_ctx* c, const char* fn, int32_t n_groups, const in
     hipStream_t st;
     if ((rc = side_stream(c, &st))) return rc;
     const size_t ng = (size_t)n_groups;
-    if ((rc = c->km_k.ensure(ng * 4))) return rc;
-    if ((rc = c->km_cnt.ensure(ng * 8))) return rc;               // cnt | state
-    if ((rc = c->km_eoff.ensure((ng + 1) * 8))) return rc;
-    if ((rc = c->km_list.ensure(lists.size() * 4))) return rc;
-    if ((rc = c->km_in.upload(view, tot, seqs, d_seqs, st))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->km_k.p, k, ng * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(c->km_list.p, lists.data(), lists.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(c->km_cnt.p, 0, ng * 8, st));
+    // what the whole call holds, in one staged buffer sized here once; cnt | state start as zeros, and the entry offsets go up
+    // before each write pass (below)
+    Staging sg(c->image);
+    const StagedGroups s_in = stage_groups(sg, view, tot, seqs, d_seqs);
+    const size_t i_k = sg.put(k, ng * 4), i_small = sg.put(lists.data(), (size_t)n_small * 4),
+                 i_large = sg.put(lists.data() + n_small, (size_t)n_large * 4), i_cnt = sg.zero(ng * 4), i_state = sg.zero(ng * 4),
+                 i_eoff = sg.room((ng + 1) * 8);
+    if ((rc = sg.upload(c->km_call, st))) return rc;
+    const DevBuf& d = c->km_call;
+    const StagedGroups::Ptrs in = s_in.on(d);
 
     KmerArgs a{};
-    a.group_off = c->km_in.off.as<int32_t>();
-    a.seqs = c->km_in.bases;
-    a.seq_start = c->km_in.start.as<int64_t>();
-    a.seq_len = c->km_in.len.as<int32_t>();
-    a.k = c->km_k.as<int32_t>();
-    a.cnt = c->km_cnt.as<int32_t>();
-    a.state = a.cnt + n_groups;
-    a.entry_off = c->km_eoff.as<int64_t>();
-    const int32_t* d_list = c->km_list.as<int32_t>();
+    a.group_off = in.off;
+    a.seqs = in.seqs;
+    a.seq_start = in.start;
+    a.seq_len = in.len;
+    a.k = d.at<int32_t>(i_k);
+    a.cnt = d.at<int32_t>(i_cnt);
+    a.state = d.at<int32_t>(i_state);
+    a.entry_off = d.at<int64_t>(i_eoff);
     auto table_pass = [&](int mode) {
         KmerArgs t = a;
         t.mode = mode;
         if (n_small) {
-            t.list = d_list;
+            t.list = d.at<int32_t>(i_small);
             t.n_list = n_small;
             hipLaunchKernelGGL(k_kmers_hash<kKmerSmallSlots>, dim3(n_small), dim3(kKmerHashThreads), 0, st, t);
         }
         if (n_large) {
-            t.list = d_list + n_small;
+            t.list = d.at<int32_t>(i_large);
             t.n_list = n_large;
             hipLaunchKernelGGL(k_kmers_hash<kKmerLargeSlots>, dim3(n_large), dim3(kKmerHashThreads), 0, st, t);
         }
     };
     // pass 1: the entries of every group the table takes
     if ((rc = timed_launch(c, st, stats, fn, "table kernel (count)", (n_small > 0) + (n_large > 0), [&] { table_pass(kKmerCount); }))) return rc;
-    std::vector<int32_t> cnt(ng * 2);
-    HIP_TRY(hipMemcpyAsync(cnt.data(), c->km_cnt.p, ng * 8, hipMemcpyDeviceToHost, st));
+    std::vector<int32_t> cnt(ng), state(ng);
+    HIP_TRY(hipMemcpyAsync(cnt.data(), a.cnt, ng * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(state.data(), a.state, ng * 4, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    const int32_t* state = cnt.data() + n_groups;
     std::vector<int32_t> sorted;   // the groups left to k_kmers_sort, ascending
     for (int32_t i = n_small; i < n_small + n_large; ++i) {
         const int32_t g = lists[(size_t)i];
@@ -107,7 +108,7 @@ int64_t count_kmers_impl(strk_ctx* c, const char* fn, int32_t n_groups, const in
     const int64_t n_out = std::min(cap, total_windows);
     if (n_out > 0 && (rc = c->km_out.ensure((size_t)n_out * 12))) return rc;
     a.out_pos = c->km_out.as<int64_t>();
-    a.out_count = reinterpret_cast<int32_t*>(a.out_pos + n_out);
+    a.out_count = c->km_out.at<int32_t>((size_t)n_out * 8);
     // pieces of the sorted groups: sort + count, and, while the entries still fit, write (the workspace holds the runs)
     int32_t done = 0;   // out_entry_off[0..done] is final
     auto prefix_to = [&](int32_t g_end) {
@@ -124,25 +125,24 @@ int64_t count_kmers_impl(strk_ctx* c, const char* fn, int32_t n_groups, const in
         p1 = strk_groups::cut_piece(p0, sorted.size(), sort_elems, ws_elems, strk_groups::kNoItemCap, ws_off, &used);
         const int32_t n_piece = (int32_t)(p1 - p0);
         if ((rc = c->km_ws.ensure((size_t)used * sizeof(KmerElem)))) return rc;
-        if ((rc = c->km_wsoff.ensure((size_t)n_piece * 8))) return rc;
-        if ((rc = c->km_slist.ensure((size_t)n_piece * 4))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->km_wsoff.p, ws_off.data(), (size_t)n_piece * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(c->km_slist.p, sorted.data() + p0, (size_t)n_piece * 4, hipMemcpyHostToDevice, st));
+        Staging ps(c->image);   // (the stream has been waited on since the call's own upload)
+        const size_t i_slist = ps.put(sorted.data() + p0, (size_t)n_piece * 4), i_wsoff = ps.put(ws_off.data(), (size_t)n_piece * 8);
+        if ((rc = ps.upload(c->km_piece, st))) return rc;
         KmerArgs s = a;
-        s.list = c->km_slist.as<int32_t>();
+        s.list = c->km_piece.at<int32_t>(i_slist);
         s.n_list = n_piece;
         s.ws = c->km_ws.as<KmerElem>();
-        s.ws_off = c->km_wsoff.as<int64_t>();
+        s.ws_off = c->km_piece.at<int64_t>(i_wsoff);
         s.mode = kKmerCount;
         if ((rc = timed_launch(c, st, stats, fn, "sort kernel", 1, [&] {
                 hipLaunchKernelGGL(k_kmers_sort, dim3(n_piece), dim3(kKmerSortThreads), 0, st, s);
             }))) return rc;
-        HIP_TRY(hipMemcpyAsync(cnt.data(), c->km_cnt.p, ng * 4, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(cnt.data(), a.cnt, ng * 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         const int32_t g_end = sorted[p1 - 1] + 1;
         prefix_to(g_end);
         if (out_entry_off[g_end] <= n_out) {
-            HIP_TRY(hipMemcpyAsync(c->km_eoff.p, out_entry_off, (size_t)g_end * 8, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(d.at<int64_t>(i_eoff), out_entry_off, (size_t)g_end * 8, hipMemcpyHostToDevice, st));
             s.mode = kKmerWrite;
             if ((rc = timed_launch(c, st, stats, fn, "sort kernel (write)", 1, [&] {
                     hipLaunchKernelGGL(k_kmers_sort, dim3(n_piece), dim3(kKmerSortThreads), 0, st, s);
@@ -154,7 +154,7 @@ int64_t count_kmers_impl(strk_ctx* c, const char* fn, int32_t n_groups, const in
     const int64_t n_entries = out_entry_off[n_groups];
     if (n_entries > cap) return n_entries;
     // pass 2: the table kernel writes its groups' entries
-    HIP_TRY(hipMemcpyAsync(c->km_eoff.p, out_entry_off, ng * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(d.at<int64_t>(i_eoff), out_entry_off, ng * 8, hipMemcpyHostToDevice, st));
     if ((rc = timed_launch(c, st, stats, fn, "table kernel (write)", (n_small > 0) + (n_large > 0), [&] { table_pass(kKmerWrite); }))) return rc;
     HIP_TRY(hipMemcpyAsync(out_pos, a.out_pos, (size_t)n_entries * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(out_count, a.out_count, (size_t)n_entries * 4, hipMemcpyDeviceToHost, st));

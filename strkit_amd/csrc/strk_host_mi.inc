@@ -121,58 +121,43 @@ int strk_mi_trio(strk_ctx* c, int32_t n_loci, const int64_t* grp_off, const int3
             off_rel.resize(6 * nl + 1);
             for (size_t k = 0; k <= 6 * nl; ++k) off_rel[k] = grp_off[6 * l0 + k] - r0;
         }
-        Carve ci, co;
-        const size_t i_off = ci.take((6 * nl + 1) * 8), i_cn = ci.take((size_t)nr * 4 + 4), i_gt = ci.take(nl * 24), i_c95 = ci.take(nl * 48),
-                     i_c99 = ci.take(nl * 48), i_sid = ci.take(nl * 24), i_slen = ci.take(nl * 24), i_wsoff = ci.take(nl * 8),
-                     i_small = ci.take(nl * 4 + 4), i_large = ci.take(nl * 4 + 4);
-        const size_t o_p = co.take(nl * 8), o_cfg = co.take(nl * 4), o_from = co.take(nl * 4), o_st = co.take(nl * 4), o_res = co.take(nl * 7);
+        // without a test no reads go up and only `respects` comes down; absent intervals and sequences are absent here as well
+        Staging sg(c->image);
+        const size_t i_gt = sg.put(gt + 6 * l0, nl * 24), i_c95 = sg.put(ci95 + 12 * l0, nl * 48);
+        const size_t i_c99 = ci99 ? sg.put(ci99 + 12 * l0, nl * 48) : 0;
+        const size_t i_sid = seq_id ? sg.put(seq_id + 6 * l0, nl * 24) : 0, i_slen = seq_id ? sg.put(seq_len + 6 * l0, nl * 24) : 0;
+        const size_t i_off = reads ? sg.put(off_rel.data(), (6 * nl + 1) * 8) : 0, i_cn = reads ? sg.put(cn + r0, (size_t)nr * 4) : 0,
+                     i_wsoff = reads ? sg.put(ws_off.data(), nl * 8) : 0, i_small = reads ? sg.put(small_list.data(), small_list.size() * 4) : 0,
+                     i_large = reads ? sg.put(large_list.data(), large_list.size() * 4) : 0;
+        const size_t o_res = sg.get(out_respects + 7 * l0, nl * 7);
+        const size_t o_p = reads ? sg.get(out_p + l0, nl * 8) : 0, o_cfg = reads ? sg.get(out_config + l0, nl * 4) : 0,
+                     o_from = reads ? sg.get(out_mutation_from + l0, nl * 4) : 0, o_st = reads ? sg.get(out_status + l0, nl * 4) : 0;
         int rc;
-        if ((rc = c->mi_in.ensure(ci.bytes))) return rc;
         if ((rc = c->mi_ws.ensure(std::max<size_t>((size_t)ws_bytes, 256)))) return rc;
-        if ((rc = c->mi_out.ensure(co.bytes))) return rc;
-        char* const di = c->mi_in.as<char>();
+        if ((rc = sg.upload(c->mi_stage, st))) return rc;
+        const DevBuf& d = c->mi_stage;
         strk_mi::Args a = mi_rule_args(in);
-        a.grp_off = reads ? c->mi_in.at<int64_t>(i_off) : nullptr;
-        a.cn = c->mi_in.at<int32_t>(i_cn);
-        a.gt = c->mi_in.at<int32_t>(i_gt);
-        a.ci95 = c->mi_in.at<int32_t>(i_c95);
-        a.ci99 = ci99 ? c->mi_in.at<int32_t>(i_c99) : nullptr;
-        a.seq_id = seq_id ? c->mi_in.at<int32_t>(i_sid) : nullptr;
-        a.seq_len = seq_id ? c->mi_in.at<int32_t>(i_slen) : nullptr;
-        a.ws_off = c->mi_in.at<int64_t>(i_wsoff);
-        a.ws = c->mi_ws.as<char>();
-        a.p = c->mi_out.at<double>(o_p); a.config = c->mi_out.at<int32_t>(o_cfg); a.from = c->mi_out.at<int32_t>(o_from);
-        a.status = c->mi_out.at<int32_t>(o_st); a.respects = c->mi_out.at<int8_t>(o_res);
+        a.gt = d.at<int32_t>(i_gt);
+        a.ci95 = d.at<int32_t>(i_c95);
+        a.ci99 = ci99 ? d.at<int32_t>(i_c99) : nullptr;
+        a.seq_id = seq_id ? d.at<int32_t>(i_sid) : nullptr;
+        a.seq_len = seq_id ? d.at<int32_t>(i_slen) : nullptr;
+        a.respects = d.at<int8_t>(o_res);
         if (reads) {
-            HIP_TRY(hipMemcpyAsync(di + i_off, off_rel.data(), (6 * nl + 1) * 8, hipMemcpyHostToDevice, st));
-            if (nr > 0) HIP_TRY(hipMemcpyAsync(di + i_cn, cn + r0, (size_t)nr * 4, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(di + i_wsoff, ws_off.data(), nl * 8, hipMemcpyHostToDevice, st));
-            if (!small_list.empty()) HIP_TRY(hipMemcpyAsync(di + i_small, small_list.data(), small_list.size() * 4, hipMemcpyHostToDevice, st));
-            if (!large_list.empty()) HIP_TRY(hipMemcpyAsync(di + i_large, large_list.data(), large_list.size() * 4, hipMemcpyHostToDevice, st));
-        }
-        HIP_TRY(hipMemcpyAsync(di + i_gt, gt + 6 * l0, nl * 24, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(di + i_c95, ci95 + 12 * l0, nl * 48, hipMemcpyHostToDevice, st));
-        if (ci99) HIP_TRY(hipMemcpyAsync(di + i_c99, ci99 + 12 * l0, nl * 48, hipMemcpyHostToDevice, st));
-        if (seq_id) {
-            HIP_TRY(hipMemcpyAsync(di + i_sid, seq_id + 6 * l0, nl * 24, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(di + i_slen, seq_len + 6 * l0, nl * 24, hipMemcpyHostToDevice, st));
+            a.grp_off = d.at<int64_t>(i_off);
+            a.cn = d.at<int32_t>(i_cn);
+            a.ws_off = d.at<int64_t>(i_wsoff);
+            a.ws = c->mi_ws.as<char>();
+            a.p = d.at<double>(o_p); a.config = d.at<int32_t>(o_cfg); a.from = d.at<int32_t>(o_from); a.status = d.at<int32_t>(o_st);
         }
         const int32_t ns = reads ? (int32_t)small_list.size() : (int32_t)nl, ng = (int32_t)large_list.size();
         if ((rc = timed_launch(c, st, stats, fn, "trio kernels", (ns > 0) + (ng > 0), [&] {
                 if (ns > 0)
                     hipLaunchKernelGGL(strk_mi::k_mi_small, dim3((unsigned)((ns + strk_mi::kSmallWaves - 1) / strk_mi::kSmallWaves)),
-                                       dim3(64 * strk_mi::kSmallWaves), 0, st, a, reads ? c->mi_in.at<int32_t>(i_small) : (const int32_t*)nullptr, ns);
-                if (ng > 0) hipLaunchKernelGGL(strk_mi::k_mi_large, dim3((unsigned)ng), dim3(256), 0, st, a, c->mi_in.at<int32_t>(i_large));
-            }, [&] {
-                HIP_TRY(hipMemcpyAsync(out_respects + 7 * l0, a.respects, nl * 7, hipMemcpyDeviceToHost, st));
-                if (reads) {
-                    HIP_TRY(hipMemcpyAsync(out_p + l0, a.p, nl * 8, hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipMemcpyAsync(out_config + l0, a.config, nl * 4, hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipMemcpyAsync(out_mutation_from + l0, a.from, nl * 4, hipMemcpyDeviceToHost, st));
-                    HIP_TRY(hipMemcpyAsync(out_status + l0, a.status, nl * 4, hipMemcpyDeviceToHost, st));
-                }
-                return 0;
-            }))) return rc;
+                                       dim3(64 * strk_mi::kSmallWaves), 0, st, a, reads ? d.at<int32_t>(i_small) : (const int32_t*)nullptr, ns);
+                if (ng > 0) hipLaunchKernelGGL(strk_mi::k_mi_large, dim3((unsigned)ng), dim3(256), 0, st, a, d.at<int32_t>(i_large));
+            }, [&] { return sg.download(d, st); }))) return rc;
+        sg.scatter();
         if (stats) { stats->n_fallback += ng; stats->n_sub_batches += 1; }
     }
     return 0;

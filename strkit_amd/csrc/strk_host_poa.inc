@@ -1,6 +1,6 @@
 // Host side of strk_consensus / strk_consensus_dseqs / strk_consensus_ws: input checks, the method of every group, launches
 // of k_poa cut at a group count and at a workspace bound, the best-representative path for the rest, the bytes' gather.
-// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, strk_ctx, check_groups,
+// Part of strk_api.hip: included inside its anonymous namespace (uses fail(), HIP_TRY, DevBuf, Staging, strk_ctx, check_groups,
 // side_stream, timed_launch and best_rep_impl defined there); not a stand-alone header.
 // ---------------------------------------------------------------------------------------------
 // Allele sequences by partial-order alignment: strk_consensus
@@ -77,18 +77,16 @@ int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int3
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t st;
     if ((rc = side_stream(c, &st))) return rc;
-    if ((rc = c->po_res.ensure(ng * 16 + 8))) return rc;              // cells | index | method | len | state
+    // What the whole call holds, in one staged buffer sized here once: the view, where each group's consensus lies in the pool,
+    // and the results, which start as zeros.  Its image is the call's own (strk_ctx::po_image).
+    Staging sg(c->po_image);
+    const StagedGroups s_in = stage_groups(sg, view, tot, seqs, d_seqs);
+    const size_t i_poolof = sg.put(pool_of.data(), ng * 8);
+    const size_t o_cells = sg.zero(8), o_index = sg.zero(ng * 4), o_method = sg.zero(ng * 4), o_len = sg.zero(ng * 4), o_state = sg.zero(ng * 4);
     if ((rc = c->po_pool.ensure(std::max<size_t>((size_t)pool_bytes, 256)))) return rc;
-    if ((rc = c->po_poolof.ensure(ng * 8))) return rc;
-    if ((rc = c->po_in.upload(view, tot, seqs, d_seqs, st))) return rc;
-    const uint8_t* dev_seqs = c->po_in.bases;
-    HIP_TRY(hipMemcpyAsync(c->po_poolof.p, pool_of.data(), ng * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(c->po_res.p, 0, ng * 16 + 8, st));
-    unsigned long long* d_cells = c->po_res.as<unsigned long long>();
-    int32_t* d_index = reinterpret_cast<int32_t*>(d_cells + 1);
-    int32_t* d_method = d_index + n_groups;
-    int32_t* d_len = d_method + n_groups;
-    int32_t* d_state = d_len + n_groups;
+    if ((rc = sg.upload(c->po_call, st))) return rc;
+    const DevBuf& d = c->po_call;
+    const StagedGroups::Ptrs in = s_in.on(d);
 
     // k_poa over its groups, in pieces
     std::vector<int64_t> ws_off, pool_off;
@@ -107,52 +105,47 @@ int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int3
             caps[(size_t)2 * n_piece + k] = need[p0 + k].row_len;
         }
         if ((rc = c->po_ws.ensure((size_t)used * 4, false))) return rc;
-        if ((rc = c->po_list.ensure((size_t)n_piece * (4 + 8 + 8 + 12)))) return rc;   // ws_off | pool_off | list | caps
-        int64_t* d_wsoff = c->po_list.as<int64_t>();
-        int64_t* d_pooloff = d_wsoff + n_piece;
-        int32_t* d_list = reinterpret_cast<int32_t*>(d_pooloff + n_piece);
-        int32_t* d_caps = d_list + n_piece;
-        HIP_TRY(hipMemcpyAsync(d_wsoff, ws_off.data(), (size_t)n_piece * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_pooloff, pool_off.data(), (size_t)n_piece * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_list, poa_list.data() + p0, (size_t)n_piece * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(d_caps, caps.data(), (size_t)n_piece * 12, hipMemcpyHostToDevice, st));
+        Staging ps(c->image);
+        const size_t i_wsoff = ps.put(ws_off.data(), (size_t)n_piece * 8), i_pooloff = ps.put(pool_off.data(), (size_t)n_piece * 8),
+                     i_list = ps.put(poa_list.data() + p0, (size_t)n_piece * 4), i_ncap = ps.put(caps.data(), (size_t)n_piece * 4),
+                     i_ecap = ps.put(caps.data() + n_piece, (size_t)n_piece * 4), i_rlen = ps.put(caps.data() + 2 * (size_t)n_piece, (size_t)n_piece * 4);
+        if ((rc = ps.upload(c->po_piece, st))) return rc;
+        const DevBuf& dp = c->po_piece;
         PoaArgs a{};
-        a.list = d_list;
-        a.group_off = c->po_in.off.as<int32_t>();
-        a.seqs = dev_seqs;
-        a.seq_start = c->po_in.start.as<int64_t>();
-        a.seq_len = c->po_in.len.as<int32_t>();
+        a.list = dp.at<int32_t>(i_list);
+        a.group_off = in.off;
+        a.seqs = in.seqs;
+        a.seq_start = in.start;
+        a.seq_len = in.len;
         a.ws = c->po_ws.as<int32_t>();
-        a.ws_off = d_wsoff;
-        a.node_cap = d_caps;
-        a.edge_cap = d_caps + n_piece;
-        a.row_len = d_caps + 2 * n_piece;
+        a.ws_off = dp.at<int64_t>(i_wsoff);
+        a.node_cap = dp.at<int32_t>(i_ncap);
+        a.edge_cap = dp.at<int32_t>(i_ecap);
+        a.row_len = dp.at<int32_t>(i_rlen);
         a.pool = c->po_pool.as<uint8_t>();
-        a.pool_off = d_pooloff;
-        a.out_index = d_index;
-        a.out_method = d_method;
-        a.out_len = d_len;
-        a.out_state = d_state;
-        a.cells = d_cells;
+        a.pool_off = dp.at<int64_t>(i_pooloff);
+        a.out_index = d.at<int32_t>(o_index);
+        a.out_method = d.at<int32_t>(o_method);
+        a.out_len = d.at<int32_t>(o_len);
+        a.out_state = d.at<int32_t>(o_state);
+        a.cells = d.at<unsigned long long>(o_cells);
         a.n_list = n_piece;
         if ((rc = timed_launch(c, st, stats, fn, "POA kernel", 1, [&] {
                 hipLaunchKernelGGL(k_poa, dim3(n_piece), dim3(kPoaThreads), 0, st, a);
             }))) return rc;
         if (stats) stats->n_sub_batches += 1;
     }
-    std::vector<int32_t> res(ng * 4);   // index | method | len | state
-    unsigned long long cells = 0;
-    HIP_TRY(hipMemcpyAsync(&cells, d_cells, 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(res.data(), d_index, ng * 16, hipMemcpyDeviceToHost, st));
+    if ((rc = sg.download(d, o_cells, o_state + ng * 4, st))) return rc;
     {
         const hipError_t q = hipStreamSynchronize(st);   // (the bases are on the device now as well)
         if (q != hipSuccess) return fail(STRK_E_DEVICE, "%s: POA results: %s", fn, hipGetErrorString(q));
     }
-    if (stats) stats->dp_cells = (int64_t)cells;
-    int32_t* r_index = res.data();
-    int32_t* r_method = r_index + ng;
-    int32_t* r_len = r_method + ng;
-    const int32_t* r_state = r_len + ng;
+    if (stats) stats->dp_cells = (int64_t)*sg.at<unsigned long long>(o_cells);
+    // the results where they came down: the best-representative pass below fills in its groups
+    int32_t* r_index = sg.mut<int32_t>(o_index);
+    int32_t* r_method = sg.mut<int32_t>(o_method);
+    int32_t* r_len = sg.mut<int32_t>(o_len);
+    const int32_t* r_state = sg.at<int32_t>(o_state);
     for (int32_t g : poa_list) {
         if (r_state[g] == kPoaBroken) return fail(STRK_E_DEVICE, "%s: group %d: the POA kernel lost its trace-back", fn, g);
         if (r_state[g] == kPoaOverflow) route[(size_t)g] = 2;
@@ -171,7 +164,7 @@ int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int3
             b_off[k + 1] = (int32_t)b_len.size();
         }
         strk_stats bs;
-        if ((rc = best_rep_impl(c, fn, (int32_t)rest.size(), b_off.data(), nullptr, dev_seqs, n_seq_bytes, b_start.data(), b_len.data(),
+        if ((rc = best_rep_impl(c, fn, (int32_t)rest.size(), b_off.data(), nullptr, in.seqs, n_seq_bytes, b_start.data(), b_len.data(),
                                 b_index.data(), b_method.data(), b_dist.data(), &bs))) return rc;
         if (stats) {
             stats->kernel_ms += bs.kernel_ms;
@@ -194,18 +187,18 @@ int64_t consensus_impl(strk_ctx* c, const char* fn, int32_t n_groups, const int3
     if (n_bytes > cap || n_bytes == 0) return n_bytes;
     // the bytes of every group, gathered on the device
     if ((rc = c->po_out.ensure((size_t)n_bytes))) return rc;
-    if ((rc = c->po_outoff.ensure((ng + 1) * 8))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->po_outoff.p, out_seq_off, (ng + 1) * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(d_index, r_index, ng * 8, hipMemcpyHostToDevice, st));   // index | method
+    Staging gs(c->image);
+    const size_t i_outoff = gs.put(out_seq_off, (ng + 1) * 8), i_index = gs.put(r_index, ng * 4), i_method = gs.put(r_method, ng * 4);
+    if ((rc = gs.upload(c->po_piece, st))) return rc;
     PoaGatherArgs ga{};
-    ga.group_off = c->po_in.off.as<int32_t>();
-    ga.seqs = dev_seqs;
-    ga.seq_start = c->po_in.start.as<int64_t>();
-    ga.index = d_index;
-    ga.method = d_method;
-    ga.out_off = c->po_outoff.as<int64_t>();
+    ga.group_off = in.off;
+    ga.seqs = in.seqs;
+    ga.seq_start = in.start;
+    ga.index = c->po_piece.at<int32_t>(i_index);
+    ga.method = c->po_piece.at<int32_t>(i_method);
+    ga.out_off = c->po_piece.at<int64_t>(i_outoff);
     ga.pool = c->po_pool.as<uint8_t>();
-    ga.pool_of = c->po_poolof.as<int64_t>();
+    ga.pool_of = d.at<int64_t>(i_poolof);
     ga.out = c->po_out.as<uint8_t>();
     ga.n_groups = n_groups;
     if ((rc = timed_launch(c, st, stats, fn, "gather kernel", 1, [&] {

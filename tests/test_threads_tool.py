@@ -1,6 +1,7 @@
 """CPU: builds tools/threads_asan.cpp without a sanitizer and runs it (no HIP in strk_threads.h, none in strk_bamrec.h for the
 host compiler): the two thread fans cover their items exactly once around their thresholds on 1 to 32 threads, FirstBad keeps
-the minimum, the piece loop covers its items in order up to INT32_MAX, and check_alt gives every refusal by its message; the
+the minimum, the piece loop covers its items in order up to INT32_MAX, check_alt gives every refusal by its message, and the
+copy plan of a staged buffer (strk_stage_plan.h, no HIP in it either) covers every byte that goes up exactly once; the
 program counts its own failures and exits 0 without one.  tools/threads_asan.sh runs the same program under the sanitizers."""
 import os
 import shutil

@@ -3,7 +3,10 @@
 // [0, n) exactly once for sizes around its thresholds on 1 to 32 threads, FirstBad keeps the minimum under 32 reporting
 // threads, the piece loop covers its items in ascending pieces up to INT32_MAX without forming a sum in 32 bits (arithmetic
 // only: the function it calls counts), and check_alt gives every refusal by its message over heap blocks of exactly their
-// length.  tools/threads_asan.sh runs it under AddressSanitizer + UBSan and under ThreadSanitizer; tests/test_threads_tool.py
+// length.  The copy plan of a staged buffer (strk_stage_plan.h): over parts around the alignment and around kDirectBytes, zeros,
+// empty parts, rooms between and behind parts and direct neighbours, every byte of a part that goes up is covered by exactly
+// one copy or memset, no stretch of the image runs over more than the alignment padding between two parts, nothing leaves the
+// buffer, and small neighbours take one copy.  tools/threads_asan.sh runs it under AddressSanitizer + UBSan and under ThreadSanitizer; tests/test_threads_tool.py
 // builds it plain and requires exit 0.
 #include <cstdint>
 #include <cstdio>
@@ -11,6 +14,7 @@
 #include <memory>
 #include <vector>
 #include "../strkit_amd/csrc/strk_bamrec.h"
+#include "../strkit_amd/csrc/strk_stage_plan.h"
 #include "../strkit_amd/csrc/strk_threads.h"
 
 namespace {
@@ -163,6 +167,94 @@ void alt_check() {
     expect(cig == rec_cigar && n_cig == 1 && at == 100, "no triple: the record's CIGAR");
 }
 
+// The plan of `l` against its parts, byte by byte; n_copies >= 0: the plan has that many steps.
+void check_plan(const strk_stage::Layout& l, const char* what, int n_copies = -1) {
+    using strk_stage::Copy;
+    const size_t n = l.cv.bytes;
+    const std::vector<Copy> plan = strk_stage::plan(l.up());
+    std::vector<uint8_t> in_part(n, 0), covered(n, 0);
+    for (const strk_stage::Part& p : l.up()) {
+        expect(p.at % 256 == 0 && p.at + p.bytes <= n, what, (long long)p.at, (long long)p.bytes);
+        for (size_t b = 0; b < p.bytes; ++b) in_part[p.at + b] = 1;
+    }
+    bool inside = true, once = true, short_gaps = true, exact = true;
+    for (const Copy& k : plan) {
+        if (k.bytes == 0 || k.at + k.bytes > n) { inside = false; continue; }
+        size_t gap = 0;
+        for (size_t b = k.at; b < k.at + k.bytes; ++b) {
+            ++covered[b];
+            gap = in_part[b] ? 0 : gap + 1;
+            if (gap > 255 || (gap && k.kind != Copy::kImage)) short_gaps = false;   // (a direct copy or a memset is one part, whole)
+        }
+        if (k.kind == Copy::kImage) continue;
+        bool found = false;   // the part it is: zeros for a memset, the caller's memory for a direct copy
+        for (const strk_stage::Part& p : l.up())
+            found = found || (p.at == k.at && p.bytes == k.bytes && p.mem == k.mem && (p.mem != nullptr) == (k.kind == Copy::kDirect));
+        exact = exact && found && k.bytes >= strk_stage::kDirectBytes;
+    }
+    for (size_t b = 0; b < n; ++b)
+        if (in_part[b] ? covered[b] != 1 : covered[b] > 1) once = false;
+    expect(inside, "plan: copies lie inside the buffer", (long long)n);
+    expect(once, what);
+    expect(short_gaps, "plan: no stretch runs over more than the padding between two parts");
+    expect(exact, "plan: a direct copy or a memset is one large part");
+    if (n_copies >= 0) expect((int)plan.size() == n_copies, what, (long long)plan.size(), n_copies);
+}
+
+void stage_plan() {
+    using strk_stage::Layout;
+    constexpr size_t kD = strk_stage::kDirectBytes;
+    static_assert(kD == 262144, "the threshold tests/test_gpu_context_staging.py is written for");
+    static const std::vector<char> mem(kD + 4, 'x');   // (the plan keeps addresses and reads nothing)
+    for (const size_t bytes : {(size_t)1, (size_t)255, (size_t)256, (size_t)257, kD - 4, kD, kD + 4}) {
+        for (const bool zeros : {false, true}) {
+            Layout one;
+            one.put(zeros ? nullptr : mem.data(), bytes);
+            check_plan(one, "plan: one part", 1);
+            Layout mid;   // between two small parts: one stretch below the threshold, three steps from it on
+            mid.put(mem.data(), 40);
+            zeros ? mid.zero(bytes) : mid.put(mem.data(), bytes);
+            mid.put(mem.data(), 8);
+            check_plan(mid, "plan: a part between two small ones", bytes < kD ? 1 : 3);
+        }
+    }
+    Layout small;   // n small neighbours: one copy
+    for (int k = 1; k <= 12; ++k) k % 4 ? small.put(mem.data(), (size_t)k * 100) : small.zero((size_t)k * 100);
+    check_plan(small, "plan: small neighbours take one copy", 1);
+    Layout empty;   // empty parts, also first and last, and nothing else
+    empty.put(mem.data(), 0);
+    check_plan(empty, "plan: nothing to send", 0);
+    empty.put(mem.data(), 100);
+    empty.zero(0);
+    empty.put(nullptr, 0);
+    empty.put(mem.data(), 300);
+    empty.put(mem.data(), 0);
+    check_plan(empty, "plan: empty parts are skipped", 1);
+    Layout gap;   // a room between two small parts is not sent
+    gap.put(mem.data(), 100);
+    gap.room((size_t)1 << 20);
+    gap.put(mem.data(), 100);
+    check_plan(gap, "plan: a stretch ends at a room", 2);
+    Layout results;   // a result between two parts is a room of the way up
+    results.put(mem.data(), 100);
+    results.get(nullptr, 4096);
+    results.zero(100);
+    check_plan(results, "plan: a stretch ends at a result", 2);
+    Layout last;   // a room last
+    last.put(mem.data(), 1000);
+    last.zero(24);
+    last.room(kD);
+    check_plan(last, "plan: a room last", 1);
+    Layout direct;   // direct neighbours, a memset among them, small parts around
+    direct.put(mem.data(), 16);
+    direct.put(mem.data(), kD);
+    direct.put(mem.data(), kD + 4);
+    direct.zero(kD);
+    direct.put(mem.data(), 16);
+    direct.put(mem.data(), 16);
+    check_plan(direct, "plan: direct neighbours", 5);
+}
+
 }  // namespace
 
 int main() {
@@ -170,6 +262,7 @@ int main() {
     first_bad();
     pieces();
     alt_check();
+    stage_plan();
     std::printf("threads_asan: %d checks, %d failed\n", g_checks, g_failed);
     return g_failed ? 1 : 0;
 }

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The thread fans, FirstBad and the piece loop of strk_threads.h and check_alt of strk_bamrec.h on the host (no GPU needed): once under AddressSanitizer + UBSan, once under ThreadSanitizer.
+# The thread fans, FirstBad and the piece loop of strk_threads.h check_alt of strk_bamrec.h and the copy plan of strk_stage_plan.h on the host (no GPU needed): once under AddressSanitizer + UBSan, once under ThreadSanitizer.
 set -e
 D=${TMPDIR:-/tmp}/strk_threads_asan
 mkdir -p $D
