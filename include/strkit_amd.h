@@ -661,6 +661,36 @@ int strk_dbam_download_cells(strk_dbam* d, int64_t n_cells, uint8_t* out_base, u
 int64_t strk_dbam_useful_snvs(strk_dbam* d, int32_t n_loci, const int32_t* kept_off, const int32_t* kept_item, int32_t min_allele_reads,
                               int32_t* out_snv_off, int32_t* out_snv_cand, uint8_t* out_base, uint8_t* out_qual, int64_t cap);
 
+/* ---- candidate SNVs from a pileup of the reads (the rule: DESIGN.md §21, frontend/snv_discovery.py) ---------------------------
+ * The reference takes its candidate SNVs from a VCF and has no such step: the rule is this project's own.
+ *
+ * strk_discover_snvs: items, alt_* and clip_threshold / take_in as in strk_phase_cells; locus l has the flanked locus
+ * [left_coord[l], right_coord[l]) and keeps the reads kept_item[kept_off[l] .. kept_off[l+1]) (items of that locus), n of them
+ * (at most 65 535; a locus that is to have no candidates is given no kept read).  The window of a locus is the positions p >= 0
+ * with left_coord - window <= p < left_coord or right_coord <= p < right_coord + window (1 <= window <= 65 536,
+ * |coordinates| <= 2^40).  At p a kept read counts for the base it would have as a cell of strk_phase_cells there, iff that
+ * base is one of A C G T and the read has no qualities or its quality there is >= min_base_qual (0 .. 255).  p is a candidate
+ * iff at least two of the four counts are >= max(rint(n / 5.0), min_allele_reads) (float64, round half to even).
+ * out_cand_off [n_loci+1], out_cand_pos = the candidates of every locus, ascending, loci back to back; a locus with more than
+ * 1 024 keeps the 1 024 nearest to its flanked locus (distance left_coord - p on the left, p - (right_coord - 1) on the right,
+ * of two at one distance the left one first).  Returns the number of candidates; when it exceeds cap no position is written
+ * (a size query), the offsets are.  A malformed record (any item's, kept or not) is STRK_E_INVALID naming the item.  Runs on
+ * the host's cores.
+ * strk_dbam_discover_snvs: the same over the file resident on the device (kernels k_snv_span: one wave per item; k_snv_pileup:
+ * one workgroup per locus and tile of 4 096 positions, the counts in LDS; k_snv_pick: one workgroup per locus).  Its workspace is
+ * 512 bytes per tile, n_loci x 2 x ceil(window / 4 096) tiles, at most 512 MB (STRK_E_NOMEM beyond: call it for fewer loci).
+ * piece_items > 0 cuts the launches into that many items (spans) and tiles (pileup) each; the result does not depend on it. */
+int64_t strk_discover_snvs(const uint8_t* buf, int64_t n_bytes, int32_t n_items, const int64_t* rec_off, const int32_t* item_locus,
+                           int32_t n_loci, const int64_t* left_coord, const int64_t* right_coord, const int32_t* kept_off /*[n_loci+1]*/,
+                           const int32_t* kept_item, const uint32_t* alt_cigar, const int64_t* alt_cigar_off, const int64_t* alt_start,
+                           int32_t clip_threshold, int32_t take_in, int32_t window, int32_t min_base_qual, int32_t min_allele_reads,
+                           int32_t* out_cand_off, int64_t* out_cand_pos, int64_t cap);
+int64_t strk_dbam_discover_snvs(strk_dbam* d, int32_t n_items, const int64_t* rec_off, const int32_t* item_locus, int32_t n_loci,
+                                const int64_t* left_coord, const int64_t* right_coord, const int32_t* kept_off, const int32_t* kept_item,
+                                const uint32_t* alt_cigar, const int64_t* alt_cigar_off, const int64_t* alt_start, int32_t clip_threshold,
+                                int32_t take_in, int32_t window, int32_t min_base_qual, int32_t min_allele_reads, int32_t piece_items,
+                                int32_t* out_cand_off, int64_t* out_cand_pos, int64_t cap);
+
 /* ---- 5-methyl CpG calls of a read inside a locus's tract, from its MM / ML tags (the rule: DESIGN.md §14, frontend/methyl.py) --
  * Stands where the reference calls STRkitAlignedSegment.get_methylation_prop(locus, 127, 0.0) (strkit_rust_ext, not in its tree;
  * call site strkit/call/call_locus.py:1301-1305): the rule is this project's own, built from the SAM tags specification.

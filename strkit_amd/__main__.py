@@ -58,6 +58,12 @@ def build_parser() -> argparse.ArgumentParser:
     c.add_argument("--snv-phase-sets", action="store_true",
                    help="--incorporate-snvs: loci that share heterozygous SNVs get one phase set (PS, '|' genotypes), and the "
                         "called SNVs are written to the VCF as records of their own")
+    c.add_argument("--discover-snvs", action="store_true",
+                   help="group the reads by the bases they carry at SNVs found in the reads themselves (GPU with the device front end): a "
+                        "position near the locus at which two bases each occur in enough reads; needs --call-alleles and no "
+                        "--incorporate-snvs")
+    c.add_argument("--snv-discover-window", type=int, default=8192, metavar="N",
+                   help="--discover-snvs: how far on either side of the flanked locus SNVs are looked for (1 .. 65536)")
     c.add_argument("--snv-min-base-qual", type=int, default=20)
     c.add_argument("--significant-clip-threshold", type=int, default=100)
     c.add_argument("--use-methyl", "-m", action="store_true",
@@ -144,6 +150,12 @@ def main(argv=None) -> int:
         ap.error("--use-hp / --incorporate-snvs need --call-alleles")
     if a.snv_phase_sets and not a.incorporate_snvs:
         ap.error("--snv-phase-sets needs --incorporate-snvs")
+    if a.discover_snvs and not a.call_alleles:
+        ap.error("--discover-snvs needs --call-alleles")
+    if a.discover_snvs and a.incorporate_snvs:
+        ap.error("--discover-snvs and --incorporate-snvs are two sources of candidate SNVs: give one of them")
+    if not 1 <= a.snv_discover_window <= 65536:
+        ap.error("--snv-discover-window must be in 1 .. 65536")
     if a.ploidy is not None:
         if not a.call_alleles:
             ap.error("--ploidy needs --call-alleles")
@@ -180,7 +192,8 @@ def main(argv=None) -> int:
                       min_read_align_score=a.min_read_align_score, front_end=a.front_end, span_bytes=a.span_mb << 20,
                       count_kmers=a.count_kmers, consensus_method=a.consensus_method, max_mdn_poa_length=a.max_mdn_poa_length,
                       **(dict(use_hp=a.use_hp, snv_vcf=a.incorporate_snvs, snv_min_base_qual=a.snv_min_base_qual,
-                              significant_clip_threshold=a.significant_clip_threshold) if a.use_hp or a.incorporate_snvs else {}),
+                              significant_clip_threshold=a.significant_clip_threshold) if a.use_hp or a.incorporate_snvs or a.discover_snvs else {}),
+                      **(dict(discover_snvs=True, snv_discover_window=a.snv_discover_window) if a.discover_snvs else {}),
                       **(dict(use_methyl=True, methyl_threshold=a.methyl_threshold) if a.use_methyl else {}),
                       **(dict(ploidy=a.ploidy) if a.ploidy is not None else {}),
                       **(dict(snv_phase_sets=True) if a.snv_phase_sets else {}),

@@ -89,6 +89,7 @@ EXPORTS = ("strk_init", "strk_destroy", "strk_last_error", "strk_version", "strk
            "strk_count_kmers", "strk_count_kmers_dseqs", "strk_count_kmers_ws",
            "strk_consensus", "strk_consensus_dseqs", "strk_consensus_ws",
            "strk_phase_cells", "strk_useful_snvs", "strk_dbam_phase_cells", "strk_dbam_download_cells", "strk_dbam_useful_snvs",
+           "strk_discover_snvs", "strk_dbam_discover_snvs",
            "strk_methyl", "strk_dbam_methyl", "strk_methyl_constants",
            "strk_vcf_snvs", "strk_dbam_vcf_snvs", "strk_vcf_constants", "strk_dbam_text_lines",
            "strk_gff_overlaps", "strk_dbam_gff_overlaps", "strk_gff_constants",
@@ -269,6 +270,12 @@ def load(build: bool = True):
         L.strk_dbam_useful_snvs.restype = C.c_int64
         L.strk_dbam_useful_snvs.argtypes = ([C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 4
                                             + [C.c_int64])
+        L.strk_discover_snvs.restype = C.c_int64
+        L.strk_discover_snvs.argtypes = ([C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7
+                                         + [C.c_int32] * 5 + [C.c_void_p] * 2 + [C.c_int64])
+        L.strk_dbam_discover_snvs.restype = C.c_int64
+        L.strk_dbam_discover_snvs.argtypes = ([C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] + [C.c_void_p] * 7
+                                              + [C.c_int32] * 6 + [C.c_void_p] * 2 + [C.c_int64])
         L.strk_methyl.restype = C.c_int
         L.strk_methyl.argtypes = [C.c_void_p, C.c_int64, C.c_int32] + [C.c_void_p] * 5 + [C.c_int32] + [C.c_void_p] * 4
         L.strk_dbam_methyl.restype = C.c_int

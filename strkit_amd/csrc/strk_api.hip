@@ -28,6 +28,7 @@
 #include "strk_threads.h"
 #include "strk_phase_check.h"
 #include "strk_phase_inputs.h"
+#include "strk_snv_discover.h"
 #include "strk_methyl.h"
 #include "strk_vcf.h"
 #include "strk_gff.h"
@@ -1377,6 +1378,7 @@ int strk_realign_i16_flags(int32_t n_pairs, const int64_t* s1_off, const int64_t
 #include "strk_dbam.inc"
 #include "strk_lines.inc"
 #include "strk_phase_inputs.inc"
+#include "strk_snv_discover.inc"
 #include "strk_methyl.inc"
 #include "strk_vcf.inc"
 #include "strk_gff.inc"

@@ -235,6 +235,7 @@ struct strk_dbam {
     std::vector<int32_t> pc_item_locus, pc_cand_off_h;
     std::vector<int64_t> pc_cell_off_h;
     bool pc_valid = false;
+    DevBuf sd_masks;   // strk_dbam_discover_snvs (strk_snv_discover.inc): the candidate masks of its tiles, 512 bytes each
     DevBuf ln_tiles, ln_starts, ln_query;   // the lines of a text (strk_lines.inc): per tile, the line starts; a reader's status words and contig name
     DevBuf vc_lines, vc_out;   // strk_dbam_vcf_snvs (strk_vcf.inc): per line, per kept line
     DevBuf gf_lines, gf_feat, gf_join, gf_pairs, gf_out, gf_text;   // strk_dbam_gff_overlaps (strk_gff.inc): per line, feature, locus, pair; what is downloaded

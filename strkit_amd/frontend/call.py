@@ -20,14 +20,14 @@ from .fasta import Fasta
 from .gather import SHARDING_REFUSALS, _collector_paused, _distributed, call_blocks_sharded, deal_locus_blocks, shared_seed
 from .loci import Locus, load_loci, resolve_contig
 from .native import DeviceBam, IndexedBam, NativeBam
-from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, AnnotationCallOptions, CallOptions, MethylCallOptions, PhasedCallOptions, PhaseSetCallOptions, PloidyCallOptions, PoaCallOptions, ReadSelectionCallOptions,
+from .options import (DEFAULT_REF_MAX_ITERS, MAX_READS, AnnotationCallOptions, CallOptions, MethylCallOptions, PhasedCallOptions, PhaseSetCallOptions, PloidyCallOptions, PoaCallOptions, ReadSelectionCallOptions, SnvDiscoveryCallOptions,
                       allele_counts, phased, report_parameters, with_keywords)
 from .phase_block import PhaseRun
 from .reader import open_path
 from .refside import get_loci_with_ref_data, get_locus_with_ref_data, ref_side_of_blocks
 
 # (what moved to the other modules is still offered here under the names it had)
-__all__ = ["AnnotationCallOptions", "CallOptions", "PoaCallOptions", "PhasedCallOptions", "MethylCallOptions", "PloidyCallOptions", "PhaseSetCallOptions", "ReadSelectionCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
+__all__ = ["AnnotationCallOptions", "CallOptions", "PoaCallOptions", "PhasedCallOptions", "MethylCallOptions", "PloidyCallOptions", "PhaseSetCallOptions", "ReadSelectionCallOptions", "SnvDiscoveryCallOptions", "call_sample", "call_locus", "call_blocks", "call_blocks_sharded", "deal_locus_blocks", "write_json", "get_locus_with_ref_data", "get_loci_with_ref_data", "MAX_READS"]
 
 
 def ploidy_blocks(blocks, opts):
@@ -60,7 +60,7 @@ def call_sample(bam: BamFile | str, ref: Fasta | str, loci_file: str, *, sample_
     memory runs out).  Under torch.distributed every rank opens the file on its own GPU and calls its share of the blocks, genotypes
     included; `seed=None` is then drawn by rank 0 and broadcast, so that every rank calls with one seed and reports
     it: the seed of a locus is locus_seeds(run seed, t_idx), so a call does not depend on which rank owns its locus.
-    `snv_phase_sets` and `use_methyl` are refused there (NotImplementedError), before a file is opened."""
+    `snv_phase_sets`, `discover_snvs` and `use_methyl` are refused there (NotImplementedError), before a file is opened."""
     opts = with_keywords(opts, **option_keywords)
     for name, why in SHARDING_REFUSALS.items():
         if getattr(opts, name, False) and _distributed():
@@ -216,7 +216,7 @@ def call_blocks(blocks, bam: BamFile, ref: Fasta, opts: CallOptions | None = Non
     opts.validate()
     blocks, _ = ploidy_blocks(blocks, opts)
     # the candidate SNVs and the renumbering of the phase sets: one per run (an indexed SNV file is read where the alignments are)
-    phase_run = PhaseRun(opts, device=getattr(bam, "device", 0) if isinstance(bam, DeviceBam) else None) if phased(opts) else None
+    phase_run = PhaseRun(opts, device=getattr(bam, "device", 0) if isinstance(bam, DeviceBam) else None, ref=ref) if phased(opts) else None
     sets = phase_run.sets if phase_run is not None else None      # (snv_phase_sets: phase sets across loci, phase_sets.py)
     ctx = ctx or _lib.default_context()
     run_block = _call_block_native if isinstance(bam, (NativeBam, IndexedBam, DeviceBam)) else _call_block_python

@@ -76,6 +76,8 @@ SHARDING_REFUSALS = {
     "snv_phase_sets": "snv_phase_sets=True under torch.distributed: the phase sets of SNV calls are a serial chain over the loci of a "
                       "contig that runs before the allele sequences and k-mer counts read the peaks (phase_sets.resolve_block), so "
                       "a rank cannot make it for its own blocks alone; run one process",
+    "discover_snvs": "discover_snvs=True under torch.distributed: the ranks do not discover candidate SNVs yet (the gathered rows would "
+                     "carry them as a file's candidates are carried, which is untested); run one process",
     "use_methyl": "use_methyl=True under torch.distributed: the records that the ranks gather (call_blocks_sharded) have no "
                   "fields for methylation yet; run one process",
 }

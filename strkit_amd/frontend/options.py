@@ -215,6 +215,34 @@ class AnnotationCallOptions(ReadSelectionCallOptions):
 ANNOTATION_OPTION_NAMES = ("annotation_file",)
 
 
+@dataclass
+class SnvDiscoveryCallOptions(AnnotationCallOptions):
+    """AnnotationCallOptions plus candidate SNVs from the reads themselves (frontend/snv_discovery.py; `strkit call
+    --discover-snvs`).  `discover_snvs`: reads are grouped by the bases they carry at the useful SNVs, as with `snv_vcf`, and the
+    candidate positions come from a pileup of each locus's kept reads instead of a file: a position within `snv_discover_window`
+    bases of the flanked locus at which two bases each occur in enough reads.  `snv_min_base_qual` and
+    `significant_clip_threshold` apply as they do with a file.  Needs call_alleles; a run has one source of candidates, so it is
+    refused together with `snv_vcf` (and `snv_phase_sets` keeps needing `snv_vcf`).  A type of its own for the reason
+    PoaCallOptions gives."""
+    discover_snvs: bool = False
+    snv_discover_window: int = 8192      # a default of the option, not a measured threshold: about half a 15 kb read
+
+    def validate(self) -> None:
+        super().validate()
+        if not isinstance(self.discover_snvs, bool):
+            raise ValueError(f"discover_snvs must be True or False: got {self.discover_snvs!r}")
+        w = self.snv_discover_window
+        if isinstance(w, bool) or not isinstance(w, int) or not 1 <= w <= 65536:
+            raise ValueError(f"snv_discover_window must be an integer in 1 .. 65536: got {w!r}")
+        if self.discover_snvs and not self.call_alleles:
+            raise ValueError("discover_snvs=True requires call_alleles=True: the SNVs decide how the reads of a call are grouped")
+        if self.discover_snvs and self.snv_vcf:
+            raise ValueError("discover_snvs=True and snv_vcf are two sources of candidate SNVs: give one of them")
+
+
+SNV_DISCOVERY_OPTION_NAMES = ("discover_snvs", "snv_discover_window")
+
+
 def allele_counts(opts):
     """What genotype.n_alleles_of takes for a run: its ploidy configuration where one is set, else its n_alleles."""
     ploidy = getattr(opts, "ploidy", None)
@@ -226,16 +254,18 @@ def allele_counts(opts):
 
 def phased(opts) -> bool:
     """Whether a switch of PhasedCallOptions is on (any options type may be asked)."""
-    return bool(getattr(opts, "use_hp", False) or getattr(opts, "snv_vcf", None))
+    return bool(getattr(opts, "use_hp", False) or getattr(opts, "snv_vcf", None) or getattr(opts, "discover_snvs", False))
 
 
 def with_keywords(opts: CallOptions | None, **option_keywords) -> CallOptions:
     """`opts` (or the defaults) with the options given by name replaced: dataclasses.replace, after widening a plain
     CallOptions to PoaCallOptions when one of POA_OPTION_NAMES is among them, to PhasedCallOptions for PHASE_OPTION_NAMES, to
     MethylCallOptions for METHYL_OPTION_NAMES, to PloidyCallOptions for PLOIDY_OPTION_NAMES, to PhaseSetCallOptions for
-    PHASE_SET_OPTION_NAMES, to ReadSelectionCallOptions for READ_SELECTION_OPTION_NAMES, and to AnnotationCallOptions for
-    ANNOTATION_OPTION_NAMES.  An unknown name is a TypeError."""
+    PHASE_SET_OPTION_NAMES, to ReadSelectionCallOptions for READ_SELECTION_OPTION_NAMES, to AnnotationCallOptions for
+    ANNOTATION_OPTION_NAMES, and to SnvDiscoveryCallOptions for SNV_DISCOVERY_OPTION_NAMES.  An unknown name is a TypeError."""
     opts = opts or CallOptions()
+    if not isinstance(opts, SnvDiscoveryCallOptions) and any(k in option_keywords for k in SNV_DISCOVERY_OPTION_NAMES):
+        opts = SnvDiscoveryCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, AnnotationCallOptions) and any(k in option_keywords for k in ANNOTATION_OPTION_NAMES):
         opts = AnnotationCallOptions(**{f.name: getattr(opts, f.name) for f in dataclasses.fields(opts)})
     if not isinstance(opts, ReadSelectionCallOptions) and any(k in option_keywords for k in READ_SELECTION_OPTION_NAMES):
@@ -277,4 +307,6 @@ def report_parameters(opts: CallOptions, processes: int) -> dict:
             **({"ploidy": opts.ploidy} if getattr(opts, "ploidy", None) is not None else {}),
             **({"snv_phase_sets": True} if getattr(opts, "snv_phase_sets", False) else {}),
             **{name: True for name in READ_SELECTION_OPTION_NAMES if getattr(opts, name, False)},
-            **({"annotation_file": opts.annotation_file} if getattr(opts, "annotation_file", None) else {})}
+            **({"annotation_file": opts.annotation_file} if getattr(opts, "annotation_file", None) else {}),
+            **({"discover_snvs": True, "snv_discover_window": opts.snv_discover_window, "snv_min_base_qual": opts.snv_min_base_qual}
+               if getattr(opts, "discover_snvs", False) else {})}

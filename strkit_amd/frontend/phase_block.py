@@ -15,6 +15,7 @@ from . import phase_inputs as pi
 from .genotype import n_alleles_of
 from .options import allele_counts
 from .phase_sets import PhaseSets
+from .snv_discovery import DiscoveredSnvs, discover_candidates, library_discover_snvs
 from .snv_vcf import IndexedSnvVcf, open_snv_candidates
 
 MAX_CELLS = (512 << 20) // 2      # cells (a base and a quality byte each) of one phase_cells call: DESIGN.md §9's 512 MB
@@ -26,16 +27,24 @@ class PhaseRun:
     """What one run keeps across its blocks: the candidate SNVs (a file with a tabix index: opened, then asked block by block,
     on the device when `device` is given, as the alignment file's reader is; any other file: read once), the renumbering of the
     phase sets and, with snv_phase_sets, the phase sets of the SNV calls (`sets`, a phase_sets.PhaseSets; the renumbering then
-    counts with it)."""
+    counts with it).  With discover_snvs there is no file: `discover` is set, the block paths ask the discovery
+    (frontend/snv_discovery.py) for every block's candidates, and `ref` (the run's Fasta) gives their reference bases."""
 
-    def __init__(self, opts, device: int | None = None):
+    def __init__(self, opts, device: int | None = None, ref=None):
         t0 = time.perf_counter()
+        self.discover = bool(getattr(opts, "discover_snvs", False))
+        self.ref = ref
         self.snvs = (open_snv_candidates(opts.snv_vcf, "host" if device is None else "device", device or 0) if opts.snv_vcf else None)
         self.open_s = time.perf_counter() - t0
         self.sets = PhaseSets() if getattr(opts, "snv_phase_sets", False) else None
         self.remap = pi.PhaseSetRemap(self.sets)
         if self.sets is not None:
             self.sets.remap = self.remap
+
+    @property
+    def has_snvs(self) -> bool:
+        """Whether the run groups reads by SNVs: it has a candidate file, or discovers its candidates."""
+        return self.snvs is not None or self.discover
 
     def close(self, tm: dict | None = None) -> None:
         """Gives the indexed reader's device object back; its stage times (only it has any) go into `tm`."""
@@ -117,6 +126,14 @@ def _gates(loci, opts, kept_locus, realigned, cn) -> np.ndarray:
     return ok
 
 
+def _discovered(run: PhaseRun, loci, cand_off, cand_pos):
+    """The discovered positions of a block in the shape _candidates gives a file's: per locus an object of ContigSnvs' shape that
+    holds that locus's positions alone, and the indices of all of them."""
+    contigs = [DiscoveredSnvs(locus.contig, cand_pos[cand_off[l]:cand_off[l + 1]], run.ref) for l, locus in enumerate(loci)]
+    idx = [np.arange(c.pos.size, dtype=np.int64) for c in contigs]
+    return contigs, idx, np.ascontiguousarray(cand_off, np.int32), np.ascontiguousarray(cand_pos, np.int64)
+
+
 def native_block_phase(run: PhaseRun, opts, loci, bam, rec, item_locus, alt, kept_item, kept_locus, cn_kept, tm) -> BlockPhase:
     """The native path: `rec` / `item_locus` = record and locus of every item, `alt` the substitute alignments, kept_item /
     kept_locus / cn_kept = item, locus and copy number of every kept read (in read order)."""
@@ -127,12 +144,24 @@ def native_block_phase(run: PhaseRun, opts, loci, bam, rec, item_locus, alt, kep
     for l in range(n_loci):
         r = rec[first[l]:first[l + 1]]
         spans.append((int(bam.pos[r].min()), int(bam.end[r].max())) if r.size else (0, 0))
-    contigs, idx, cand_off, cand_pos = _candidates(run, loci, spans)
-    bp = BlockPhase(None, None, contigs=contigs)
     mar = (opts.allele_params or AlleleParams()).min_allele_reads
     realigned = np.array([int(i) in alt for i in kept_item], bool) if alt else np.zeros(len(kept_item), bool)
-    allowed = (_gates(loci, opts, kept_locus, realigned, cn_kept)[kept_locus] if len(kept_item) and run.snvs is not None
+    allowed = (_gates(loci, opts, kept_locus, realigned, cn_kept)[kept_locus] if len(kept_item) and run.has_snvs
                else np.zeros(len(kept_item), bool))
+    if run.discover:
+        # the candidates come from the kept reads of the loci whose gate is open (a closed one gets no kept read, so no candidate)
+        t_b, k_b = time.perf_counter(), bam.kernel_s() if hasattr(bam, "kernel_s") else None
+        found = library_discover_snvs(bam, rec, item_locus, [l.left_flank_coord for l in loci], [l.right_flank_coord for l in loci],
+                                      np.concatenate(([0], np.cumsum(np.bincount(kept_locus[allowed], minlength=n_loci)))), kept_item[allowed],
+                                      alt=alt or None, window=opts.snv_discover_window, min_base_qual=opts.snv_min_base_qual, min_allele_reads=mar,
+                                      clip_threshold=opts.significant_clip_threshold)
+        contigs, idx, cand_off, cand_pos = _discovered(run, loci, *found)
+        tm["snv_discover_s"] = tm.get("snv_discover_s", 0.0) + time.perf_counter() - t_b
+        if k_b is not None:
+            tm["snv_discover_device_s"] = tm.get("snv_discover_device_s", 0.0) + bam.kernel_s() - k_b
+    else:
+        contigs, idx, cand_off, cand_pos = _candidates(run, loci, spans)
+    bp = BlockPhase(None, None, contigs=contigs)
     # The cells of one call stay within MAX_CELLS: the loci are cut into pieces (a locus is never cut; one locus alone has at most
     # max_reads x 1 024 cells) and every piece makes its own pair of calls.  The result does not depend on the cut.
     per_locus = np.bincount(item_locus, minlength=n_loci).astype(np.int64) * np.diff(cand_off)
@@ -154,7 +183,7 @@ def native_block_phase(run: PhaseRun, opts, loci, bam, rec, item_locus, alt, kep
         tm["phase_cells_s"] = tm.get("phase_cells_s", 0.0) + time.perf_counter() - t_b
         mine = (kept_locus >= l0) & (kept_locus < l1)
         hp[mine], ps[mine] = cells["hp"][kept_item[mine] - i0], cells["ps"][kept_item[mine] - i0]
-        if run.snvs is not None:
+        if run.has_snvs:
             t_b = time.perf_counter()
             use = mine & allowed
             kept_off = np.concatenate(([0], np.cumsum(np.bincount(kept_locus[use] - l0, minlength=l1 - l0)))).astype(np.int32)
@@ -162,7 +191,7 @@ def native_block_phase(run: PhaseRun, opts, loci, bam, rec, item_locus, alt, kep
             tm["useful_snvs_s"] = tm.get("useful_snvs_s", 0.0) + time.perf_counter() - t_b
     if opts.use_hp:
         bp.hp, bp.ps = hp, run.remap(ps, hp)
-    if run.snvs is not None:
+    if run.has_snvs:
         bp.snv_off = np.concatenate(([0], np.cumsum(np.concatenate([np.diff(u["snv_off"]) for u in parts])))).astype(np.int32)
         bp.snv_base, bp.snv_qual = (np.concatenate([u[k] for u in parts]) for k in ("snv_base", "snv_qual"))
         snv_cand = np.concatenate([u["snv_cand"] for u in parts])
@@ -177,16 +206,28 @@ def python_block_phase(run: PhaseRun, opts, loci, entries_of, kept_of, tm) -> Bl
     the locus (segment, realigned, copy number), in read order."""
     t_a = time.perf_counter()
     spans = [((min(s.start for s, _ in e), max(s.end for s, _ in e)) if e else (0, 0)) for e in entries_of]
-    contigs, idx, cand_off, cand_pos = _candidates(run, loci, spans)
-    hp, ps, bases, quals, sels = [], [], [], [], []
     mar = (opts.allele_params or AlleleParams()).min_allele_reads
+    if run.discover:
+        t_b = time.perf_counter()
+        found = []
+        for locus, entries, kept in zip(loci, entries_of, kept_of):
+            ok = bool(kept) and _gates([locus], opts, np.zeros(len(kept), np.int64), np.array([k[1] for k in kept], bool),
+                                       np.array([k[2] for k in kept], np.int64))[0]
+            found.append(discover_candidates(entries, kept, locus.left_flank_coord, locus.right_flank_coord, opts.snv_discover_window,
+                                             opts.snv_min_base_qual, mar, opts.significant_clip_threshold, allowed=ok))
+        contigs, idx, cand_off, cand_pos = _discovered(run, loci, np.concatenate(([0], np.cumsum([f.size for f in found]))),
+                                                       np.concatenate(found + [np.zeros(0, np.int64)]))
+        tm["snv_discover_s"] = tm.get("snv_discover_s", 0.0) + time.perf_counter() - t_b
+    else:
+        contigs, idx, cand_off, cand_pos = _candidates(run, loci, spans)
+    hp, ps, bases, quals, sels = [], [], [], [], []
     for l, (locus, kept) in enumerate(zip(loci, kept_of)):
         cand = cand_pos[cand_off[l]:cand_off[l + 1]]
         for seg, _re, _cn in kept:
             h, p = pi.read_tags(seg.tags)
             hp.append(h)
             ps.append(p)
-        if run.snvs is None:
+        if not run.has_snvs:
             continue
         cells = [pi.alignment_cells(np.zeros(0, np.uint32), 0, "", None, cand) if re_ else
                  pi.segment_cells(seg, cand, clip_threshold=opts.significant_clip_threshold) for seg, re_, _cn in kept]
@@ -202,7 +243,7 @@ def python_block_phase(run: PhaseRun, opts, loci, entries_of, kept_of, tm) -> Bl
     if opts.use_hp:
         bp.hp = np.array(hp, np.int32)
         bp.ps = run.remap(np.array(ps, np.int32), bp.hp)
-    if run.snvs is not None:
+    if run.has_snvs:
         bp.snv_off, bp.snv_base, bp.snv_qual = pi.pack_cells(bases, quals, sels)
         bp.snv_rec = np.concatenate([idx[l][s] for l, s in enumerate(sels)] + [np.zeros(0, np.int64)]).astype(np.int64)
     tm["phase_inputs_s"] = tm.get("phase_inputs_s", 0.0) + time.perf_counter() - t_a
